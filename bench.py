@@ -62,7 +62,7 @@ def free_port():
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=40)
+    ap.add_argument("--steps", type=int, default=40, help="LM iterations of every timed block: each block runs exactly this many from the same prepared state")
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--workload", default="auto", choices=["auto"] + sorted(WORKLOADS))
     ap.add_argument("--frames", type=int, default=0, help="override the workload's total frame count")
@@ -73,6 +73,11 @@ def main():
                     help="multi-rank runs: rccl = one GPU per rank, the library's own RCCL communicator (auto: the same); gloo = torch.distributed "
                          "gloo + the FrameShardComm callback, ranks share the visible device(s) -- executes the whole multi-rank branch of this "
                          "script on a one-GPU box (a functional check, not a scaling measurement)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed blocks, write what the last one computed as DIR/<name>.npy (float64): the solved state (cameras, "
+                         "frame poses and, with the IMU, velocities, biases, scale factors, gravity, time offset), its LM trace rows, the cost "
+                         "of that state and, with the IMU, its IMU weights and IMU blocks (a fixed seeded sample of the frames / blocks on large "
+                         "problems; at most 64 MB in all).  The same arguments give the same inputs on every run")
     args = ap.parse_args()
     gloo = args.transport == "gloo"
 
@@ -214,6 +219,8 @@ def main():
     block_dt = []; block_local = []
     done = jac_sweeps = res_sweeps = 0
     for _ in range(max(1, args.repeats)):
+        if args.dump_outputs:
+            trace_mark = len(cal.trace())       # where the block's rows will start (outside the timed region)
         barrier()
         t0 = time.perf_counter()
         done, jac_sweeps, res_sweeps = cal.run_iterations(args.steps)
@@ -225,6 +232,8 @@ def main():
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             d = float(tt.item())
         block_dt.append(d)
+    if args.dump_outputs:
+        dump_outputs(cal, trace_mark, vi, args.dump_outputs, rank, world)
     dt = float(np.median(block_dt))
     per_rank_ms = None
     if world > 1:
@@ -443,6 +452,63 @@ def main():
             pass
         sys.stdout.flush(); sys.stderr.flush()
         os._exit(0)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+NPY_HEADER_BYTES = 256          # allowance per file for the .npy header (numpy pads it to a multiple of 64 bytes, 128 for these arrays)
+
+
+def _rows_within(n, row_bytes, budget):
+    """All n rows, or a fixed seeded sample of as many as fit into budget bytes (sorted)."""
+    if n * row_bytes <= budget:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(0).choice(n, max(budget // row_bytes, 0), replace=False))
+
+
+def dump_outputs(cal, trace_mark, vi, out_dir, rank, world):
+    """--dump-outputs: what the last timed block computed, one float64 .npy per array (names get _rank<r> with several ranks).
+    The solved state (the getters' values after vc_download_state -- the LM iterations themselves leave it on the device):
+      camera<c>_params, camera<c>_T_ck   intrinsics and camera-to-IMU transform of every camera
+      frame_poses (N x 7), frame_rows    T_wk of the frames; frame_rows says which frames: all, or a fixed seeded sample where the
+                                         whole dump would exceed 64 MB (shared by the ranks)
+      frame_velocities (N x 3)           with the IMU, of the same frames
+      imu_biases, imu_scale_factors, gravity, time_offset                  with the IMU
+    What the block computed on the way there:
+      trace               LM trace rows of the block (iteration, cost, cost change, max |g|, |g|, |step|, rho, radius, accepted, stage)
+      state_cost          [cost, sum of squares] of the reprojection residuals at the final state (a fresh residual sweep)
+      imu_weights         per IMU block: the 9 x 9 weight factor W the last pass used
+      imu_block_hessian   per IMU block: weighted J^T J (33 x 33), imu_block_gradient: J^T r (33), imu_block_cost
+      imu_block_rows      which IMU blocks the four arrays above hold (all, or a fixed seeded sample as for the frames)"""
+    os.makedirs(out_dir, exist_ok=True)
+    cal.download_state()
+    cost, sum_sq = cal.evaluate()
+    arrays = {"trace": cal.trace()[trace_mark:], "state_cost": np.array([cost, sum_sq])}
+    for c in range(cal.NumCameras()):
+        arrays["camera%d_params" % c], arrays["camera%d_T_ck" % c] = cal.GetCamera(c)
+    if vi:
+        arrays.update({"imu_biases": cal.GetBiases(), "imu_scale_factors": cal.GetScaleFactor(), "gravity": cal.GetGravity(),
+                       "time_offset": np.array([cal.time_offset()])})
+    n_frames = cal.NumFrames()
+    n_blocks = max(n_frames - 1, 0) if vi else 0
+    frame_bytes = 8 * (7 + (3 if vi else 0) + 1)                       # pose, velocity, row index
+    block_bytes = 8 * (81 + 33 * 33 + 33 + 1 + 1)                       # weight, J^T J, J^T r, cost, row index
+    n_files = len(arrays) + (3 if vi else 2) + (5 if vi else 0)
+    room = DUMP_LIMIT_BYTES // world - n_files * NPY_HEADER_BYTES - sum(np.asarray(a).nbytes for a in arrays.values())
+    if n_frames * frame_bytes + n_blocks * block_bytes <= room:
+        f_rows, b_rows = np.arange(n_frames), np.arange(n_blocks)
+    else:                                                               # half of the room each (what one of them leaves goes to the other)
+        f_rows = _rows_within(n_frames, frame_bytes, max(room // 2, room - n_blocks * block_bytes))
+        b_rows = _rows_within(n_blocks, block_bytes, room - len(f_rows) * frame_bytes)
+    arrays["frame_rows"] = f_rows.astype(np.float64)
+    arrays["frame_poses"] = np.array([cal.GetFrame(int(f))[0] for f in f_rows]).reshape(-1, 7)
+    if vi:
+        arrays["frame_velocities"] = np.array([cal.GetFrame(int(f))[1] for f in f_rows]).reshape(-1, 3)
+        H, g, bc = cal.imu_blocks()
+        arrays.update({"imu_block_rows": b_rows.astype(np.float64), "imu_weights": cal.imu_weights()[b_rows], "imu_block_hessian": H[b_rows],
+                       "imu_block_gradient": g[b_rows], "imu_block_cost": bc[b_rows]})
+    suffix = "_rank%d" % rank if world > 1 else ""
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def secondary(device):

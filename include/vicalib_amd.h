@@ -199,6 +199,9 @@ int vc_shared_dim(vc_calibrator* h);
 /* Runs exactly `iters` LM iterations of the real solver (complete solves back to back from the uploaded
  * initial state, the last one cut short); returns the number of iterations run (>= 0) or an error. */
 int vc_run_iterations(vc_calibrator* h, int iters, int* jac_sweeps, int* res_sweeps);
+/* Copies the device's accepted state -- where vc_run_iterations left it -- into what vc_get_camera, vc_get_frame, vc_get_biases,
+ * vc_get_scale_factor, vc_get_gravity and vc_time_offset return (a solve does this itself when it ends; vc_run_iterations does not). */
+int vc_download_state(vc_calibrator* h);
 /* Per-tile reprojection residual sweep on the accepted state: cost (1/2 sum rho) and sum of squares */
 int vc_evaluate(vc_calibrator* h, double* cost, double* sum_sq);
 /* Times the dominant kernels with HIP events on the calibrator's stream: average ms per launch over reps */

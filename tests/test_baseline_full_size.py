@@ -3,7 +3,9 @@
 at these sizes, so the checks are size-independent properties (complete stage schedule, falling accepted costs, generator
 ground truth recovered, RMSE at the noise floor) plus: the frame-sharded solve (4 / 8 ranks, the partition BASELINE names) must
 reproduce the single-process solve -- every iteration's cost and accept / reject decision, the shared parameters, the frames --
-at 1e-7.  All ranks share the one GPU of the test box (gloo all-reduces); the same code path runs over RCCL on 4 / 8 GPUs."""
+at 1e-7.  All ranks share the one GPU of the test box (gloo all-reduces); the same code path runs over RCCL on 4 / 8 GPUs.  The
+ranks run in at most four worker processes (cfg5: two ranks per process), so that with this one at most five processes have the
+GPU open at a time."""
 import os
 import socket
 import subprocess
@@ -78,22 +80,24 @@ def test_cfg5_full_size_single_gpu(tmp_path_factory):
     _check_properties(p, r, 8)
 
 
-def _run_sharded(name, ref_path, nproc, timeout):
+def _run_sharded(name, ref_path, n_ranks, nproc, timeout, tmp_path_factory):
+    """n_ranks ranks in nproc worker processes (n_ranks / nproc threads each, every rank with a calibrator of its own)."""
+    store = str(tmp_path_factory.mktemp("store") / "store")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(nproc), "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(HERE, "full_size_worker.py"), name, ref_path]
+           "--master-port", str(_free_port()), os.path.join(HERE, "full_size_worker.py"), name, ref_path, str(n_ranks), store]
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=timeout)
     fail = out.stdout.find("WORKER-FAILURE")
     assert out.returncode == 0, (out.stdout[fail:fail + 7000] if fail >= 0 else out.stdout[-3000:] + out.stderr[-3000:])
-    assert out.stdout.count("ok") >= nproc
+    assert all(("rank %d ok" % r) in out.stdout for r in range(n_ranks)), out.stdout[-3000:]
 
 
 def test_cfg4_full_size_sharded_over_4_ranks_matches_single(tmp_path_factory):
     _, _, path = _single("cfg4", tmp_path_factory)
-    _run_sharded("cfg4", path, 4, 900)
+    _run_sharded("cfg4", path, 4, 4, 900, tmp_path_factory)
 
 
 def test_cfg5_full_size_sharded_over_8_ranks_matches_single(tmp_path_factory):
     """Reduced dimension 115 + 7 x 9 = 178 (packed-triangle reduced solve, 12 column tiles in the chain Gram)."""
     _, _, path = _single("cfg5", tmp_path_factory)
-    _run_sharded("cfg5", path, 8, 900)
+    _run_sharded("cfg5", path, 8, 4, 900, tmp_path_factory)

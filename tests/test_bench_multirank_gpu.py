@@ -8,6 +8,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -63,3 +64,50 @@ def test_one_rank_through_the_library_rccl_communicator_reports_what_rccl_saw():
     assert comm["transport"] == "rccl" and comm["rccl_error"] is None
     assert comm["communicator_size"] == 1 and comm["rccl_ranks_seen"] == [1, 1] and comm["ranks_agree"] is True
     assert comm["allreduce_calls"] > 0
+
+
+def _dump(out_dir, *extra):
+    out, _ = _bench("--steps", "3", "--warmup", "1", "--repeats", "2", "--no-cpu-baseline", "--no-secondary", "--dump-outputs", str(out_dir), *extra)
+    assert out["steps"] == 3
+    files = {p.name[:-4]: np.load(p) for p in out_dir.iterdir()}
+    assert all(p.name.endswith(".npy") for p in out_dir.iterdir())
+    assert all(a.dtype == np.float64 and np.all(np.isfinite(a)) for a in files.values())
+    assert sum(p.stat().st_size for p in out_dir.iterdir()) <= 64 << 20
+    tr = files["trace"]
+    assert tr.shape[1] == 10 and int(np.sum(tr[:, 0] > 0)) == 3 and np.all(tr[:, 9] == tr[-1, 9])     # three iterations, one stage
+    assert files["state_cost"].shape == (2,) and files["state_cost"][0] > 0
+    return files
+
+
+def test_dump_outputs_hold_what_the_last_timed_block_computed(tmp_path):
+    """--dump-outputs DIR: float64 arrays of the last timed block of cfg3 -- the solved state it ended in, its trace rows (exactly --steps
+    LM iterations), the cost of that state, the IMU weights and blocks (small enough to be written whole).  Two runs with the same
+    arguments write the same bits."""
+    files = _dump(tmp_path / "a")
+    n = 2000                                                                                   # cfg3: 2000 frames, one camera
+    assert set(files) == {"trace", "state_cost", "camera0_params", "camera0_T_ck", "imu_biases", "imu_scale_factors", "gravity", "time_offset",
+                          "frame_rows", "frame_poses", "frame_velocities",
+                          "imu_block_rows", "imu_weights", "imu_block_hessian", "imu_block_gradient", "imu_block_cost"}
+    assert files["camera0_params"].ndim == 1 and len(files["camera0_params"]) > 0 and files["camera0_T_ck"].shape == (7,)
+    assert files["imu_biases"].shape == (6,) and files["imu_scale_factors"].shape == (6,) and files["gravity"].shape == (2,)
+    assert files["time_offset"].shape == (1,)
+    np.testing.assert_array_equal(files["frame_rows"], np.arange(n))
+    assert files["frame_poses"].shape == (n, 7) and files["frame_velocities"].shape == (n, 3)
+    np.testing.assert_allclose(np.linalg.norm(files["frame_poses"][:, :4], axis=1), 1.0, rtol=1e-9)      # unit quaternions
+    np.testing.assert_array_equal(files["imu_block_rows"], np.arange(n - 1))
+    assert files["imu_weights"].shape == (n - 1, 9, 9) and files["imu_block_hessian"].shape == (n - 1, 33, 33)
+    assert files["imu_block_gradient"].shape == (n - 1, 33) and files["imu_block_cost"].shape == (n - 1,)
+    again = _dump(tmp_path / "b")
+    assert set(again) == set(files)
+    for k in files:
+        np.testing.assert_array_equal(again[k], files[k], err_msg=k)
+
+
+def test_dump_outputs_vision_only_state_is_the_one_the_trace_ends_in(tmp_path):
+    """cfg2 (no IMU): the reprojection cost of the dumped state, swept afresh, is the cost the trace of the block ends with (the last
+    accepted row) -- the state is the one the timed iterations left on the device, not an earlier copy."""
+    files = _dump(tmp_path, "--workload", "cfg2")
+    assert set(files) == {"trace", "state_cost", "camera0_params", "camera0_T_ck", "camera1_params", "camera1_T_ck", "frame_rows", "frame_poses"}
+    assert files["frame_poses"].shape == (500, 7)
+    tr = files["trace"]
+    np.testing.assert_allclose(files["state_cost"][0], tr[tr[:, 8] == 1][-1, 1], rtol=1e-9)

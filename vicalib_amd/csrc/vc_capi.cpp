@@ -629,6 +629,12 @@ int vc_run_iterations(vc_calibrator* h, int iters, int* jac_sweeps, int* res_swe
   if (res_sweeps) *res_sweeps = (int)(h->res_sweeps - r0);
   return rc ? rc : done;
 }
+int vc_download_state(vc_calibrator* h) {
+  NOT_RUNNING(h);
+  BIND_DEVICE(h);
+  if (h->device_dirty) return VC_OK;      // nothing uploaded since the last change: the host copies are the state
+  return h->download_state();
+}
 int vc_time_kernels(vc_calibrator* h, int reps, double* jac_ms, double* res_ms) {
   NOT_RUNNING(h);
   BIND_DEVICE(h);

@@ -85,6 +85,9 @@ __global__ __launch_bounds__(256) void k_imu_jac(DevView v, int wr, int trial) {
   // (round 6 also tried requesting everything ahead of the control record -- the two frames' states and the gravity record of BOTH state
   //  buffers, one value per lane, the buffer in use to LDS --: 23.1 us against 21.4 on the same box, reverted)
   IJSTAMP(0);
+  // (vc_kutil.hpp: a void pass's trial kernels may run ahead of the previous decision -- nothing stored, not counted either: k_final of a
+  //  void pass does not wait for the counts)
+  if (trial && v.sync_seq > 0 && workgroup_pass_void(v)) return;
   const Ctrl* ct = v.ctrl;
   if (ct->done || (!trial && !ct->need_lin)) {
     // (a finished solve: the workgroup still counts itself in the second count -- k_final of this pass waits for it, so that the main
@@ -417,6 +420,7 @@ __global__ __launch_bounds__(256, VC_IMU_BLOCK_WAVES) void k_imu_block(DevView v
   __shared__ double s_parkv[4 * 8 * 11];
 #endif
   IBSTAMP(0);
+  if (trial && v.sync_seq > 0 && workgroup_pass_void(v)) return;      // (vc_kutil.hpp: a void pass's trial kernels may run ahead of the previous decision)
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);      // (scalar: everything per block stays out of the vector registers)
   const int g = lane >> 3, l = lane & 7;
   const int n_blocks = v.n_frames - 1;

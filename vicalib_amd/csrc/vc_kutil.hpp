@@ -117,6 +117,19 @@ __device__ __forceinline__ void mark_sync_timeout(const DevView& v, long long se
   if (!__hip_atomic_compare_exchange_strong(v.sync_flags + 6, &expect, seq, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
     __hip_atomic_fetch_min(v.sync_flags + 6, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
+// A trial-point kernel of the second stream (k_imu_block / k_imu_jac in trial mode) of a pass that is void already stores nothing.  The
+// only thing that holds the second stream of pass p behind the previous pass's decision is p's own wait for k_final(p - 1); a wait that
+// gave up (or returned because p was marked) lets those kernels run while k_final(p - 1) is still deciding, with the control record not
+// yet moved on -- their "trial side" (1 - cur) is then the previous pass's trial side: they would overwrite the IMU records and trial
+// costs that decision reads and, if it accepts, makes the linearisation the resumed pass keeps (computed with the weights one update
+// behind: k_imu_weights of the void pass stored nothing).  Uniform over the workgroup: the word may move while the kernel starts.
+// Call from all threads, only where v.sync_seq > 0 (a kernel argument: the barrier is reached by every thread or by none).
+__device__ __forceinline__ bool workgroup_pass_void(const DevView& v) {
+  __shared__ int s_void;
+  if (threadIdx.x == 0) { const long long m = sync_marked(v); s_void = (m != 0 && m <= v.sync_seq) ? 1 : 0; }
+  __syncthreads();
+  return s_void != 0;
+}
 // (relaxed polls, ONE acquire at the end: an acquire load per poll invalidates the CU's L1 every time round -- 2-3x slower per hop; the
 //  flag and the sticky word are requested together: one memory round trip per poll.)  ACQ = false: the waiting thread reads nothing of
 //  what the flag publishes itself (k_imu_block's thread, which only holds its kernel's end back: the next kernel's start acquires).
