@@ -196,6 +196,17 @@ int vc_prepare(vc_calibrator* h);
 int vc_linearize(vc_calibrator* h, double* cost, double* Hpp, double* gp, double* S, double* g_red,
                  double* hss_diag, double* g_s);
 int vc_shared_dim(vc_calibrator* h);
+/* One LM pass at the current state with trust-region radius `radius` and the decision withheld (the state does not move; like
+ * vc_linearize, every rank of a sharded calibrator calls it), then copies of what the pass left (any pointer may be NULL):
+ *   cost at the linearisation point; the step of the shared parameters delta_s (D) and their damping lambda_s (D);
+ *   the frames' damping (n x 9: pose 6, velocity 3 with the IMU; vision-only passes fill the first 6 of each row);
+ *   the trial state the pass formed, in vc_get_frame / vc_get_camera layout: poses (n x 7, [q(4) t(3)]), velocities (n x 3),
+ *   cameras (n_cams x 17: T_ck(7), then the intrinsics padded to 10), IMU parameters (15: g(2) b(6) sf(6) time offset(1)).
+ * Velocities and IMU parameters are zero without inertial terms.  The frames' own steps are not stored by every form of the pass
+ * (vision-only passes form them in registers): they are available only through the trial state.  On a sharded calibrator the
+ * frames are this rank's, separators included, and delta_s holds the separators' steps at their columns. */
+int vc_step_hold(vc_calibrator* h, double radius, double* cost, double* delta_s, double* slam, double* frame_lam, double* poses,
+                 double* vels, double* cams, double* imus);
 /* Runs exactly `iters` LM iterations of the real solver (complete solves back to back from the uploaded
  * initial state, the last one cut short); returns the number of iterations run (>= 0) or an error. */
 int vc_run_iterations(vc_calibrator* h, int iters, int* jac_sweeps, int* res_sweeps);

@@ -169,6 +169,19 @@ int vco_solve_normal(void* h, const double* lam, int dense, double* dfv, double*
   std::memcpy(dfv, a.data(), a.size() * 8); if (!b.empty()) std::memcpy(dsv, b.data(), b.size() * 8);
   return 0;
 }
+// The damping solve_once uses in the first iteration of a solve that starts at the current linearisation (after vco_linearize) with
+// trust-region radius `radius`; lam: N*9 + D, the solve_normal indexing.
+void vco_lm_lambda(void* h, double radius, double* lam) {
+  std::vector<double> hd, s2, diag, l;
+  CAL->hdiag(hd); CAL->jacobi_scale2(hd, s2); CAL->clamped_diag(hd, s2, diag); Calibrator::lm_lambda(diag, s2, radius, l);
+  std::memcpy(lam, l.data(), l.size() * 8);
+}
+// The trial update solve_once applies (manifold plus for poses and q_ck, additive for the rest): the state moves by (dfv: N x 9, dsv: D).
+void vco_apply_step(void* h, const double* dfv, const double* dsv) {
+  std::vector<double> a(dfv, dfv + (size_t)CAL->N() * 9), b(dsv, dsv + CAL->L.D);
+  double s2, x2;
+  CAL->apply_step(a, b, &s2, &x2);
+}
 // Per-observation residuals (sorted order) and the sorted (frame, cam) keys.
 int vco_num_obs(void* h) { return (int)CAL->obs.size(); }
 void vco_residuals(void* h, double* r, int* frame, int* cam) {

@@ -507,6 +507,21 @@ class Calibrator {
     *gmax = m; *g2 = std::sqrt(s);
   }
 
+  // LevenbergMarquardtStrategy's damping, in the lam indexing: Jacobi scale^2 = 1 / (1 + sqrt(h_ii))^2 (fixed per solve), the scaled
+  // diagonal clamped to [min_diag, max_diag] (kept while reuse_diagonal), lam = diag / (radius * scale^2)
+  void jacobi_scale2(const std::vector<double>& hd, std::vector<double>& s2) const {
+    s2.assign(hd.size(), 1.0);
+    if (opt.jacobi_scaling) for (size_t i = 0; i < hd.size(); ++i) { const double s = 1.0 / (1.0 + std::sqrt(hd[i])); s2[i] = s * s; }
+  }
+  void clamped_diag(const std::vector<double>& hd, const std::vector<double>& s2, std::vector<double>& diag) const {
+    diag.resize(hd.size());
+    for (size_t i = 0; i < hd.size(); ++i) diag[i] = std::min(std::max(hd[i] * s2[i], opt.min_diag), opt.max_diag);
+  }
+  static void lm_lambda(const std::vector<double>& diag, const std::vector<double>& s2, double radius, std::vector<double>& lam) {
+    lam.resize(diag.size());
+    for (size_t i = 0; i < lam.size(); ++i) lam[i] = diag[i] / (radius * s2[i]);
+  }
+
   // ---- the trust-region (Levenberg-Marquardt) loop ---------------------------------
   // Restates ceres::internal::TrustRegionMinimizer + LevenbergMarquardtStrategy
   // with the reference's options (vicalibrator.h:141-151) except the strategy
@@ -519,9 +534,9 @@ class Calibrator {
     for (const Obs& o : obs) nres += 2 * std::max(0, vis_mult + o.mult_delta);
     if (L.imu) nres += (long)9 * imu_mult * std::max(0, n - 1);
     *num_residual_scalars = (int)nres;
-    std::vector<double> hd, scale2((size_t)n * 9 + D, 1.0), lam((size_t)n * 9 + D, 0.0), diag;
+    std::vector<double> hd, scale2, lam((size_t)n * 9 + D, 0.0), diag;
     hdiag(hd);
-    if (opt.jacobi_scaling) for (size_t i = 0; i < hd.size(); ++i) { const double s = 1.0 / (1.0 + std::sqrt(hd[i])); scale2[i] = s * s; }
+    jacobi_scale2(hd, scale2);
     double radius = opt.initial_radius, decrease_factor = 2.0;
     bool reuse_diagonal = false;
     double gmax, gnorm;
@@ -538,11 +553,8 @@ class Calibrator {
       ++iter;
       IterRecord rec = {iter, cost, 0, gmax, gnorm, 0, 0, radius, 0, stage};
       // LevenbergMarquardtStrategy::ComputeStep
-      if (!reuse_diagonal) {
-        diag = hd;
-        for (size_t i = 0; i < diag.size(); ++i) diag[i] = std::min(std::max(diag[i] * scale2[i], opt.min_diag), opt.max_diag);
-      }
-      for (size_t i = 0; i < lam.size(); ++i) lam[i] = diag[i] / (radius * scale2[i]);
+      if (!reuse_diagonal) clamped_diag(hd, scale2, diag);
+      lm_lambda(diag, scale2, radius, lam);
       reuse_diagonal = true;
       std::vector<double> dfv, dsv;
       bool ok = opt.dense_check ? solve_dense(lam, dfv, dsv) : solve_blocks(lam, dfv, dsv);

@@ -192,6 +192,19 @@ class Oracle:
         assert rc == 0
         return dfv, dsv[:D]
 
+    def lm_lambda(self, radius):
+        """The damping the oracle's solve_once forms in the first iteration of a solve from the current linearisation (N*9 + D)."""
+        out = np.zeros(self.n_frames * 9 + self.L.vco_layout_D(self.h))
+        self.L.vco_lm_lambda(self.h, C.c_double(radius), _d(out))
+        return out
+
+    def apply_step(self, dfv, dsv):
+        """Moves the state by the step (dfv: N x 9, dsv: D) with solve_once's update (manifold plus for poses and q_ck)."""
+        D = self.L.vco_layout_D(self.h)
+        dfv = np.ascontiguousarray(dfv, dtype=np.float64).reshape(self.n_frames, 9)
+        dsv = np.ascontiguousarray(np.resize(np.asarray(dsv, dtype=np.float64), max(D, 1)))
+        self.L.vco_apply_step(self.h, _d(dfv), _d(dsv))
+
     def residuals(self):
         n = self.L.vco_num_obs(self.h)
         r = np.zeros((n, 2)); f = np.zeros(n, dtype=np.int32); c = np.zeros(n, dtype=np.int32)
@@ -225,6 +238,11 @@ class Oracle:
         out = np.zeros((max(self.n_frames - 1, 0), 9, 9))
         self.L.vco_get_imu_weights(self.h, _d(out))
         return out
+
+    def set_imu_weights(self, W):
+        """Installs weight_sqrt_ factors ((N - 1) x 9 x 9), e.g. the ones a device pass linearised with."""
+        W = np.ascontiguousarray(W, dtype=np.float64).reshape(max(self.n_frames - 1, 0), 9, 9)
+        self.L.vco_set_imu_weights(self.h, _d(W))
 
     def compute_rmse(self):
         self.L.vco_compute_rmse(self.h)

@@ -588,6 +588,52 @@ int vc_linearize(vc_calibrator* h, double* cost, double* Hpp, double* gp, double
   if (g_s) std::memcpy(g_s, sb.data() + (size_t)D * D + 2 * D, D * 8);
   return VC_OK;
 }
+int vc_step_hold(vc_calibrator* h, double radius, double* cost, double* delta_s, double* slam, double* frame_lam, double* poses,
+                 double* vels, double* cams, double* imus) {
+  NOT_RUNNING(h);
+  BIND_DEVICE(h);
+  if (!(radius > 0.0)) return VC_ERR_BAD_ARG;
+  if (h->device_dirty) { int rc = vc_prepare(h); if (rc) return rc; }
+  double lin_cost = 0;
+  int rc = h->linearize_hold(radius, &lin_cost); if (rc) return rc;
+  // read-outs only: every buffer below is what the held pass left (the decision on hold keeps `cur`, the trial state is in 1 - cur)
+  const int N = h->dv.n_frames, C = h->dv.n_cams, D = h->dv.D, tr = 1 - h->cur;
+  auto get = [&](double* dst, const double* src, size_t n) { return !dst || !n || hipMemcpy(dst, src, n * 8, hipMemcpyDeviceToHost) == hipSuccess; };
+  if (cost) *cost = lin_cost;
+  if (!get(delta_s, h->dv.delta_s, D) || !get(slam, h->dv.slam, D)) return VC_ERR_NO_DEVICE;
+  if (frame_lam && N) {
+    if (h->dv.imu_on) { if (!get(frame_lam, h->dv.clam, (size_t)N * 9)) return VC_ERR_NO_DEVICE; }
+    else {
+      std::vector<double> fr((size_t)N * kFrStride);
+      if (!get(fr.data(), h->dv.fr, fr.size())) return VC_ERR_NO_DEVICE;
+      for (int f = 0; f < N; ++f) for (int i = 0; i < 9; ++i) frame_lam[(size_t)f * 9 + i] = i < 6 ? fr[(size_t)f * kFrStride + kFrLam + i] : 0.0;
+    }
+  }
+  if ((poses || vels) && N) {
+    std::vector<double> p((size_t)N * kPoseStride), w((size_t)N * 4, 0.0);
+    if (!get(p.data(), h->dv.poses[tr], p.size())) return VC_ERR_NO_DEVICE;
+    if (h->dv.imu_on && !get(w.data(), h->dv.vel[tr], w.size())) return VC_ERR_NO_DEVICE;
+    for (int f = 0; f < N; ++f) {
+      if (poses) std::memcpy(poses + 7 * (size_t)f, &p[(size_t)f * kPoseStride], 56);
+      if (vels) std::memcpy(vels + 3 * (size_t)f, &w[(size_t)f * 4], 24);
+    }
+  }
+  if (cams && C) {
+    std::vector<double> cr((size_t)C * kCamStride);
+    if (!get(cr.data(), h->dv.cams[tr], cr.size())) return VC_ERR_NO_DEVICE;
+    for (int c = 0; c < C; ++c) {
+      double* o = cams + 17 * (size_t)c;
+      std::memcpy(o, &cr[(size_t)c * kCamStride], 56);
+      for (int i = 0; i < 10; ++i) o[7 + i] = i < h->cams[c].nk ? cr[(size_t)c * kCamStride + kCamK + i] : 0.0;
+    }
+  }
+  if (imus) {
+    double r[16] = {0};
+    if (h->dv.imu_on && !get(r, h->dv.imus[tr], 16)) return VC_ERR_NO_DEVICE;
+    std::memcpy(imus, r, 15 * 8);
+  }
+  return VC_OK;
+}
 int vc_evaluate(vc_calibrator* h, double* cost, double* sum_sq) {
   NOT_RUNNING(h);
   BIND_DEVICE(h);

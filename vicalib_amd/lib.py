@@ -28,7 +28,7 @@ SYMBOLS = [
     "vc_solve", "vc_start", "vc_resume", "vc_set_stage_limit", "vc_sync_timeouts", "vc_set_kernel_timing", "vc_get_kernel_timing", "vc_is_running", "vc_stop", "vc_num_frames", "vc_num_cameras", "vc_get_camera", "vc_get_frame",
     "vc_get_biases", "vc_get_scale_factor", "vc_get_gravity", "vc_time_offset", "vc_mean_squared_error", "vc_get_camera_proj_rmse",
     "vc_get_num_iterations", "vc_num_imu_measurements", "vc_get_imu_measurements", "vc_get_integration_poses", "vc_print_results", "vc_write_camera_models", "vc_trace_len", "vc_get_trace", "vc_set_shard", "vc_get_stream", "vc_prepare",
-    "vc_linearize", "vc_shared_dim", "vc_run_iterations", "vc_download_state", "vc_evaluate", "vc_time_kernels", "vc_time_stages", "vc_get_imu_blocks", "vc_get_debug_stamps", "vc_num_observations", "vc_num_tiles",
+    "vc_linearize", "vc_step_hold", "vc_shared_dim", "vc_run_iterations", "vc_download_state", "vc_evaluate", "vc_time_kernels", "vc_time_stages", "vc_get_imu_blocks", "vc_get_debug_stamps", "vc_num_observations", "vc_num_tiles",
     "vc_init_frame_poses_pnp", "vc_pnp_planar", "vc_pnp_planar_ransac", "vc_set_pnp_ransac", "vc_rccl_unique_id", "vc_set_shard_rccl", "vc_shard_comm_create", "vc_set_shard_comm", "vc_shard_comm_destroy", "vc_allreduce_calls", "vc_shard_info", "vc_pass_paths", "vc_last_error", "vc_get_imu_weights",
     "vc_solution_covariance_dim", "vc_get_solution_covariance", "vc_get_solution_covariance_names",
     "vc_target_make_pattern", "vc_target_find",
@@ -363,6 +363,15 @@ class ViCalibrator:
         cost = C.c_double(0); H = np.zeros((n, 6, 6)); g = np.zeros((n, 6)); S = np.zeros((D, D)); gr = np.zeros(D); hd = np.zeros(D); gs = np.zeros(D)
         _check(self.L.vc_linearize(self.h, C.byref(cost), _d(H), _d(g), _d(S), _d(gr), _d(hd), _d(gs)), "linearize")
         return dict(cost=cost.value, Hpp=H, gp=g, S=S, g_red=gr, hss_diag=hd, g_s=gs)
+
+    def step_hold(self, radius):
+        """One LM pass at the current state with the decision withheld (vc_step_hold): the step it formed and the trial state, read out."""
+        self.prepare()
+        n, D, nc = self.NumFrames(), self.shared_dim(), self.NumCameras()
+        cost = C.c_double(0); ds = np.zeros(max(D, 1)); sl = np.zeros(max(D, 1)); fl = np.zeros((n, 9))
+        T = np.zeros((n, 7)); v = np.zeros((n, 3)); cams = np.zeros((max(nc, 1), 17)); imus = np.zeros(15)
+        _check(self.L.vc_step_hold(self.h, C.c_double(radius), C.byref(cost), _d(ds), _d(sl), _d(fl), _d(T), _d(v), _d(cams), _d(imus)), "step_hold")
+        return dict(cost=cost.value, delta_s=ds[:D], slam=sl[:D], frame_lam=fl, poses=T, vels=v, cams=cams[:nc], imus=imus)
 
     def evaluate(self):
         cost = C.c_double(0); sq = C.c_double(0)
