@@ -112,6 +112,11 @@ int vc_stop(vc_calibrator* h);
 
 /* readers (fields of CalibrationStats, calibration-stats.h:34-42) */
 int vc_num_frames(vc_calibrator* h);                                               /* NumFrames :471 */
+/* IMU blocks this rank owns (0 without inertial terms): one per own frame that has a successor.  On a frame-sharded visual-inertial
+ * calibrator every rank but the last also owns the block that ends in the next rank's separator, of which it keeps a ghost copy:
+ * vc_num_frames - 1, plus 1 on those ranks (VC_ERR_BAD_ARG for a sharded rank of fewer than 2 frames, which the upload refuses).
+ * vc_get_imu_blocks and vc_get_imu_weights write the blocks of the last upload, never more than this count. */
+int vc_num_imu_blocks(vc_calibrator* h);
 int vc_num_cameras(vc_calibrator* h);                                              /* NumCameras :484 */
 int vc_get_camera(vc_calibrator* h, int camera, double* params, int* nparams, double T_ck[7]);   /* GetCamera :492 */
 int vc_get_frame(vc_calibrator* h, int frame, double T_wk[7], double v_w[3], double* time);      /* GetFrame :477 */
@@ -180,7 +185,7 @@ long long vc_allreduce_calls(vc_calibrator* h);    /* all-reduces issued through
  * ranks it was started with.  Any of the pointers may be NULL.  (The reference is single-process: vicalibrator.h:263-274.) */
 int vc_shard_info(vc_calibrator* h, int* rank, int* world_size, int* rccl_ranks, int* rccl_rank);
 /* Which forms of the visual-inertial pass the uploaded problem runs (after vc_prepare / a solve; a parity hook: the tests assert that the
- * kernels they mean to check are the ones that ran): out4 = { chain assembly folded into the bottom level (k_chain_l0), back-substitution as
+ * kernels they mean to check are the ones that ran): out6 = { chain assembly folded into the bottom level (k_chain_l0), back-substitution as
  * one launch (k_chain_back_path), Gram sums in the top level's launch, top-level frames as a partial record of their own, the reduced
  * solve's tail in the back-substitution's launch, the shared parameters' blocks formed ahead of the reduced solve }. */
 int vc_pass_paths(vc_calibrator* h, int* out6);
@@ -192,7 +197,9 @@ const char* vc_last_error(void);
 int vc_prepare(vc_calibrator* h);
 /* Copies of device results after vc_prepare / vc_linearize (any pointer may be NULL):
  *   cost, per-frame H_pp (n x 36), g_p (n x 6), reduced S (D x D, undamped Schur complement), g_red (D),
- *   H_ss diagonal (D), g_s (D) */
+ *   H_ss diagonal (D), g_s (D).
+ * n = vc_num_frames: this rank's own frames on a sharded calibrator, its separator included, the ghost copy of the next rank's
+ * separator excluded.  S and g_red are the all-reduced ones, separator columns included (D = vc_shared_dim). */
 int vc_linearize(vc_calibrator* h, double* cost, double* Hpp, double* gp, double* S, double* g_red,
                  double* hss_diag, double* g_s);
 int vc_shared_dim(vc_calibrator* h);
@@ -204,7 +211,8 @@ int vc_shared_dim(vc_calibrator* h);
  *   cameras (n_cams x 17: T_ck(7), then the intrinsics padded to 10), IMU parameters (15: g(2) b(6) sf(6) time offset(1)).
  * Velocities and IMU parameters are zero without inertial terms.  The frames' own steps are not stored by every form of the pass
  * (vision-only passes form them in registers): they are available only through the trial state.  On a sharded calibrator the
- * frames are this rank's, separators included, and delta_s holds the separators' steps at their columns. */
+ * frames are this rank's, separators included, and delta_s holds the separators' steps at their columns.  Frame-indexed buffers
+ * (frame_lam, poses, vels) hold n = vc_num_frames rows: the ghost copy of the next rank's separator is not read out. */
 int vc_step_hold(vc_calibrator* h, double radius, double* cost, double* delta_s, double* slam, double* frame_lam, double* poses,
                  double* vels, double* cams, double* imus);
 /* Runs exactly `iters` LM iterations of the real solver (complete solves back to back from the uploaded
@@ -230,10 +238,11 @@ int vc_get_kernel_timing(vc_calibrator* h, char* names, int names_len, double* t
  * reduced solve, trial sweep, decision), `reps` back-to-back launches each */
 int vc_time_stages(vc_calibrator* h, int reps, double out[6]);
 /* After vc_linearize with inertial terms active: weighted J^T J (33 x 33), J^T r (33), cost of each IMU block,
- * columns [frame j: pose 6, vel 3 | frame j-1: pose 6, vel 3 | g 2, b 6, sf 6, time offset 1] */
+ * columns [frame j: pose 6, vel 3 | frame j-1: pose 6, vel 3 | g 2, b 6, sf 6, time offset 1].  Writes vc_num_imu_blocks blocks:
+ * on a sharded calibrator, those this rank owns, the one that ends in the ghost frame included. */
 int vc_get_imu_blocks(vc_calibrator* h, double* H, double* g, double* cost);
 /* Current weight_sqrt_ factors W (9 x 9 per IMU block, row-major) with W W^T = (J Sigma J^T)^-1, after vc_linearize
- * with the weight update active (UpdateImuWeights, vicalibrator.h:723-799). */
+ * with the weight update active (UpdateImuWeights, vicalibrator.h:723-799).  vc_num_imu_blocks blocks, as vc_get_imu_blocks. */
 int vc_get_imu_weights(vc_calibrator* h, double* W);
 int vc_get_debug_stamps(vc_calibrator* h, long long out[32]);   /* shader-clock stamps of the last k_reduced (profiling aid) */
 long long vc_num_observations(vc_calibrator* h);

@@ -77,6 +77,76 @@ def scaled_norm(ref, frame_part, shared_part):
     return float(np.linalg.norm(x[ref["active"]]))
 
 
+# ---- frame-sharded passes: the separator frames of the reduced system -------------------------------------------------------------
+
+def separator_frames(n_frames, world):
+    """Global index of the separator frames of a P-rank visual-inertial split, in column order: rank r > 0 moves its first frame
+    (vicalib_amd.parallel.frame_shard) into the reduced system at columns D0 + 9 (r - 1) + [0, 9) (vc_upload.cpp: sep_col0), the 9
+    in the frame's own order, pose 6 then velocity 3 (the back-substitution reads a pinned frame's step as delta_s[sep_col0 + i])."""
+    from vicalib_amd.parallel import frame_shard
+    return [frame_shard(n_frames, r, world)[0] for r in range(1, world)]
+
+
+def sharded_order(n, D0, seps, df=9):
+    """(interior, reduced): indices into the dense unknowns of dense_hessian (frames n * df, then the D0 shared parameters) of the
+    frames a sharded pass eliminates, and of the D0 + df * len(seps) columns of its reduced system in their order."""
+    sep_set = set(seps)
+    interior = np.array([f * df + i for f in range(n) if f not in sep_set for i in range(df)], dtype=np.int64)
+    reduced = np.array(list(range(n * df, n * df + D0)) + [f * df + i for f in seps for i in range(df)], dtype=np.int64)
+    return interior, reduced
+
+
+def sharded_schur(M, b, interior, reduced):
+    """Dense Schur complement of M on the `reduced` unknowns: S = M_rr - M_ri M_ii^-1 M_ir, b_red = b_r - M_ri M_ii^-1 b_i.  Interior
+    unknowns without equations (frames without detections, vision only) are decoupled and dropped."""
+    act = np.abs(M[interior]).sum(axis=1) > 0
+    i = interior[act]
+    Mii = M[np.ix_(i, i)]; Mir = M[np.ix_(i, reduced)]
+    X = np.linalg.solve(Mii, np.column_stack([Mir, b[i]]))
+    k = len(reduced)
+    return M[np.ix_(reduced, reduced)] - Mir.T @ X[:, :k], b[reduced] - Mir.T @ X[:, k], X, i
+
+
+def sharded_step(lin, lam, df, seps):
+    """The damped step solved the way a sharded pass solves it: eliminate every non-separator frame, solve the reduced system on the
+    shared parameters and the separators, back-substitute.  Returns the step in the dense layout of dense_hessian."""
+    n = lin["A"].shape[0]; D0 = lin["Hss"].shape[0]
+    H = dense_hessian(lin, df)
+    M = H + np.diag(_pack(lam[:n * 9], lam[n * 9:], n, df))
+    g = _pack(lin["gf"], lin["gs"], n, df)
+    interior, reduced = sharded_order(n, D0, seps, df)
+    S, br, X, i = sharded_schur(M, -g, interior, reduced)
+    Mii = M[np.ix_(i, i)]; Mir = M[np.ix_(i, reduced)]
+
+    def solve(b):
+        xi0 = np.linalg.solve(Mii, b[i])
+        xr = np.linalg.solve(S, b[reduced] - Mir.T @ xi0)
+        d = np.zeros(n * df + D0)
+        d[reduced] = xr
+        d[i] = xi0 - X[:, :-1] @ xr
+        return d
+    d = solve(-g)
+    # one step of iterative refinement, residual in long double (as reference_step)
+    res = (-g.astype(np.longdouble) - M.astype(np.longdouble) @ d.astype(np.longdouble)).astype(np.float64)
+    return d + solve(res)
+
+
+def device_columns(D0, n_seps, df):
+    """Columns of the sharded reduced system that have a counterpart among the reference's unknowns, in the order of sharded_order: the
+    shared D0, then the first df of each separator's 9 (pose 6, velocity 3).  With rotation-only initialisation the frames have df = 6
+    unknowns; a separator keeps 9 columns, the last 3 without equations."""
+    return np.array(list(range(D0)) + [D0 + 9 * j + i for j in range(n_seps) for i in range(df)], dtype=np.int64)
+
+
+def to_sharded(ref, seps):
+    """The reference step's delta_s and Jacobi scale in the sharded reduced system's column order (shared D0, then the separators)."""
+    n, df = ref["dfv"].shape[0], ref["df"]
+    D0 = len(ref["dsv"])
+    _, reduced = sharded_order(n, D0, seps, df)
+    d = _pack(ref["dfv"], ref["dsv"], n, df)
+    return d[reduced], ref["scale"][reduced]
+
+
 if __name__ == "__main__":      # child-process entry of the GPU test: python lm_step_ref.py <case name> (environment switches set by the parent)
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
     import test_lm_step_gpu as t

@@ -67,3 +67,50 @@ def test_damping_and_step_update_reproduce_the_first_iteration_of_solve_once(mod
     assert tr[1, 8] == 1 and tr[1, 7] > 1e4                 # accepted, radius grown
     assert abs(tr[0, 1] - lin["cost"]) <= 1e-12 * lin["cost"]
     assert abs(tr[1, 1] - trial_cost) <= 1e-9 * trial_cost
+
+
+@pytest.mark.parametrize("world,n_frames", [(3, 20), (2, 17), (8, 16)])
+@pytest.mark.parametrize("radius", [1e0, 1e4])
+def test_separator_reduced_solve_reproduces_the_dense_step(world, n_frames, radius):
+    """The separator layout the sharded GPU test compares against (lm_step_ref.separator_frames / sharded_order): eliminating every
+    non-separator frame of the oracle's linearisation, solving the reduced system on the shared parameters and the separators, and
+    back-substituting gives the dense reference step.  A wrong permutation in the helper fails here, without a GPU."""
+    _, orc = _vi(("kb4",), n_frames, 7)
+    lin = orc.linearize()
+    lam = orc.lm_lambda(radius)
+    r = ref.reference_step(lin, lam, 9)
+    seps = ref.separator_frames(n_frames, world)
+    assert seps == {3: [6, 13], 2: [8], 8: [2, 4, 6, 8, 10, 12, 14]}[world]       # the first frame of ranks 1 .. P - 1
+    n = lin["A"].shape[0]
+    d = ref.sharded_step(lin, lam, 9, seps)
+    want = ref._pack(r["dfv"], r["dsv"], n, 9)
+    s = r["scale"]
+    err = np.linalg.norm((d - want) / s) / np.linalg.norm(want / s)
+    print(f"world {world}, {n_frames} frames, radius {radius:g}: error {err:.3e}, bound {r['rel']:.3e}")
+    assert err <= 1e-12, err
+    ds, ss = ref.to_sharded(r, seps)
+    D0 = lin["Hss"].shape[0]
+    assert ds.shape == (D0 + 9 * (world - 1),) and ss.shape == ds.shape
+    np.testing.assert_array_equal(ds[:D0], r["dsv"])
+    for k, f in enumerate(seps):
+        np.testing.assert_array_equal(ds[D0 + 9 * k:D0 + 9 * k + 9], r["dfv"][f])
+    # the reduced system itself: its solution is the step's reduced part, and it is symmetric
+    interior, reduced = ref.sharded_order(n, D0, seps, 9)
+    assert len(set(interior) | set(reduced)) == n * 9 + D0 and not set(interior) & set(reduced)
+    H = ref.dense_hessian(lin, 9)
+    S, br, _, _ = ref.sharded_schur(H + np.diag(ref._pack(lam[:n * 9], lam[n * 9:], n, 9)), -r["g"], interior, reduced)
+    np.testing.assert_allclose(S, S.T, rtol=0, atol=1e-12 * np.abs(S).max())
+    np.testing.assert_allclose(S @ ds, br, rtol=0, atol=1e-9 * np.abs(br).max())
+    # independent of sharded_order: the inverse of a Schur complement is the matching block of the inverse of the whole matrix, so each
+    # separator's 9 x 9 block of S^-1, at columns D0 + 9 k, is the block of frame f = seps[k] of (H + Lambda)^-1, indexed by frame
+    Minv = np.linalg.inv(H + np.diag(ref._pack(lam[:n * 9], lam[n * 9:], n, 9)))
+    Sinv = np.linalg.inv(S)
+    tol = 1e-9 * np.abs(Minv).max()
+    np.testing.assert_allclose(Sinv[:D0, :D0], Minv[n * 9:, n * 9:], rtol=0, atol=tol)
+    for k, f in enumerate({3: [6, 13], 2: [8], 8: [2, 4, 6, 8, 10, 12, 14]}[world]):
+        np.testing.assert_allclose(Sinv[D0 + 9 * k:D0 + 9 * k + 9, D0 + 9 * k:D0 + 9 * k + 9], Minv[9 * f:9 * f + 9, 9 * f:9 * f + 9], rtol=0, atol=tol)
+        np.testing.assert_allclose(Sinv[:D0, D0 + 9 * k:D0 + 9 * k + 9], Minv[n * 9:, 9 * f:9 * f + 9], rtol=0, atol=tol)
+    # ... and a frame that is not a separator is nowhere in S: its block of (H + Lambda)^-1 matches no separator block of S^-1
+    f = {3: 5, 2: 7, 8: 3}[world]
+    assert all(np.abs(Sinv[D0 + 9 * k:D0 + 9 * k + 9, D0 + 9 * k:D0 + 9 * k + 9] - Minv[9 * f:9 * f + 9, 9 * f:9 * f + 9]).max() > 100 * tol
+               for k in range(world - 1))

@@ -282,6 +282,20 @@ int vc_is_running(vc_calibrator* h) { return h && h->is_running && !h->is_finish
 int vc_stop(vc_calibrator* h) { if (!h) return VC_ERR_BAD_ARG; h->stop(); return VC_OK; }
 
 int vc_num_frames(vc_calibrator* h) { return h ? (int)h->frames.size() : VC_ERR_BAD_ARG; }
+int vc_num_imu_blocks(vc_calibrator* h) {
+  if (!h) return VC_ERR_BAD_ARG;
+  if (!h->imu_on()) return 0;
+  // own frames - 1, plus the block that ends in the ghost copy of the next rank's separator (vc_upload.cpp: every rank but the last)
+  const bool shard_imu = h->world > 1;
+  if (shard_imu && h->frames.size() < 2) return VC_ERR_BAD_ARG;      // (the upload refuses such a rank)
+  const int ghost = (shard_imu && h->rank + 1 < h->world) ? 1 : 0;
+  return std::max((int)h->frames.size() - 1 + ghost, 0);
+}
+// blocks the IMU read-outs copy: those of the last upload, never more than vc_num_imu_blocks (the host state may have changed since)
+static size_t imu_blocks_out(vc_calibrator* h) {
+  const int nb = vc_num_imu_blocks(h);
+  return (size_t)std::max(0, std::min(h->dv.n_frames - 1, nb));
+}
 int vc_num_cameras(vc_calibrator* h) { return h ? (int)h->cams.size() : VC_ERR_BAD_ARG; }
 int vc_get_camera(vc_calibrator* h, int c, double* params, int* nparams, double T_ck[7]) {
   if (!h || c < 0 || c >= (int)h->cams.size()) return VC_ERR_BAD_ARG;
@@ -562,7 +576,7 @@ int vc_linearize(vc_calibrator* h, double* cost, double* Hpp, double* gp, double
   double lin_cost = 0;
   // radius = +inf-like: lambda -> ~0 so that L L^T = H_pp to rounding; S is stored undamped anyway
   int rc = h->linearize_hold(1e300, &lin_cost); if (rc) return rc;
-  const int N = h->dv.n_frames, D = h->dv.D;
+  const int N = h->dv.n_frames - h->dv.pin_last, D = h->dv.D;      // this rank's frames: a ghost copy of the next rank's separator is not read out
   if (cost) *cost = lin_cost;
   std::vector<double> fr((size_t)N * kFrStride);
   if ((Hpp || gp) && N) {
@@ -597,7 +611,7 @@ int vc_step_hold(vc_calibrator* h, double radius, double* cost, double* delta_s,
   double lin_cost = 0;
   int rc = h->linearize_hold(radius, &lin_cost); if (rc) return rc;
   // read-outs only: every buffer below is what the held pass left (the decision on hold keeps `cur`, the trial state is in 1 - cur)
-  const int N = h->dv.n_frames, C = h->dv.n_cams, D = h->dv.D, tr = 1 - h->cur;
+  const int N = h->dv.n_frames - h->dv.pin_last, C = h->dv.n_cams, D = h->dv.D, tr = 1 - h->cur;      // (own frames: as vc_linearize)
   auto get = [&](double* dst, const double* src, size_t n) { return !dst || !n || hipMemcpy(dst, src, n * 8, hipMemcpyDeviceToHost) == hipSuccess; };
   if (cost) *cost = lin_cost;
   if (!get(delta_s, h->dv.delta_s, D) || !get(slam, h->dv.slam, D)) return VC_ERR_NO_DEVICE;
@@ -747,7 +761,7 @@ int vc_get_imu_blocks(vc_calibrator* h, double* H, double* g, double* cost) {
   NOT_RUNNING(h);
   BIND_DEVICE(h);
   if (!h->dv.imu_on) return VC_ERR_BAD_ARG;
-  const size_t ns = (size_t)std::max(h->dv.n_frames - 1, 0);
+  const size_t ns = imu_blocks_out(h);
   const int b = h->cur;
   if ((H || g) && ns) {                          // the device keeps the blocks compact (vc_device.h: kSeg*): unfold them
     std::vector<double> rec(ns * kSegStride);
@@ -768,7 +782,7 @@ int vc_get_imu_weights(vc_calibrator* h, double* out) {
   NOT_RUNNING(h);
   BIND_DEVICE(h);
   if (!out || !h->dv.imu_on) return VC_ERR_BAD_ARG;
-  const size_t n = (size_t)std::max(0, h->dv.n_frames - 1) * 81;
+  const size_t n = imu_blocks_out(h) * 81;
   if (n == 0) return VC_OK;
   if (hipMemcpyAsync(out, h->dv.wsqrtb[h->wcur], n * 8, hipMemcpyDeviceToHost, h->stream) != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess) return VC_ERR_NO_DEVICE;
   return VC_OK;

@@ -25,7 +25,7 @@ SYMBOLS = [
     "vc_create", "vc_destroy", "vc_clear", "vc_add_camera", "vc_fix_camera_intrinsics", "vc_add_frame", "vc_set_frame_pose",
     "vc_add_observations", "vc_add_observation_tiles", "vc_add_imu", "vc_set_sigmas", "vc_set_biases", "vc_set_scale_factor", "vc_set_time_offset",
     "vc_set_function_tolerance", "vc_set_optimization_flags", "vc_set_max_iters", "vc_set_tolerances", "vc_set_gravity", "vc_set_frame_velocities", "vc_set_calibrate_imu", "vc_set_remove_outliers",
-    "vc_solve", "vc_start", "vc_resume", "vc_set_stage_limit", "vc_sync_timeouts", "vc_set_kernel_timing", "vc_get_kernel_timing", "vc_is_running", "vc_stop", "vc_num_frames", "vc_num_cameras", "vc_get_camera", "vc_get_frame",
+    "vc_solve", "vc_start", "vc_resume", "vc_set_stage_limit", "vc_sync_timeouts", "vc_set_kernel_timing", "vc_get_kernel_timing", "vc_is_running", "vc_stop", "vc_num_frames", "vc_num_imu_blocks", "vc_num_cameras", "vc_get_camera", "vc_get_frame",
     "vc_get_biases", "vc_get_scale_factor", "vc_get_gravity", "vc_time_offset", "vc_mean_squared_error", "vc_get_camera_proj_rmse",
     "vc_get_num_iterations", "vc_num_imu_measurements", "vc_get_imu_measurements", "vc_get_integration_poses", "vc_print_results", "vc_write_camera_models", "vc_trace_len", "vc_get_trace", "vc_set_shard", "vc_get_stream", "vc_prepare",
     "vc_linearize", "vc_step_hold", "vc_shared_dim", "vc_run_iterations", "vc_download_state", "vc_evaluate", "vc_time_kernels", "vc_time_stages", "vc_get_imu_blocks", "vc_get_debug_stamps", "vc_num_observations", "vc_num_tiles",
@@ -224,6 +224,7 @@ class ViCalibrator:
     def IsRunning(self): return bool(self.L.vc_is_running(self.h))
     def Stop(self): _check(self.L.vc_stop(self.h), "Stop")
     def NumFrames(self): return self.L.vc_num_frames(self.h)
+    def num_imu_blocks(self): return _check(self.L.vc_num_imu_blocks(self.h), "num_imu_blocks")
     def NumCameras(self): return self.L.vc_num_cameras(self.h)
 
     def GetCamera(self, c):
@@ -411,7 +412,7 @@ class ViCalibrator:
         return {k: (int(cnt[i]), float(tot[i] / cnt[i])) for i, k in enumerate(keys)}
 
     def imu_weights(self):
-        ns = max(self.NumFrames() - 1, 0)
+        ns = self.num_imu_blocks()
         W = np.zeros((ns, 9, 9))
         _check(self.L.vc_get_imu_weights(self.h, _d(W)), "imu_weights")
         return W
@@ -427,7 +428,7 @@ class ViCalibrator:
         return cov, buf.value.decode().split()
 
     def imu_blocks(self):
-        ns = max(self.NumFrames() - 1, 0)
+        ns = self.num_imu_blocks()
         H = np.zeros((ns, 33, 33)); g = np.zeros((ns, 33)); c = np.zeros(ns)
         _check(self.L.vc_get_imu_blocks(self.h, _d(H), _d(g), _d(c)), "imu_blocks")
         return H, g, c
