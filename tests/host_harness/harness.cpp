@@ -7,6 +7,7 @@
 #include <vector>
 #include "../../vicalib_amd/csrc/vc_imu.hpp"
 #include "seq_weights.hpp"
+#include "../../vicalib_amd/csrc/vc_chain_plan.hpp"
 using namespace vc;
 
 template <int MODEL>
@@ -139,5 +140,20 @@ void hh_so3_exp_jl(const double* w, const double* dir, double* q, double* AB, do
   for (int k = 0; k < 3; ++k) W[k] = mk(w[k], dir[k]);
   tso3_exp(W, Q);
   for (int k = 0; k < 4; ++k) dq[k] = Q[k].v;
+}
+// the chain plan of a problem (vc_chain_plan.hpp); switches: bits 0..3 = fold_l0, back_path, hadd_early, defer_tail.  out: n_levels, top_stride,
+// forward_launches, bottom_groups, fold_l0, gram_top_stride, back_path, top_gram_launch, hadd_early, tail_deferred, then stride[], m[], groups[],
+// two[] (kChainMaxLevels each)
+int hh_chain_plan(int N, int D, int n_cams, int imu_on, int sharded, int switches, int* out) {
+  ChainSwitches sw;
+  sw.fold_l0 = switches & 1; sw.back_path = switches & 2; sw.hadd_early = switches & 4; sw.defer_tail = switches & 8;
+  const ChainPlan p = plan_chain(N, D, n_cams, imu_on != 0, sharded != 0, sw);
+  const int head[10] = {p.n_levels, p.top_stride, p.forward_launches, p.bottom_groups, p.fold_l0, p.gram_top_stride, p.back_path,
+                        p.top_gram_launch, p.hadd_early, p.tail_deferred};
+  for (int i = 0; i < 10; ++i) out[i] = head[i];
+  for (int l = 0; l < kChainMaxLevels; ++l) {
+    out[10 + l] = p.stride[l]; out[10 + kChainMaxLevels + l] = p.m[l]; out[10 + 2 * kChainMaxLevels + l] = p.groups[l]; out[10 + 3 * kChainMaxLevels + l] = p.two[l];
+  }
+  return kChainMaxLevels;
 }
 }

@@ -15,7 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 def _run(tmp_path, name, **env):
     out = str(tmp_path / (name + ".npz"))
     e = dict(os.environ)
-    for k in ("VICALIB_AMD_FLAG_SYNC", "VICALIB_AMD_SYNC_BOUND", "VICALIB_AMD_SYNC_BOUND_FROM_PASS", "VICALIB_AMD_STREAM2_PRIORITY", "GPU_MAX_HW_QUEUES", "VICALIB_AMD_BATCHED", "VICALIB_AMD_GRAPHS", "VICALIB_AMD_BACK_FUSED", "VICALIB_AMD_NO_MERGED_DECISION"):
+    for k in ("VICALIB_AMD_FLAG_SYNC", "VICALIB_AMD_SYNC_BOUND", "VICALIB_AMD_SYNC_BOUND_FROM_PASS", "VICALIB_AMD_STREAM2_PRIORITY", "GPU_MAX_HW_QUEUES", "VICALIB_AMD_BATCHED", "VICALIB_AMD_GRAPHS", "VICALIB_AMD_NO_MERGED_DECISION"):
         e.pop(k, None)
     e.update({k: str(v) for k, v in env.items()})
     r = subprocess.run([sys.executable, os.path.join(HERE, "sync_worker.py"), out], env=e, capture_output=True, text=True, timeout=600)

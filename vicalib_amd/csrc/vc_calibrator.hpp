@@ -7,30 +7,40 @@
 // are in vc_capi.cpp.
 #include "vc_host.hpp"
 
+// The run-time switches of the pass, read once per calibrator by vc_create: nothing else reads a pass switch from the environment
+struct Switches {
+  bool graphs = false;                  // VICALIB_AMD_GRAPHS=1: capture a pass once and replay it
+  bool merged = true;                   // VICALIB_AMD_NO_MERGED_DECISION=1: false
+  bool batched = false;                 // VICALIB_AMD_BATCHED=1: batch-and-synchronise schedule instead of feeding passes
+  bool stream2_default = false;         // VICALIB_AMD_STREAM2_PRIORITY=default: plain second stream, no priority class of its own
+  int flag_sync = -1;                   // VICALIB_AMD_FLAG_SYNC=0 / 1: events / flags whatever the second stream's priority class (-1: unset)
+  int shard_flag_sync = -1;             // VICALIB_AMD_SHARD_FLAG_SYNC=0 / 1 (-1: unset; flags with an RCCL communicator of several ranks)
+  bool force_shard_path = false;        // VICALIB_AMD_FORCE_SHARD_PATH=1: the sharded code path with one rank
+  long long sync_bound = 800000;        // VICALIB_AMD_SYNC_BOUND: polls before a flag wait gives up (~0.2 s; a tiny bound forces the time-out path)
+  int sync_bound_from_pass = 0;         // VICALIB_AMD_SYNC_BOUND_FROM_PASS: that bound only from this pass of the calibrator on
+  int pre_backsub = -1;                 // VICALIB_AMD_PRE_BACKSUB=0 / 1: k_backsub off / on whatever the tile count (-1: unset)
+  ChainSwitches chain;                  // VICALIB_AMD_FOLD_L0, _BACK_PATH, _HADD_EARLY, _DEFER_TAIL (vc_chain_plan.hpp)
+  static Switches read();
+};
+
 struct vc_calibrator {
+  Switches sw;                          // (vc_create)
+  ChainPlan plan;                       // the chain's levels and the forms of the visual-inertial pass (upload)
   int device = 0;
   hipStream_t stream = nullptr;
   hipStream_t stream2 = nullptr;        // the IMU weight update of a pass runs here, under the pass's Jacobian sweeps and chain solve
   hipEvent_t ev_state = nullptr, ev_weights = nullptr, ev_imujac = nullptr, ev_reduced = nullptr, ev_back = nullptr, ev_pre = nullptr;
-  bool top_gram_launch = false;         // early Gram: the chain's top-level frames need a Gram launch of their own (upload)
   bool pre_weights_pending = false;     // solve_once has recorded ev_pre ahead of the weight update that precedes a solve
   bool pre_weights_fresh = false;       // ... and nothing has moved the state since: the first pass's own update would repeat it
   int wcur = 0;                         // weight buffer holding the current weight_sqrt_
   Packer pack;                          // staging image of a stage's small uploads
   bool flag_sync = false;               // hand-overs to the second stream through device flags instead of event records (set at creation)
-  bool weights_behind_l0 = !(std::getenv("VICALIB_AMD_WEIGHTS_BEHIND_L0") && std::getenv("VICALIB_AMD_WEIGHTS_BEHIND_L0")[0] == '0');
-  bool shard_flag_sync = std::getenv("VICALIB_AMD_SHARD_FLAG_SYNC") && std::getenv("VICALIB_AMD_SHARD_FLAG_SYNC")[0] == '1';
-  long long sync_bound = 800000;        // polls before a flag wait gives up (~0.2 s); VICALIB_AMD_SYNC_BOUND (test hook: a tiny bound forces the time-out path)
-  int sync_bound_from_pass = 0;         // VICALIB_AMD_SYNC_BOUND_FROM_PASS (test hook): the tiny bound only from this pass of the calibrator on -- a time-out in the middle of a solve
+  bool shard_flag_sync = false;         // ... in sharded passes too (set at creation and by attach_rccl)
   int wr_ring[16] = {0};                // weight buffer read by pass (pass_seq & 15)
   int sync_timeouts = 0;                // flag hand-overs that ran into their bound (each one reported on stderr, the solve resumed with events)
   long long pass_seq = 0;               // passes enqueued (the value the flags carry)
   bool prev_pass_signals = false;       // the previous pass of this solve was enqueued with signalling kernels
   DBuf<long long> d_sync, d_part_ready;
-  bool jac_on_stream2 = true;           // the trial point's k_imu_jac beside the vision sweep (VICALIB_AMD_JAC_STREAM2=0: after it, main stream)
-  bool serial_weights = false;          // false: IMU Jacobians + weight update on the second stream (VICALIB_AMD_OVERLAP_WEIGHTS=0: in line); was: VICALIB_AMD_OVERLAP_WEIGHTS=1 moves it to a second
-                                        // stream under the Jacobian sweeps / chain solve (measured: the two latency-bound kernels then
-                                        // share the CUs and the pass gets 4 % slower on cfg3)
   hipGraphExec_t pass_graph[2] = {nullptr, nullptr};   // one captured LM pass per weight-buffer parity (single process)
   bool use_graphs = false;      // measured slower on ROCm 7.2 (cfg2: 65 vs 62 us / pass, instantiation ~10 ms per stage): opt-in via VICALIB_AMD_GRAPHS=1
   hipError_t last_hip_error = hipSuccess;
@@ -72,8 +82,7 @@ struct vc_calibrator {
   std::mutex result_mutex;
   // ---- sharding ---------------------------------------------------------------------------
   int rank = 0, world = 1;
-  bool force_shard_path = false;   // VICALIB_AMD_FORCE_SHARD_PATH=1: run the sharded code path (split kernels + callbacks) with one rank (test hook)
-  bool sharded() const { return world > 1 || (force_shard_path && (allreduce || rccl_comm)); }
+  bool sharded() const { return world > 1 || (sw.force_shard_path && (allreduce || rccl_comm)); }      // (force: split kernels + callbacks with one rank)
   DBuf<double> d_halo, d_sep_strip, d_gath;
   long global_first = 0, global_total = 0;     // this rank's frame range in the sharded problem (known after gather_shard_info)
   vc_allreduce_fn allreduce = nullptr;
@@ -111,7 +120,6 @@ struct vc_calibrator {
   long solve_epoch = 0, nres_epoch_cached = -1;     // ... and the public solve call it was formed in (bumped by every rank at the same entry points)
   int expected_passes = 8;       // passes the previous solve needed: size of the first batch of the next one (batched schedule)
   int feed_ahead = 1;            // passes kept queued beyond the last decision seen (grows when the host is found late)
-  bool feed_passes = std::getenv("VICALIB_AMD_BATCHED") == nullptr;   // single process: feed passes against the device's progress word
   DBuf<unsigned char> d_mask;
   std::vector<int> h_tile_frame, h_tile_cam, h_tile_off, h_obs_index;   // h_obs_index: device corner -> host observation
   std::vector<int> cam_flags, cam_col0;

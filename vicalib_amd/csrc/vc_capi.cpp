@@ -2,6 +2,24 @@
 // status codes; RCCL communicators; parity / timing hooks; solution covariance; results as text and cameras.xml.
 #include "vc_calibrator.hpp"
 
+static int env_bit(const char* name) { const char* e = std::getenv(name); return (e && (e[0] == '0' || e[0] == '1')) ? e[0] - '0' : -1; }
+Switches Switches::read() {
+  Switches w;
+  w.graphs = env_bit("VICALIB_AMD_GRAPHS") == 1;
+  w.merged = env_bit("VICALIB_AMD_NO_MERGED_DECISION") != 1;
+  w.batched = std::getenv("VICALIB_AMD_BATCHED") != nullptr;
+  { const char* e = std::getenv("VICALIB_AMD_STREAM2_PRIORITY"); w.stream2_default = e && std::strcmp(e, "default") == 0; }
+  w.flag_sync = env_bit("VICALIB_AMD_FLAG_SYNC");
+  w.shard_flag_sync = env_bit("VICALIB_AMD_SHARD_FLAG_SYNC");
+  w.force_shard_path = env_bit("VICALIB_AMD_FORCE_SHARD_PATH") == 1;
+  { const char* e = std::getenv("VICALIB_AMD_SYNC_BOUND"); if (e && std::atoll(e) > 0) w.sync_bound = std::atoll(e); }
+  { const char* e = std::getenv("VICALIB_AMD_SYNC_BOUND_FROM_PASS"); if (e) w.sync_bound_from_pass = std::atoi(e); }
+  w.pre_backsub = env_bit("VICALIB_AMD_PRE_BACKSUB");
+  w.chain.fold_l0 = env_bit("VICALIB_AMD_FOLD_L0") != 0; w.chain.back_path = env_bit("VICALIB_AMD_BACK_PATH") != 0;
+  w.chain.hadd_early = env_bit("VICALIB_AMD_HADD_EARLY") != 0; w.chain.defer_tail = env_bit("VICALIB_AMD_DEFER_TAIL") != 0;
+  return w;
+}
+
 // =====================================================================================================
 extern "C" {
 
@@ -13,14 +31,10 @@ int vc_create(vc_calibrator** out, int device) {
   if (hipSetDevice(device) != hipSuccess) return VC_ERR_NO_DEVICE;
   vc_calibrator* h = new vc_calibrator();
   h->device = device;
-  { const char* e = std::getenv("VICALIB_AMD_GRAPHS"); if (e && e[0] == '1') h->use_graphs = true; }
-  { const char* e = std::getenv("VICALIB_AMD_NO_MERGED_DECISION"); if (e && e[0] == '1') h->merged_enabled = false; }
-  { const char* e = std::getenv("VICALIB_AMD_OVERLAP_WEIGHTS"); if (e && e[0] == '0') h->serial_weights = true; }
-  { const char* e = std::getenv("VICALIB_AMD_JAC_STREAM2"); if (e && e[0] == '0') h->jac_on_stream2 = false; }
+  h->sw = Switches::read();
+  h->use_graphs = h->sw.graphs; h->merged_enabled = h->sw.merged; h->shard_flag_sync = h->sw.shard_flag_sync == 1;
   // the hand-over events between the calibrator's two streams order work on ONE device: no system-scope fence at the record
-  // (VICALIB_AMD_EVENT_SYSTEM_FENCE=1 restores the default, for A/B measurements)
-  unsigned evf = hipEventDisableTiming | hipEventDisableSystemFence;
-  { const char* e = std::getenv("VICALIB_AMD_EVENT_SYSTEM_FENCE"); if (e && e[0] == '1') evf = hipEventDisableTiming; }
+  const unsigned evf = hipEventDisableTiming | hipEventDisableSystemFence;
   // The second stream carries the off-critical-path kernels of a visual-inertial pass (weight update, interval deltas).  It is
   // created with the LOWEST priority: (a) its kernels yield to the chain solve they run beside, and (b) streams of a different
   // priority live in their own pool of hardware queues -- with equal priorities HIP multiplexes all streams of the process onto
@@ -28,11 +42,8 @@ int vc_create(vc_calibrator** out, int device) {
   // communicator does it) can land both of ours on ONE queue, which serialises the pass: 0.30 -> 0.46 ms at cfg3, measured.
   int prio_least = 0, prio_greatest = 0;
   (void)hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest);
-  const char* prio_env = std::getenv("VICALIB_AMD_STREAM2_PRIORITY");      // "default": plain hipStreamCreate (A/B measurements)
-  const bool plain2 = prio_env && std::strcmp(prio_env, "default") == 0;
-  auto make_stream2 = [&]() -> hipError_t {
-    const bool high2 = prio_env && std::strcmp(prio_env, "high") == 0;      // (A/B: the second stream in the HIGHEST priority class instead of the lowest)
-    if (!plain2 && prio_least != prio_greatest && hipStreamCreateWithPriority(&h->stream2, hipStreamDefault, high2 ? prio_greatest : prio_least) == hipSuccess) { h->flag_sync = true; return hipSuccess; }
+  auto make_stream2 = [&]() -> hipError_t {      // (VICALIB_AMD_STREAM2_PRIORITY=default: plain hipStreamCreate, the test that puts both streams on one queue)
+    if (!h->sw.stream2_default && prio_least != prio_greatest && hipStreamCreateWithPriority(&h->stream2, hipStreamDefault, prio_least) == hipSuccess) { h->flag_sync = true; return hipSuccess; }
     (void)hipGetLastError();
     return hipStreamCreate(&h->stream2);          // (a runtime without stream priorities: plain stream, same results)
   };
@@ -44,9 +55,7 @@ int vc_create(vc_calibrator** out, int device) {
   // flag hand-overs need the two streams on different hardware queues (a waiting kernel at the head of a shared queue would hold
   // its own producer back): only with the second stream in its own priority class; VICALIB_AMD_FLAG_SYNC=0 keeps the events
   // (=1 forces the flags on whatever the second stream's priority class: the test that puts both streams on one hardware queue)
-  { const char* e = std::getenv("VICALIB_AMD_FLAG_SYNC"); if (e && e[0] == '0') h->flag_sync = false; if (e && e[0] == '1') h->flag_sync = true; }
-  { const char* e = std::getenv("VICALIB_AMD_SYNC_BOUND"); if (e && std::atoll(e) > 0) h->sync_bound = std::atoll(e); }      // (test hook: a tiny bound forces the time-out path)
-  { const char* e = std::getenv("VICALIB_AMD_SYNC_BOUND_FROM_PASS"); if (e) h->sync_bound_from_pass = std::atoi(e); }
+  if (h->sw.flag_sync >= 0) h->flag_sync = h->sw.flag_sync == 1;
   // (the flag words are there whatever the hand-over mode: the counted hand-over inside k_reduced's launch uses two of them)
   if (h->d_sync.alloc(kSyncWords) != hipSuccess || hipMemset(h->d_sync.p, 0, kSyncWords * sizeof(long long)) != hipSuccess) { delete h; return VC_ERR_NO_DEVICE; }
   *out = h;
@@ -449,7 +458,6 @@ int vc_set_shard(vc_calibrator* h, int rank, int world_size, vc_allreduce_fn fn,
   // failed on another one must end up on the same transport everywhere)
   h->drop_comm();
   h->rank = rank; h->world = world_size; h->allreduce = fn; h->allreduce_ctx = ctx; h->device_dirty = true;
-  { const char* e = std::getenv("VICALIB_AMD_FORCE_SHARD_PATH"); h->force_shard_path = e && e[0] == '1'; }
   return VC_OK;
 }
 int vc_rccl_unique_id(void* out128) {
@@ -494,10 +502,9 @@ static void attach_rccl(vc_calibrator* h, int rank, int world_size, void* comm, 
   h->drop_comm();
   h->rccl_comm = comm; h->rccl_comm_owned = owned;
   h->rank = rank; h->world = world_size; h->allreduce = nullptr; h->allreduce_ctx = nullptr; h->device_dirty = true;
-  { const char* e = std::getenv("VICALIB_AMD_FORCE_SHARD_PATH"); h->force_shard_path = e && e[0] == '1'; }
   // an RCCL communicator of several ranks has one device per rank: this process has its device to itself, the cross-stream hand-overs of
   // the pass can go through device flags as in a single-process solve (-25 us per pass and rank; VICALIB_AMD_SHARD_FLAG_SYNC=0 keeps events)
-  { const char* e = std::getenv("VICALIB_AMD_SHARD_FLAG_SYNC"); if (world_size > 1 && !(e && e[0] == '0')) h->shard_flag_sync = true; }
+  if (world_size > 1 && h->sw.shard_flag_sync != 0) h->shard_flag_sync = true;
 }
 int vc_set_shard_rccl(vc_calibrator* h, int rank, int world_size, const void* unique_id128) {
   g_last_error.clear();
@@ -552,13 +559,9 @@ int vc_shard_info(vc_calibrator* h, int* rank, int* world_size, int* rccl_ranks,
 const char* vc_last_error(void) { return g_last_error.c_str(); }
 int vc_pass_paths(vc_calibrator* h, int* out6) {
   if (!h || !out6) return VC_ERR_BAD_ARG;
-  out6[0] = h->dv.imu_on ? h->dv.fold_l0 : 0; out6[1] = h->dv.imu_on ? h->dv.back_path : 0;
-  out6[2] = (h->dv.imu_on && h->dv.gram_top_stride > 0) ? 1 : 0; out6[3] = h->top_gram_launch ? 1 : 0;
-  // (decided per pass by enqueue_pass from the same predicates and switches)
-  static const bool defer_env = [] { const char* e = std::getenv("VICALIB_AMD_DEFER_TAIL"); return !(e && e[0] == '0'); }();
-  static const bool hadd_env = [] { const char* e = std::getenv("VICALIB_AMD_HADD_EARLY"); return !(e && e[0] == '0'); }();
-  out6[4] = (h->dv.imu_on && defer_env && chain_back_is_path(h->dv)) ? 1 : 0;
-  out6[5] = (h->dv.imu_on && hadd_env && chain_hadd_early(h->dv)) ? 1 : 0;
+  const ChainPlan& p = h->plan;      // (the forms of the uploaded problem: every pass runs them)
+  out6[0] = p.fold_l0; out6[1] = p.back_path; out6[2] = p.gram_top_stride > 0 ? 1 : 0; out6[3] = p.top_gram_launch;
+  out6[4] = p.tail_deferred; out6[5] = p.hadd_early;
   return VC_OK;
 }
 void* vc_get_stream(vc_calibrator* h) { return h ? (void*)h->stream : nullptr; }

@@ -9,6 +9,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include "vc_chain_plan.hpp"
 
 namespace vc {
 
@@ -25,6 +26,7 @@ enum { kScGd = 0, kScDld = 1, kScStep2 = 2, kScX2 = 3, kScG2 = 4, kScCost = 5, k
 constexpr int kTraceCols = 10;     // iteration cost cost_change gmax gnorm step_norm rho radius accepted stage
 constexpr int kSmallD = 32;        // reduced systems up to this width are solved by one wavefront; above it the workgroup-wide LDS factorisation is faster
 constexpr int kEarlyTopD = kSmallD - 1;   // early Gram inside k_reduced: its three 16 x 16 column tiles cover the D + 1 <= 32 columns of [Y | z] (D = 32: the z column would fall outside)
+static_assert(kEarlyTopD == kChainEarlyTopD, "vc_chain_plan.hpp plans the top level's Gram launch by this width");
 constexpr int kSyncWords = 16;     // DevView::sync_flags
 
 // termination codes in Ctrl::done (0 = keep running)
@@ -212,7 +214,7 @@ struct DevView {
   double* sep_strip;               // 2 x 9 x ldw: rows of the reduced system contributed directly by the pinned frames
   // (round 6) 1: k_reduced ends with the step and the trial IMU parameters stored; the trial cameras and the shared parameters' terms of the
   // step scalars (vc_reduced_tail.hpp) are formed by one extra workgroup of the back-substitution's launch (k_chain_back_path).  Set per pass
-  // by enqueue_pass (chain_back_is_path)
+  // by enqueue_pass (ChainPlan::tail_deferred)
   int tail_deferred;
   // (round 6) the camera blocks, the IMU-parameter block and the chunk costs of the reduced system, formed ahead of k_reduced by side jobs of
   // the chain's upper-level launches (vc_shared_blocks.hpp): hadd has Sbuf's layout; hadd_early = 1: this pass's k_reduced starts from Sbuf + hadd
@@ -234,11 +236,6 @@ void launch_reduced(const DevView& v, int mode, hipStream_t s);
 bool reduced_fits(const DevView& v);              // the reduced system fits k_reduced's LDS (D <= 179 on gfx950)
 void launch_trial(const DevView& v, hipStream_t s);            // back-substitution + manifold update + trial residual sweep
 void launch_final(const DevView& v, int mode, hipStream_t s);
-int chain_forward_launches(const DevView& v);      // launches of the chain's forward elimination (levels + top)
-int chain_top_stride(int n_frames);                // stride of the frames the chain's top level eliminates
-bool chain_fold_supported(int n_frames, int D, int n_cams);      // k_chain_l0 can serve this problem (vc_imu_kernels.hip)
-bool chain_hadd_early(const DevView& v);           // the forward elimination of this problem has the two launches above the bottom level that carry the side jobs of DevView::hadd
-bool chain_back_is_path(const DevView& v);         // the back-substitution of this problem is one launch of k_chain_back_path with >= 256 threads per workgroup (it can carry the reduced solve's tail)
 // a segment of a packed upload: `bytes` (a multiple of 4) from offset src_off of the staging image to dst; src_off = ~0: zero-fill
 struct UnpackSeg { unsigned long long dst, src_off, bytes; };
 void launch_unpack(const UnpackSeg* segs, int n, const void* image, size_t total_bytes, hipStream_t s);
@@ -253,15 +250,13 @@ void launch_cam_sq(const DevView& v, double* out /*n_cams x 2: sum sq, count*/, 
 void launch_outlier_mask(const DevView& v, int state, const double* thresh /*device, n_cams*/, unsigned char* mask, hipStream_t s);
 
 // inertial path (vc_imu_kernels.hip)
-int chain_group_size_upper();    // ... above the bottom level (VICALIB_AMD_CHAIN_M_UPPER)
-int chain_group_size();          // frames per group of the partitioned chain elimination (test hook: VICALIB_AMD_CHAIN_M)
 void launch_imu_delta(const DevView& v, hipStream_t s, int trial = 0);         // block deltas under the IMU parameters of the accepted (0) / trial (1) state (k_imu_block)
 void launch_imu_jac(const DevView& v, int wr, hipStream_t s, int trial = 0);   // wr: weight buffer to read; trial as for launch_reproj_jac; needs launch_imu_delta
 void launch_imu_weights(const DevView& v, int wr, hipStream_t s);          // reads wsqrtb[wr], writes wsqrtb[1 - wr];                   // weight_sqrt_ from the accepted state
 void launch_chain_init(const DevView& v, hipStream_t s);                    // frame images from the tile Gram records and the IMU blocks
-void launch_chain_fwd(const DevView& v, hipStream_t s);                     // forward elimination, one launch per level
+void launch_chain_fwd(const DevView& v, const ChainPlan& p, hipStream_t s);   // forward elimination, one launch per level
 void launch_chain_gram(const DevView& v, hipStream_t s);                    // sum of [Y | z]^T [Y | z] per chunk
 void launch_chain_gram_top(const DevView& v, hipStream_t s);                // early Gram: the top level's frames as one more partial record
-void launch_chain_solve_b(const DevView& v, hipStream_t s);                 // back-substitution + trial frame state
+void launch_chain_solve_b(const DevView& v, const ChainPlan& p, hipStream_t s);   // back-substitution + trial frame state
 
 }  // namespace vc

@@ -402,23 +402,18 @@ template <int N> __device__ __forceinline__ void delta_t_scan_level(IntervalDelt
 #ifndef VC_IMU_BLOCK_WAVES
 #define VC_IMU_BLOCK_WAVES 2
 #endif
-#ifndef VC_IMU_BLOCK_PARK
-#define VC_IMU_BLOCK_PARK 1
-#endif
 #ifdef VC_IMU_BLOCK_EU      // (A/B builds: a register budget of 512 / n per wavefront -- n = 3: 168 registers, 268 B of scratch)
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(VC_IMU_BLOCK_EU, VC_IMU_BLOCK_EU))) void k_imu_block(DevView v, int trial) {
 #else
 __global__ __launch_bounds__(256, VC_IMU_BLOCK_WAVES) void k_imu_block(DevView v, int trial) {
 #endif
   __shared__ double s_carry[32 * kDtDoubles];
-#if VC_IMU_BLOCK_PARK
   // the first interval's delta while the second is formed: tangent and accelerometer partials per lane (16 doubles), the VALUES once per
   // interval -- they are the same numbers in all eight groups, group 0 writes them: 42 KB per workgroup with the carry, not 62: two
   // workgroups fit a CU's LDS beside a workgroup of the back-substitution (68 KB at BASELINE cfg3).  (Its registers then hold the grid to
   // one workgroup per CU there -- 252 + 216 of a SIMD's 512 -- and two rounds; a step under ~144 registers spills: HISTORY round 6)
   __shared__ double s_park[256 * (kDtDoubles - 11)];
   __shared__ double s_parkv[4 * 8 * 11];
-#endif
   IBSTAMP(0);
   if (trial && v.sync_seq > 0 && workgroup_pass_void(v)) return;      // (vc_kutil.hpp: a void pass's trial kernels may run ahead of the previous decision)
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);      // (scalar: everything per block stays out of the vector registers)
@@ -456,10 +451,8 @@ __global__ __launch_bounds__(256, VC_IMU_BLOCK_WAVES) void k_imu_block(DevView v
         // under the second RK4 step); a loop that is not unrolled: one copy of the step, nothing of the second interval scheduled
         // into the first
         IntervalDeltaT Y;
-#if VC_IMU_BLOCK_PARK
         double* pk = s_park + threadIdx.x;
         double* pv = s_parkv + (wave * 8 + l) * 11;
-#endif
 #pragma unroll 1
         for (int half = 0; half < 2; ++half) {
           // (the group index made opaque per iteration: otherwise everything the step derives from it -- seed masks, unit vector,
@@ -469,7 +462,6 @@ __global__ __launch_bounds__(256, VC_IMU_BLOCK_WAVES) void k_imu_block(DevView v
           imu_interval_delta_t(buf, rg, mk(toff, gs == 6 ? 1.0 : 0.0), t_start, t_end, base + 2 * l + 1 + half, n_int, im + 2, im + 8, gs, &Y);
           IBSTAMP(3 + half);
           if (half == 0) {
-#if VC_IMU_BLOCK_PARK
             double f[kDtDoubles];
             delta_t_pack(Y, f);
 #pragma unroll
@@ -478,12 +470,8 @@ __global__ __launch_bounds__(256, VC_IMU_BLOCK_WAVES) void k_imu_block(DevView v
 #pragma unroll
               for (int k = 0; k < 11; ++k) pv[k] = f[k];
             }
-#else
-            X = Y;
-#endif
           }
         }
-#if VC_IMU_BLOCK_PARK
         wave_lds_sync_local();               // (group 0's values are read by the other groups' lanes)
         double f[kDtDoubles];
 #pragma unroll
@@ -492,7 +480,6 @@ __global__ __launch_bounds__(256, VC_IMU_BLOCK_WAVES) void k_imu_block(DevView v
         for (int k = 11; k < kDtDoubles; ++k) f[k] = pk[(k - 11) * 256];
         delta_t_unpack(f, &X);
         wave_lds_sync_local();               // (... before the next round's first interval overwrites them)
-#endif
         imu_delta_t_then(&X, Y);
       }
       IBSTAMP(5);
@@ -1240,7 +1227,6 @@ __global__ __launch_bounds__(256, 2) void k_chain_init(DevView v) {     // (two 
 // image (rX, double-buffered by level parity) and is folded in when that frame is loaded or written at the next level.
 // A few levels (N = 2000, m = 8: 2000 -> 250 -> 32 -> 4) and a top level that eliminates what is left replace the
 // 2 log2(N) launches of cyclic reduction by log_m(N) + 1, with (m - 1) log_m(N) dependent eliminations.
-constexpr int kChainM = 8;          // group size: 7 eliminations per wavefront and level
 constexpr int kXsLd = 20;           // row stride of the [X_s | X_n] LDS image
 // phase stamps of the first group of level 0 (profiling builds only, -DVC_CHAIN_STAMPS): 100 MHz s_memrealtime ticks in dbg[0..31]
 #ifdef VC_CHAIN_STAMPS
@@ -3157,59 +3143,19 @@ void launch_imu_weights(const DevView& v, int wr, hipStream_t s) {
   if (v.n_frames < 2) return;
   hipLaunchKernelGGL(k_imu_weights, dim3((v.n_frames - 1 + 3) / 4), dim3(64), 0, s, v, wr);      // four blocks per wavefront
 }
-// Level schedule of the partitioned chain elimination: strides 1, m, m^2, ... while more than m - 1 frames are active, then
-// the top level (one wavefront eliminates the rest).  forward: bottom-up; backward: top-down.
-int chain_group_size() {
-  static int m = 0;
-  if (!m) { const char* e = std::getenv("VICALIB_AMD_CHAIN_M"); m = e ? std::max(2, std::min(kChainM, std::atoi(e))) : kChainM; }
-  return m;
-}
-// group size above the bottom level (test hook VICALIB_AMD_CHAIN_M_UPPER; default: the same as the bottom level)
-int chain_group_size_upper() {
-  static int m = 0;
-  if (!m) { const char* e = std::getenv("VICALIB_AMD_CHAIN_M_UPPER"); m = e ? std::max(2, std::min(kChainM, std::atoi(e))) : chain_group_size(); }
-  return m;
-}
 void launch_chain_gram(const DevView& v, hipStream_t s);
-// Level schedule of the partitioned chain elimination: strides 1, m0, m0 m1, ... while more than m - 1 frames are active, then
-// the top level (one wavefront eliminates the rest).  forward: bottom-up; backward: top-down.
-static void chain_levels(const DevView& v, hipStream_t s, bool forward) {
+// The levels of the partitioned chain elimination as the plan gives them (vc_chain_plan.hpp).  forward: bottom-up; backward: top-down.
+static void chain_levels(const DevView& v, const ChainPlan& p, hipStream_t s, bool forward) {
   const int N = v.n_frames;
   if (N < 1) return;
-  int strides[32], ms[32], nl = 0;
-  long st = 1;
-  while (true) {
-    const int m = nl == 0 ? chain_group_size() : chain_group_size_upper();
-    if (!((N - 1) / st + 1 > m - 1)) break;
-    strides[nl] = (int)st; ms[nl] = m; ++nl; st *= m;
-  }
-  const int top_stride = (int)st, m_top = kChainM;      // the top level eliminates whatever is left (fewer than a group)
+  const int nl = p.n_levels, top_stride = p.top_stride, m_top = kChainM;      // the top level eliminates whatever is left (fewer than a group)
   const int cpl = (v.D + 1 + 27 + 63) / 64;
   // wide borders: wavefronts side by side (measured in round 2 against several columns per lane: 1.68 -> 1.51 ms per pass at cfg5's per-rank
   // size, 8.74 -> 8.39 ms at its full size; the columns-per-lane instances -- 256 registers + up to 256 accumulation registers, scratch at
   // four columns -- were kept for A/B runs until round 6 and are gone)
-  // narrow borders: above the bottom level the groups are eliminated from both ends (k_chain_fwd2: 4 dependent eliminations per
-  // level instead of 7; measured 26.3 -> 21.7 us per level at cfg3).  Not at the bottom level: its 250 groups would need 500
-  // wavefronts of ~370 registers next to the weight update's 500 on the other stream, and queue behind them (42 vs 32 us).
-  // VICALIB_AMD_CHAIN_TWO=0: one-sided throughout
-  static const bool two_env = [] { const char* e = std::getenv("VICALIB_AMD_CHAIN_TWO"); return !(e && std::atoi(e) == 0); }();
-  const bool two_sided = two_env && cpl <= 2;
-  // ... and at the bottom level too once the weight update on the other stream starts behind it (vc_pass.cpp: enqueue_pass;
-  // VICALIB_AMD_CHAIN_TWO_BOTTOM=0: one-sided bottom level)
-  static const bool two_bottom = [] { const char* e = std::getenv("VICALIB_AMD_CHAIN_TWO_BOTTOM"); return !(e && std::atoi(e) == 0); }();
-  // (whatever the hand-over mode: a solve resumed with events after a flag time-out must repeat the withheld passes with the same
-  //  arithmetic -- with events the weight update runs beside the bottom level and the pass is ~4 us slower than one-sided would be)
-  const int two_from = two_bottom ? 0 : 1;
-  // (two columns per lane's worth of border, D <= 100: two wavefronts per sweep, a whole CU per group -- on levels whose groups the chip
-  //  holds at once; a function of the frame count and the level only: forward, backward and every hand-over mode agree on it)
-  auto two_at = [&](int l) {
-    if (!(two_sided && ms[l] >= 4 && l >= two_from)) return false;
-    if (cpl <= 1) return true;
-    const long groups = ((long)N - 1) / ((long)strides[l] * ms[l]) + 1;
-    return groups <= 256;
-  };
+  // narrow borders: the levels ChainPlan::two marks are eliminated from both ends (k_chain_fwd2: 4 dependent eliminations per level instead of 7)
   auto fwd = [&](int groups, int stride, int m, int top, int lvl) {
-    if (!top && two_at(lvl)) {
+    if (!top && p.two[lvl]) {
       // (hadd_early: the first launch above the bottom level carries the sums of the chunk records' entries behind S and g_red)
       const int extra = (v.hadd_early && lvl == 1) ? (v.part_stride - (v.D * v.D + v.D) + 15) / 16 : 0;
       if (cpl <= 1) hipLaunchKernelGGL(k_chain_fwd2<1>, dim3(groups + extra), dim3(128), 0, s, v, stride, m, lvl, groups);
@@ -3222,11 +3168,10 @@ static void chain_levels(const DevView& v, hipStream_t s, bool forward) {
   };
   if (forward) {
     for (int l = 0; l < nl; ++l) {
-      const int groups = (int)(((long)N - 1) / ((long)strides[l] * ms[l]) + 1);
       if (l == 0 && v.fold_l0) {      // the chain assembly rides in the bottom level's launch (k_chain_l0)
-        if (v.n_cams <= 1) hipLaunchKernelGGL(k_chain_l0<1>, dim3(groups), dim3(256), 0, s, v);
-        else hipLaunchKernelGGL(k_chain_l0<2>, dim3(groups), dim3(256), 0, s, v);
-      } else fwd(groups, strides[l], ms[l], 0, l);
+        if (v.n_cams <= 1) hipLaunchKernelGGL(k_chain_l0<1>, dim3(p.groups[0]), dim3(256), 0, s, v);
+        else hipLaunchKernelGGL(k_chain_l0<2>, dim3(p.groups[0]), dim3(256), 0, s, v);
+      } else fwd(p.groups[l], p.stride[l], p.m[l], 0, l);
     }
     if (v.gram_top_stride > 0) {
       // early Gram: the top level's one group and the Gram sums of all frames below it in one launch
@@ -3250,29 +3195,28 @@ static void chain_levels(const DevView& v, hipStream_t s, bool forward) {
     // the whole back-substitution as one launch without hand-overs (k_chain_back_path): any border width, sharded passes included
     if (v.back_path && nl >= 1 && nl <= 5) {
       BackPath P; P.n = nl;
-      for (int l = 0; l < 6; ++l) { P.stride[l] = l < nl ? strides[l] : 1; P.m[l] = l < nl ? ms[l] : 2; P.two[l] = (l < nl && two_at(l)) ? 1 : 0; }
+      for (int l = 0; l < 6; ++l) { P.stride[l] = l < nl ? p.stride[l] : 1; P.m[l] = l < nl ? p.m[l] : 2; P.two[l] = l < nl ? p.two[l] : 0; }
       const bool ct0 = v.D + 1 > kPathRowCols;
       P.top_stride = top_stride; P.ldr = ct0 ? 1 : ((v.D + 1) | 1); P.dsw = ((v.D + 63) / 64) * 64;
       if (ct0) hipLaunchKernelGGL(k_chain_t0, dim3((N + 3) / 4), dim3(256), 0, s, v);
-      const int groups0 = (int)(((long)N - 1) / ((long)strides[0] * ms[0]) + 1), nw = nl + 1;
+      const int nw = nl + 1;
       P.tail = (v.tail_deferred && nw >= 4) ? 1 : 0;
       const size_t lds = std::max(((size_t)nw * kPathDl + (size_t)nw * P.dsw + 4 + (ct0 ? 0 : (size_t)nw * 63 * P.ldr)), (size_t)(P.tail ? kTailLds : 0)) * sizeof(double);
       static LdsGrant g4, g6;
       auto go = [&](auto kern, LdsGrant& g) {
         if (lds > 60000 && g.need(lds)) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(kern, dim3(groups0 + P.tail), dim3(64 * nw), lds, s, v, P);
+        hipLaunchKernelGGL(kern, dim3(p.groups[0] + P.tail), dim3(64 * nw), lds, s, v, P);
       };
       if (nw <= 4) { if (ct0) go(k_chain_back_path<4, true>, g4); else go(k_chain_back_path<4, false>, g4); }
       else { if (ct0) go(k_chain_back_path<6, true>, g6); else go(k_chain_back_path<6, false>, g6); }
       return;
     }
     hipLaunchKernelGGL(k_chain_back, dim3(1 + (nl > 0 ? (N + kBackT0Frames - 1) / kBackT0Frames : 0)), dim3(64), 0, s, v, top_stride, m_top, 1, nl, 0);
-    // the levels below: one launch (k_chain_back_levels: ready words instead of kernel boundaries); VICALIB_AMD_BACK_FUSED=0: one launch per level
-    static const bool fused = [] { const char* e = std::getenv("VICALIB_AMD_BACK_FUSED"); return !(e && std::atoi(e) == 0); }();
+    // the levels below: one launch (k_chain_back_levels: ready words instead of kernel boundaries)
     // (only while every workgroup of the launch can be resident at once -- 119 registers, 4 wavefronts per SIMD, 4096 on the chip; half of
     //  that here: a group that waits for its separators then never keeps a producer from starting, whatever order the dispatcher picks)
     int total_groups = 0;
-    for (int l = 0; l < nl; ++l) total_groups += (int)(((long)N - 1) / ((long)strides[l] * ms[l]) + 1);
+    for (int l = 0; l < nl; ++l) total_groups += p.groups[l];
     // (half of what the device can hold of this kernel -- asked once, not a constant of one chip: the other half is left to whatever the
     //  second stream runs beside it)
     static const int resident_limit = [] {
@@ -3281,81 +3225,20 @@ static void chain_levels(const DevView& v, hipStream_t s, bool forward) {
           hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)k_chain_back_levels, 64, 0) != hipSuccess || per_cu <= 0) return 2048;
       return std::max(64, per_cu * pr.multiProcessorCount / 2);
     }();
-    if (fused && nl > 0 && nl <= 8 && v.cready && total_groups <= resident_limit) {
+    if (nl > 0 && nl <= 8 && v.cready && total_groups <= resident_limit) {
       BackLevels L; L.n = nl;
       int at = 0;
       for (int i = 0; i < nl; ++i) {
         const int l = nl - 1 - i;
-        L.start[i] = at; L.stride[i] = strides[l]; L.m[i] = ms[l]; L.two[i] = two_at(l) ? 1 : 0;
-        at += (int)(((long)N - 1) / ((long)strides[l] * ms[l]) + 1);
+        L.start[i] = at; L.stride[i] = p.stride[l]; L.m[i] = p.m[l]; L.two[i] = p.two[l];
+        at += p.groups[l];
       }
       for (int i = nl; i < 8; ++i) { L.start[i] = 1 << 30; L.stride[i] = 1; L.m[i] = 2; L.two[i] = 0; }
       hipLaunchKernelGGL(k_chain_back_levels, dim3(at), dim3(64), 0, s, v, L);
     } else
     for (int l = nl - 1; l >= 0; --l)
-      hipLaunchKernelGGL(k_chain_back, dim3((int)(((long)N - 1) / ((long)strides[l] * ms[l]) + 1)), dim3(64), 0, s, v, strides[l], ms[l], 0, l,
-                         two_at(l) ? 1 : 0);
+      hipLaunchKernelGGL(k_chain_back, dim3(p.groups[l]), dim3(64), 0, s, v, p.stride[l], p.m[l], 0, l, p.two[l]);
   }
-}
-// k_chain_l0 (the chain assembly folded into the bottom level) serves narrow borders, at most two cameras, groups of 8 eliminated from
-// both ends -- and at least one level below the top one
-bool chain_fold_supported(int n_frames, int D, int n_cams) {
-  static const bool two_env = [] { const char* e = std::getenv("VICALIB_AMD_CHAIN_TWO"); return !(e && std::atoi(e) == 0); }();
-  static const bool two_bottom = [] { const char* e = std::getenv("VICALIB_AMD_CHAIN_TWO_BOTTOM"); return !(e && std::atoi(e) == 0); }();
-  return two_env && two_bottom && chain_group_size() == kChainM && D + 1 + 27 <= 64 && n_cams <= 2 && (n_frames - 1) + 1 > kChainM - 1;
-}
-// The forward elimination has the two launches above the bottom level that carry the side jobs of DevView::hadd (vc_shared_blocks.hpp): a
-// two-sided level 1 (k_chain_fwd2: the sums of the chunk records' entries behind S and g_red) and the top level with the early Gram sums
-// (k_chain_top_gram: the record itself).  Mirrors chain_levels.
-bool chain_hadd_early(const DevView& v) {
-  if (!v.imu_on || !v.hadd || v.gram_top_stride <= 0 || v.n_frames < 1) return false;
-  static const bool two_env = [] { const char* e = std::getenv("VICALIB_AMD_CHAIN_TWO"); return !(e && std::atoi(e) == 0); }();
-  const int cpl = (v.D + 1 + 27 + 63) / 64;
-  if (!two_env || cpl > 2 || chain_group_size_upper() < 4) return false;
-  int nl = 0; long st = 1, st1 = 1;
-  while (true) {
-    const int m = nl == 0 ? chain_group_size() : chain_group_size_upper();
-    if (!((v.n_frames - 1) / st + 1 > m - 1)) break;
-    if (nl == 1) st1 = st;
-    ++nl; st *= m;
-  }
-  if (nl < 2) return false;
-  const long groups1 = ((long)v.n_frames - 1) / (st1 * chain_group_size_upper()) + 1;
-  return cpl <= 1 || groups1 <= 256;      // (two_at(1))
-}
-// the back-substitution is one launch of k_chain_back_path (chain_levels, backward) whose workgroups have at least 256 threads
-bool chain_back_is_path(const DevView& v) {
-  if (!v.back_path || v.n_frames < 1) return false;
-  int nl = 0; long st = 1;
-  while (true) {
-    const int m = nl == 0 ? chain_group_size() : chain_group_size_upper();
-    if (!((v.n_frames - 1) / st + 1 > m - 1)) break;
-    ++nl; st *= m;
-  }
-  return nl >= 3 && nl <= 5;
-}
-// stride of the frames the top level eliminates (1: no level below it)
-int chain_top_stride(int n_frames) {
-  if (n_frames < 1) return 1;
-  int nl = 0; long st = 1;
-  while (true) {
-    const int m = nl == 0 ? chain_group_size() : chain_group_size_upper();
-    if (!((n_frames - 1) / st + 1 > m - 1)) break;
-    ++nl; st *= m;
-  }
-  return (int)st;
-}
-// launches of the forward elimination (levels + the top level)
-int chain_forward_launches(const DevView& v) {
-  const int N = v.n_frames;
-  if (N < 1) return 0;
-  int nl = 0; long st = 1;
-  while (true) {
-    const int m = nl == 0 ? chain_group_size() : chain_group_size_upper();
-    if (!((N - 1) / st + 1 > m - 1)) break;
-    ++nl; st *= m;
-  }
-  return nl + 1;
 }
 void launch_chain_init(const DevView& v, hipStream_t s) {
   const size_t slot = (size_t)v.n_cams * kGStride + kGStride;
@@ -3366,7 +3249,7 @@ void launch_chain_init(const DevView& v, hipStream_t s) {
   };
   if (v.n_cams <= 1) go(k_chain_init<1>); else if (v.n_cams <= 2) go(k_chain_init<2>); else if (v.n_cams <= 4) go(k_chain_init<4>); else go(k_chain_init<8>);
 }
-void launch_chain_fwd(const DevView& v, hipStream_t s) { chain_levels(v, s, true); }
+void launch_chain_fwd(const DevView& v, const ChainPlan& p, hipStream_t s) { chain_levels(v, p, s, true); }
 static void chain_gram_go(const DevView& v, hipStream_t s, int gather) {
   const size_t lds = (size_t)36 * v.ldw * sizeof(double);
   const int nT = (v.D + 1 + 15) / 16, nPairs = nT * (nT + 1) / 2, nq = std::min(kMaxPairsPerWaveI, (nPairs + 3) / 4);
@@ -3386,6 +3269,6 @@ static void chain_gram_go(const DevView& v, hipStream_t s, int gather) {
 void launch_chain_gram(const DevView& v, hipStream_t s) { chain_gram_go(v, s, 0); }
 // early Gram where k_reduced does not add the top level's frames itself (D > kEarlyTopD, sharded passes): their sums as one more partial record
 void launch_chain_gram_top(const DevView& v, hipStream_t s) { chain_gram_go(v, s, 1); }
-void launch_chain_solve_b(const DevView& v, hipStream_t s) { chain_levels(v, s, false); }
+void launch_chain_solve_b(const DevView& v, const ChainPlan& p, hipStream_t s) { chain_levels(v, p, s, false); }
 
 }  // namespace vc

@@ -42,9 +42,6 @@ __device__ void merged_control(const DevView& v, Ctrl* out, double* red, bool wr
 //   <= 12 used columns (fov, linear; 3 block columns): 2 instructions -- diagonal (0,0)(1,1)(2,2)(3,3) and, with
 //                A = (0,0,1,3), B = (1,2,2,3): (0,1)(0,2)(1,2)(3,3)           [3 LDS reads per group]
 //   otherwise  : 3 instructions -- B = A rotated by 0, 1, 2 blocks: diagonal, (0,1)(1,2)(2,3)(3,0), (0,2)(1,3)(2,0)(3,1)
-#ifndef VC_JAC_SPLIT_ROWS
-#define VC_JAC_SPLIT_ROWS 1      // poly2 / poly3: the two row types' Gram blocks apart (jac_tile_body_split below; 0: the four-block-column form for A/B runs)
-#endif
 template <int MODEL>
 __device__ __forceinline__ double jac_tile_body(const DevView& v, const double* pose, const double* cam, double mult, int tile, int lane,
                                                 double* wl, double* G, int off_in, int cnt_in /* corner range if known (cnt_in >= 0) */) {
@@ -397,13 +394,8 @@ __device__ __forceinline__ double jac_tile_dispatch(const DevView& v, int model,
     // (fov / linear through the split form as well -- 48 instead of 64 matrix instructions per pass -- measured SLOWER: 237 against 233.5 us
     //  at cfg5 / 6250 frames, k_trial 16.8 against 15.6 us at cfg2: their tiles are three passes long and the per-tile assembly of the
     //  two compact blocks costs more than the instructions saved; poly3 at cfg4's nine passes per tile: 150 against 161 us)
-#if VC_JAC_SPLIT_ROWS
     case kPoly2: return jac_tile_body_split<kPoly2>(v, pose, cam, mult, tile, lane, wl, G, off, cnt);
     case kPoly3: return jac_tile_body_split<kPoly3>(v, pose, cam, mult, tile, lane, wl, G, off, cnt);
-#else
-    case kPoly2: return jac_tile_body<kPoly2>(v, pose, cam, mult, tile, lane, wl, G, off, cnt);
-    case kPoly3: return jac_tile_body<kPoly3>(v, pose, cam, mult, tile, lane, wl, G, off, cnt);
-#endif
     case kKb4: return jac_tile_body<kKb4>(v, pose, cam, mult, tile, lane, wl, G, off, cnt);
     case kRational6: return jac_tile_body<kRational6>(v, pose, cam, mult, tile, lane, wl, G, off, cnt);
     default: return jac_tile_body<kLinear>(v, pose, cam, mult, tile, lane, wl, G, off, cnt);
@@ -2175,19 +2167,9 @@ static inline int tiles_grid(const DevView& v) { return (v.n_tiles + 3) / 4; }
 
 void launch_reproj_jac(const DevView& v, hipStream_t s, int trial) {
   if (v.n_tiles == 0) return;
-  size_t lds = 4 * 64 * kDotStride * sizeof(double);
-  // Visual-inertial trial sweep: k_imu_jac(trial) starts on the second stream a few microseconds behind this kernel.  Both take ~230
-  // registers; two workgroups of this kernel per CU (two wavefronts per SIMD) leave no room for a wavefront of the other, which then runs
-  // behind this kernel's first round instead of beside it (26 instead of 17 us, and the pass ends with it).  One workgroup per CU here --
-  // a larger LDS request is the lever a launch has -- lets the two share every SIMD from the start: k_imu_jac 18 us, this kernel 24 us
-  // instead of 16 and now the last to end, with k_final's start-up no longer hidden behind the other stream: 0.2075 against 0.2035 ms per
-  // iteration.  Off; VICALIB_AMD_TRIAL_ONE_WG=1 for A/B runs
-  static const bool one_wg = [] { const char* e = std::getenv("VICALIB_AMD_TRIAL_ONE_WG"); return e && e[0] == '1'; }();
-  if (trial && v.imu_on && one_wg && tiles_grid(v) <= 1024) {
-    lds = 88 * 1024;
-    static LdsGrant granted;
-    if (granted.need(lds)) (void)hipFuncSetAttribute((const void*)k_reproj_jac, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  }
+  // (one workgroup per CU for the visual-inertial trial sweep, so that k_imu_jac(trial) shares every SIMD with it from the start, was
+  //  measured slower: 0.2075 against 0.2035 ms per iteration)
+  const size_t lds = 4 * 64 * kDotStride * sizeof(double);
   hipLaunchKernelGGL(k_reproj_jac, dim3(tiles_grid(v)), dim3(256), lds, s, v, trial);
 }
 void launch_part_sum(const DevView& v, hipStream_t s) {

@@ -82,7 +82,7 @@ int vc_calibrator::solve_once(Termination* term, double* final_cost, long* nres)
   if (d_sync.p) HIP_OK(hipMemsetAsync(d_sync.p + 6, 0, sizeof(long long), stream));
   pre_weights_fresh = false; pre_weights_pending = false;
   if (dv.imu_on && dv.weights_on) {     // UpdateImuWeights() before ceres::Solve (vicalibrator.h:955)
-    if (!serial_weights && stream2) { HIP_OK(hipEventRecord(ev_pre, stream)); pre_weights_pending = true; }
+    if (stream2) { HIP_OK(hipEventRecord(ev_pre, stream)); pre_weights_pending = true; }
     dv.sync_seq = 0;      // (not a pass: a sticky time-out mark left by the previous solve's last pass must not make this update skip itself)
     launch_imu_weights(dv, wcur, stream); wcur = 1 - wcur;
     pre_weights_fresh = true;
@@ -93,7 +93,7 @@ int vc_calibrator::solve_once(Termination* term, double* final_cost, long* nres)
   double enqueue_ms = 0.0, wait_ms = 0.0;
   const auto tso0 = std::chrono::steady_clock::now();
   for (;;) {                          // (one round, unless a device-flag hand-over runs into its bound: then a second one, with events)
-  const bool feed = !sharded() && !use_graphs && feed_passes && dv.imu_on;
+  const bool feed = !sharded() && !use_graphs && !sw.batched && dv.imu_on;
   if (feed) {
     // Single process, visual-inertial passes (18 launches at cfg3, ~270 us): the deciding thread publishes (decisions << 32 | done) to a page-locked word after every decision and
     // the host keeps kAhead passes queued beyond the last decision it has seen -- no stream synchronisation inside the

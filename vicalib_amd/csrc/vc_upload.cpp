@@ -206,12 +206,9 @@ int vc_calibrator::upload() {
   // wide borders: a chunk's partial record is D^2 doubles -- written once and read once per pass; keep all of them under ~64 MB
   // (8 cameras, 6250 frames per rank: 197 MB at 4 frames per chunk, k_part_sum 47 -> 19 us at 16)
   while (chunk_frames < 16 && (double)((N + chunk_frames - 1) / chunk_frames) * ((double)D * D + D + (C + 1) * kGStride) * 8.0 > 64e6) chunk_frames *= 2;
-  { const char* e = std::getenv("VICALIB_AMD_CHUNK_FRAMES"); if (e && std::atoi(e) >= 4) chunk_frames = std::atoi(e) / 4 * 4; }      // (A/B hook)
-  // the chain assembly folded into the bottom level of the elimination (k_chain_l0): a function of the problem only, never of the
-  // hand-over mode; its chunk of the partial sums is the group of 8 frames.  VICALIB_AMD_FOLD_L0=0: the two kernels apart (A/B)
-  static const bool fold_env = [] { const char* e = std::getenv("VICALIB_AMD_FOLD_L0"); return !(e && e[0] == '0'); }();
-  const bool fold = fold_env && imu_on() && !sharded() && !shard_imu && chain_fold_supported(N, D, C);
-  if (fold) chunk_frames = 8;
+  // the chain's levels and the forms of the visual-inertial pass (shard_imu implies sharded())
+  plan = plan_chain(N, D, C, imu_on(), sharded(), sw.chain);
+  if (plan.fold_l0) chunk_frames = kChainM;      // (k_chain_l0: the chunk of the partial sums is the bottom level's group)
   const int n_chunks = std::max(1, (N + chunk_frames - 1) / chunk_frames);
   const int part_stride = D * D + D + C * kGStride + (imu_on() ? kGStride : 0) + 2;     // ... + [x2 of observation-less frames, chunk cost] (vision path)
   for (int b = 0; b < 2; ++b) {
@@ -256,12 +253,10 @@ int vc_calibrator::upload() {
   dv.fdiag = d_fdiag.p; dv.fscale2 = d_fscale2.p; dv.part = d_part.p; dv.part_total = d_part_total.p; dv.Sbuf = d_Sbuf.p; dv.hadd = d_hadd.p; dv.part_ready = d_part_ready.p;
   dv.sdiag = d_sdiag.p; dv.sscale2 = d_sscale2.p; dv.slam = d_slam.p; dv.delta_s = d_delta_s.p;
   dv.fpart = d_fpart.p; dv.scal = d_scal.p; dv.flags = d_flags.p;
-  dv.pre_backsub = (T > 2048) ? 1 : 0;
-  { const char* e = std::getenv("VICALIB_AMD_PRE_BACKSUB"); if (e && (e[0] == '0' || e[0] == '1')) dv.pre_backsub = e[0] - '0'; }   // test hook     // 1024 SIMDs x 2 resident waves: beyond that the per-tile repeat of the back-substitution is pure cost
+  dv.pre_backsub = (sw.pre_backsub >= 0) ? sw.pre_backsub : (T > 2048) ? 1 : 0;      // 1024 SIMDs x 2 resident waves: beyond that the per-tile repeat of the back-substitution is pure cost
   {
-    // bottom-level groups of the chain elimination (launch_chain_solve_*: groups of 8 while more than 7 frames are active)
-    const int cm = chain_group_size();
-    const int groups = (N > cm - 1) ? (N - 1) / cm + 1 : 1;
+    // bottom-level groups of the chain elimination
+    const int groups = plan.bottom_groups;
     HIP_OK(d_grp_part.alloc((size_t)groups * kNumScal)); HIP_OK(d_wg_trial.alloc((size_t)std::max(1, (T + 3) / 4)));
     HIP_OK(d_wg_imu_trial.alloc((size_t)std::max(1, (N + 6) / 8)));
     dv.grp_part = d_grp_part.p; dv.wg_trial = d_wg_trial.p; dv.wg_imu_trial = d_wg_imu_trial.p; dv.n_chain_groups = groups;
@@ -285,24 +280,10 @@ int vc_calibrator::upload() {
   for (int a = 0; a < 15; ++a) dv.imu_param_col[a] = imu_param_col[a];
   dv.ldw = (((D + 1 + 15) / 16) * 16 % 32 == 0) ? ((D + 1 + 15) / 16) * 16 + 16 : ((D + 1 + 15) / 16) * 16;
   dv.ldx = dv.ldw + 32;
-  {
-    // early Gram (vc_device.h): narrow reduced systems of a single process; a function of the problem only, never of the hand-over
-    // mode -- a solve resumed with events after a flag time-out must repeat the withheld passes with the same arithmetic
-    static const bool early_env = [] { const char* e = std::getenv("VICALIB_AMD_EARLY_GRAM"); return !(e && e[0] == '0'); }();
-    // (where it pays: the top level's one group must outlast the Gram sums beside it -- at 6250 frames x 8 cameras, D = 115, the top
-    //  level is two frames and the sums take 50 us: 0.906 -> 0.938 ms per pass with them in its launch; at 2500 frames, D = 67: -4.5 us)
-    const bool narrow = D + 1 + 27 <= 128;      // at most two image columns per lane
-    dv.gram_top_stride = (early_env && dv.imu_on && N >= 1 && N <= 4096 && narrow) ? chain_top_stride(N) : 0;
-    dv.fold_l0 = fold ? 1 : 0;
-    // the back-substitution as one launch (k_chain_back_path): round 6 -- any border width, sharded passes (pinned frames) included
-    static const bool path_env = [] { const char* e = std::getenv("VICALIB_AMD_BACK_PATH"); return !(e && e[0] == '0'); }();
-    // (every bottom group recomputes the levels above it: (levels + 1) x the level-by-level form's work -- free while the bottom groups
-    //  fit the chip in one round, 120 us against 71 at 6250 frames x D = 115 (profiles/r06_per_rank_passes.txt): up to 4096 frames)
-    dv.back_path = (path_env && dv.imu_on && N <= 4096) ? 1 : 0;
-    // the top level's own frames: added by k_reduced (single process, narrow system) or a partial record of their own
-    top_gram_launch = dv.gram_top_stride > 0 && !(D <= kEarlyTopD && !sharded());
-    dv.n_part = dv.n_chunks + (top_gram_launch ? 1 : 0);
-  }
+  // the forms of the chain's launches: functions of the problem only, never of the hand-over mode -- a solve resumed with events after a
+  // flag time-out must repeat the withheld passes with the same arithmetic
+  dv.gram_top_stride = plan.gram_top_stride; dv.fold_l0 = plan.fold_l0; dv.back_path = plan.back_path;
+  dv.n_part = dv.n_chunks + plan.top_gram_launch;      // (the top level's own frames: added by k_reduced or a partial record of their own)
   dv.pin_first = (shard_imu && rank > 0) ? 1 : 0; dv.pin_last = ghost ? 1 : 0;
   dv.sep_col0 = D0 + 9 * (rank - 1); dv.sep_col1 = D0 + 9 * rank;
   HIP_OK(d_sep_strip.alloc((size_t)2 * 9 * dv.ldw)); dv.sep_strip = d_sep_strip.p;
@@ -325,12 +306,12 @@ int vc_calibrator::upload() {
     {
       const int ldw_max = (((Dmax + 1 + 15) / 16) * 16 % 32 == 0) ? ((Dmax + 1 + 15) / 16) * 16 + 16 : ((Dmax + 1 + 15) / 16) * 16;
       HIP_OK(d_cW.alloc(nf * 9 * (ldw_max + 32)));
-      for (int b = 0; b < 2; ++b) HIP_OK(d_rX[b].alloc((nf / std::min(chain_group_size(), chain_group_size_upper()) + 2) * 9 * (ldw_max + 32)));
+      for (int b = 0; b < 2; ++b) HIP_OK(d_rX[b].alloc((nf / kChainM + 2) * 9 * (ldw_max + 32)));
     }
     HIP_OK(d_cW.alloc(nf * 9 * dv.ldx)); HIP_OK(d_cdelta.alloc(nf * 9)); HIP_OK(d_ct0.alloc(nf * 9)); HIP_OK(d_cg.alloc(nf * 9)); HIP_OK(d_clam.alloc(nf * 9));
     HIP_OK(d_cdiag.alloc(nf * 9)); HIP_OK(d_cscale2.alloc(nf * 9));
     HIP_OK(d_cready.alloc(nf)); pack.zero(d_cready.p, nf * sizeof(long long));
-    for (int b = 0; b < 2; ++b) HIP_OK(d_rX[b].alloc((nf / std::min(chain_group_size(), chain_group_size_upper()) + 2) * 9 * dv.ldx));
+    for (int b = 0; b < 2; ++b) HIP_OK(d_rX[b].alloc((nf / kChainM + 2) * 9 * dv.ldx));
   }
   dv.imu_t = d_imu_t.p; dv.imu_w = d_imu_w.p; dv.imu_a = d_imu_a.p; dv.frame_time = d_frame_time.p;
   dv.vel[0] = d_vel[0].p; dv.vel[1] = d_vel[1].p; dv.imus[0] = d_imus[0].p; dv.imus[1] = d_imus[1].p;
