@@ -29,6 +29,7 @@
 #include <cstring>
 #include <fstream>
 #include <glob.h>
+#include <sys/stat.h>
 #include <map>
 #include <memory>
 #include <set>
@@ -60,7 +61,7 @@ static void DefineFlags() {
   Define("grid_spacing", "double", "0.01355", "Distance between circles on grid (m).");
   Define("grid_seed", "int32", "71", "Seed used to generate the grid.");
   Define("has_initial_guess", "bool", "false", "Whether or not the given calibration file has a valid guess.");
-  Define("output_conics", "bool", "false", "Echo the detections that were used (frame,dot_id,u,v,X,Y,Z).");
+  Define("output_conics", "bool", "false", "Echo the detections that were used (frame,dot_id,u,v,X,Y,Z), before the solve; their residuals come from -report_dir.");
   Define("grid_preset", "string", "", "Which grid preset to use: small, large, letter, medium.");
   Define("grid_pattern_file", "string", "", "(image input) large / small pattern of the target: grid_height rows of grid_width 0 / 1 entries (1 = large dot).");
   Define("max_reprojection_error", "double", "0.15", "Maximum allowed reprojection error (pixels).");
@@ -118,6 +119,10 @@ static void DefineFlags() {
   Define("frame_rate", "double", "30", "Frame rate used for timestamps when the detections carry no time column.");
   Define("device", "int32", "0", "HIP device ordinal (first device with -gpus N).");
   Define("gpus", "int32", "1", "Number of GPUs: frames are sharded, one calibrator per device, RCCL all-reduce per iteration.");
+  // residual report (vc_report_*): off unless asked for
+  Define("report_dir", "string", "", "Directory for the residual report of the result: views.csv, corners.csv, error_map_cam<c>.csv, imu_blocks.csv (empty: none).");
+  Define("report_bins", "string", "16x12", "Cells of the report's error maps, WIDTHxHEIGHT, each 1..32.");
+  Define("report_worst", "int32", "0", "Print the N views with the largest reprojection RMSE of every camera behind the results (0: none).");
 }
 
 static int Usage(int code) {
@@ -382,6 +387,14 @@ static void T2Cart(const double* T, double* c) {
   c[5] = std::atan2(R[3], R[0]);
 }
 
+// -report_bins WxH, each 1..32
+static bool ParseBins(const std::string& s, int* bx, int* by) {
+  int a = 0, b = 0; char tail = 0;
+  if (std::sscanf(s.c_str(), "%dx%d%c", &a, &b, &tail) != 2 || a < 1 || a > 32 || b < 1 || b > 32) return false;
+  *bx = a; *by = b;
+  return true;
+}
+
 int main(int argc, char** argv) {
   DefineFlags();
   std::string err;
@@ -390,6 +403,12 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "ERROR: %s\n", err.c_str());
     return 1;
   }
+  int report_bx = 16, report_by = 12;
+  if (!ParseBins(FlagString("report_bins"), &report_bx, &report_by)) {
+    std::fprintf(stderr, "ERROR: illegal value '%s' specified for flag 'report_bins': expected WIDTHxHEIGHT with both between 1 and 32\n", FlagString("report_bins").c_str());
+    return 1;
+  }
+  const bool want_report = !FlagString("report_dir").empty() || FlagInt("report_worst") > 0;
   if (FlagString("cam").empty()) { std::fprintf(stderr, "F No camera URI given\n"); return 1; }      // vicalib-engine.cc:445
   // ---- grid (vicalib-engine.cc:449-464): the detections already carry X,Y,Z; the preset only bounds the dot ids ----
   int grid_w = (int)FlagInt("grid_width"), grid_h = (int)FlagInt("grid_height");
@@ -508,6 +527,7 @@ int main(int argc, char** argv) {
     if (calibrate_imu && FlagBool("find_time_offset") && !FlagBool("use_system_time") && !imu.time.empty()) image_time_offset = imu.time[0] - t0f;
   }
   long n_obs = 0; int seeded = 0;
+  std::vector<std::vector<const Detection*>> rank_corners((size_t)n_gpus);      // (report) the detection behind every corner, in the order it was added
   for (int r = 0; r < n_gpus; ++r) {
     vic::ViCalibrator& cal = *cals[r];
     cal.SetSigmas(FlagDouble("gyro_sigma"), FlagDouble("accel_sigma"));                     // vicalib-engine.cc:301-303
@@ -545,6 +565,7 @@ int main(int argc, char** argv) {
           if (FlagBool("output_conics")) std::printf("%ld,%d,%.10g,%.10g,%.10g,%.10g,%.10g\n", d->frame, d->dot, d->u, d->v, d->X, d->Y, d->Z);
         }
         cal.AddObservations(kv.first, c, (int)kv.second.size(), pw.data(), pc.data());
+        if (want_report) rank_corners[r].insert(rank_corners[r].end(), kv.second.begin(), kv.second.end());
         n_obs += (long)kv.second.size();
       }
     }
@@ -614,6 +635,101 @@ int main(int argc, char** argv) {
         std::printf("\n");
       }
     } else std::printf("Failed to compute covariance...\n");
+  }
+
+  // ---- residual report (-report_dir, -report_worst): per rank, rows concatenated in frame order, maps summed ----------------------------
+  if (want_report) {
+    struct ViewRow { long frame; int cam, count, removed; double rmse, max_err; int worst_dot; };
+    std::vector<ViewRow> views;
+    std::vector<std::vector<double>> maps(n_cam, std::vector<double>((size_t)report_bx * report_by * 4, 0.0));
+    const std::string dir = FlagString("report_dir");
+    FILE* fc = nullptr; FILE* fi = nullptr;
+    bool ok = true;
+    if (!dir.empty()) {
+      (void)mkdir(dir.c_str(), 0777);
+      fc = std::fopen((dir + "/corners.csv").c_str(), "w");
+      if (!fc) { std::fprintf(stderr, "E cannot write the report into %s\n", dir.c_str()); ok = false; }
+      else std::fprintf(fc, "frame,camera,dot,u,v,ru,rv,removed\n");
+    }
+    try {
+      for (int r = 0; r < n_gpus && ok; ++r) {
+        vic::ViCalibrator& rc = *cals[r];
+        rc.ReportCompute(report_bx, report_by);
+        const std::vector<const Detection*>& dets = rank_corners[r];
+        const vic::ViCalibrator::ReportViews v = rc.GetReportViews();
+        for (size_t i = 0; i < v.frame.size(); ++i) {
+          const long wc = (long)v.worst_corner[i];
+          const long fid = frame_ids[frame_ids.size() * (size_t)r / (size_t)n_gpus + (size_t)v.frame[i]];      // (the rank's local frame -> id as in the input)
+          views.push_back(ViewRow{fid, v.camera[i], v.count[i], v.removed[i], v.count[i] > 0 ? std::sqrt(v.sum_sq[i] / (2.0 * v.count[i])) : 0.0, v.max_err[i],
+                                  wc >= 0 ? dets[(size_t)wc]->dot : -1});
+        }
+        for (size_t c = 0; c < n_cam; ++c) {
+          const std::vector<double> m = rc.GetReportErrorMap((int)c, report_bx, report_by);
+          for (size_t k = 0; k < m.size(); ++k) maps[c][k] += m[k];
+        }
+        if (fc) {
+          const size_t kSlice = 65536;
+          std::vector<double> res(2 * kSlice); std::vector<int> cam(kSlice); std::vector<unsigned char> fl(kSlice);
+          for (size_t first = 0; first < dets.size(); first += kSlice) {
+            const size_t n = std::min(kSlice, dets.size() - first);
+            rc.ReportCorners((long long)first, (long long)n, res.data(), nullptr, cam.data(), fl.data());
+            for (size_t k = 0; k < n; ++k) {
+              const Detection* d = dets[first + k];
+              std::fprintf(fc, "%ld,%d,%d,%.10g,%.10g,%.10g,%.10g,%d\n", d->frame, cam[k], d->dot, d->u, d->v, res[2 * k], res[2 * k + 1], (int)fl[k]);
+            }
+          }
+        }
+        const size_t nb = rc.NumReportImuBlocks();
+        if (nb > 0 && !dir.empty()) {
+          if (!fi) {
+            fi = std::fopen((dir + "/imu_blocks.csv").c_str(), "w");
+            if (fi) {
+              std::fprintf(fi, "frame,time");
+              for (int k = 0; k < 9; ++k) std::fprintf(fi, ",whitened%d", k);
+              for (int k = 0; k < 9; ++k) std::fprintf(fi, ",unwhitened%d", k);
+              std::fprintf(fi, ",flag\n");
+            }
+          }
+          std::vector<double> w(9 * nb), u(9 * nb); std::vector<unsigned char> fl(nb);
+          rc.ReportImu(w.data(), u.data(), fl.data());
+          const size_t lo = frame_ids.size() * (size_t)r / (size_t)n_gpus;
+          for (size_t s = 0; s < nb && fi; ++s) {
+            std::fprintf(fi, "%ld,%.9f", frame_ids[lo + s], rc.GetFrame(s).time);
+            for (int k = 0; k < 9; ++k) std::fprintf(fi, ",%.10g", w[9 * s + k]);
+            for (int k = 0; k < 9; ++k) std::fprintf(fi, ",%.10g", u[9 * s + k]);
+            std::fprintf(fi, ",%d\n", (int)fl[s]);
+          }
+        }
+      }
+    } catch (const std::exception& e) { std::fprintf(stderr, "E residual report failed: %s\n", e.what()); ok = false; }
+    if (fc) std::fclose(fc);
+    if (fi) std::fclose(fi);
+    if (ok && !dir.empty()) {
+      if (FILE* f = std::fopen((dir + "/views.csv").c_str(), "w")) {
+        std::fprintf(f, "frame,camera,corners,removed,rmse_px,max_px,worst_dot\n");
+        for (const ViewRow& v : views) std::fprintf(f, "%ld,%d,%d,%d,%.10g,%.10g,%d\n", v.frame, v.cam, v.count, v.removed, v.rmse, v.max_err, v.worst_dot);
+        std::fclose(f);
+      }
+      for (size_t c = 0; c < n_cam; ++c)
+        if (FILE* f = std::fopen((dir + "/error_map_cam" + std::to_string(c) + ".csv").c_str(), "w")) {
+          std::fprintf(f, "ix,iy,count,mean_ru,mean_rv,rms\n");
+          for (int iy = 0; iy < report_by; ++iy) for (int ix = 0; ix < report_bx; ++ix) {
+            const double* m = &maps[c][((size_t)iy * report_bx + ix) * 4];
+            const double n = m[0];
+            std::fprintf(f, "%d,%d,%.0f,%.10g,%.10g,%.10g\n", ix, iy, n, n > 0 ? m[1] / n : 0.0, n > 0 ? m[2] / n : 0.0, n > 0 ? std::sqrt(m[3] / (2.0 * n)) : 0.0);
+          }
+          std::fclose(f);
+        }
+    }
+    if (ok && FlagInt("report_worst") > 0)
+      for (size_t c = 0; c < n_cam; ++c) {
+        std::vector<const ViewRow*> of;
+        for (const ViewRow& v : views) if (v.cam == (int)c && v.count > 0) of.push_back(&v);
+        std::stable_sort(of.begin(), of.end(), [](const ViewRow* a, const ViewRow* b) { return a->rmse > b->rmse; });
+        std::printf("worst views of camera %zu (reprojection RMSE):\n", c);
+        for (size_t k = 0; k < of.size() && k < (size_t)FlagInt("report_worst"); ++k)
+          std::printf("  frame %ld: rmse %.6g px, max %.6g px at dot %d, %d corners, %d removed\n", of[k]->frame, of[k]->rmse, of[k]->max_err, of[k]->worst_dot, of[k]->count, of[k]->removed);
+      }
   }
 
   // ---- WriteCalibration (vicalib-engine.cc:353-372) + poses.csv (:407-421) ----------------------------------------------

@@ -244,6 +244,45 @@ int vc_get_imu_blocks(vc_calibrator* h, double* H, double* g, double* cost);
 /* Current weight_sqrt_ factors W (9 x 9 per IMU block, row-major) with W W^T = (J Sigma J^T)^-1, after vc_linearize
  * with the weight update active (UpdateImuWeights, vicalibrator.h:723-799).  vc_num_imu_blocks blocks, as vc_get_imu_blocks. */
 int vc_get_imu_weights(vc_calibrator* h, double* W);
+/* ---- residual report: which corners, views, image regions and IMU blocks carry the error ------------------------------------
+ * vc_report_compute runs two device sweeps at the current (accepted) state -- it uploads the problem first if it changed, like
+ * vc_evaluate, without touching the solve's bookkeeping -- and keeps their results until the problem or the state changes; the other
+ * entry points read slices of them.  Reading before a compute, or after an add_* / set_* / vc_clear / solve, is VC_ERR_BAD_ARG,
+ * never stale data.  Not collective: a sharded rank reports its own frames (frame numbers are the rank's local ones).  Nothing is
+ * allocated or launched for a calibrator that never asks.  bins_x / bins_y in [1, 32].  VC_ERR_RUNNING while a solve runs.
+ * Which corners count: after an outlier stage (vc_set_remove_outliers) a corner is either dropped (vision-only calibration: no copy
+ * of its residual block is left, it is not part of the problem any more) or kept with one copy fewer than the others
+ * (visual-inertial calibration).  vc_get_camera_proj_rmse, the view rows and the error maps count every corner that still has a
+ * copy, once each; dropped corners get a residual and a flag and enter no sum.  rmse of a camera = sqrt(sum sum_sq / (2 sum count))
+ * over its views, which is what vc_get_camera_proj_rmse returns. */
+int vc_report_compute(vc_calibrator* h, int bins_x, int bins_y);
+/* Corners [first, first + n) in the order the caller added them (vc_add_observations / vc_add_observation_tiles call order, then the
+ * order inside a call).  Any pointer may be NULL.  r: n x 2, (ru, rv) = projection - detection in pixels.  flags: bit 0 = dropped by
+ * the outlier stage (residual still reported, at the same state), bit 1 = kept with one copy fewer. */
+int vc_report_corners(vc_calibrator* h, long long first, long long n, double* r, int* frame, int* camera, unsigned char* flags);
+long long vc_report_num_corners(vc_calibrator* h);   /* every corner the caller added, dropped ones included (< 0: a status) */
+int vc_report_num_views(vc_calibrator* h);
+/* One row per (frame, camera) that has corners, ordered by frame, then camera (any pointer may be NULL): count = corners still in the
+ * problem, removed = corners the outlier stage marked (either kind), sum_sq = sum |r|^2 and max_err = max |r| over the corners still
+ * in the problem, worst_corner = the index (as in vc_report_corners) of the corner that has the maximum, the lowest one on ties,
+ * -1 in a view with no corner left. */
+int vc_report_views(vc_calibrator* h, int* frame, int* camera, int* count, int* removed, double* sum_sq, double* max_err,
+                    long long* worst_corner);
+/* Error map of one camera: the image cut into bins_x x bins_y cells, a corner belongs to the cell of its DETECTED pixel (u, v):
+ * ix = clamp(int(floor(u * bins_x / width)), 0, bins_x - 1), iy likewise with v, bins_y, height.  cells: bins_y x bins_x x 4 =
+ * count, sum ru, sum rv, sum |r|^2 over the corners still in the problem (sums, so that the maps of several ranks add up).  Summed in
+ * a fixed order: two reports of the same state give the same bits. */
+int vc_report_error_map(vc_calibrator* h, int camera, double* cells);
+/* IMU blocks of the report (vc_num_imu_blocks at the time of the compute; 0 without inertial terms in the stage), row s = the block
+ * from frame s to frame s + 1: the 9 residuals as the cost sees them (times the block's current weight_sqrt_, rotation-only switch
+ * applied: the block's cost is 1/2 x copies x CauchyLoss(100)(|whitened|^2)) and the 9 unweighted ones in the functor's order and
+ * units (log of the pose difference: translation 3, rotation 3; velocity difference 3).  flags: bit 0 = the block's IMU sample range
+ * is empty (rows are zero). */
+int vc_report_num_imu_blocks(vc_calibrator* h);
+int vc_report_imu(vc_calibrator* h, double* whitened /* x 9 */, double* unwhitened /* x 9 */, unsigned char* flags);
+/* Times the sweeps of the last vc_report_compute with HIP events on the calibrator's stream, `reps` launches each: out_ms[0] the vision
+ * sweep, [1] the error map's two passes, [2] the IMU sweep (the blocks' deltas + the residuals' tail; 0 without IMU blocks). */
+int vc_time_report_sweeps(vc_calibrator* h, int reps, double out_ms[3]);
 int vc_get_debug_stamps(vc_calibrator* h, long long out[32]);   /* shader-clock stamps of the last k_reduced (profiling aid) */
 long long vc_num_observations(vc_calibrator* h);
 int vc_num_tiles(vc_calibrator* h);

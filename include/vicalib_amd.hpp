@@ -155,6 +155,26 @@ class ViCalibrator {
     s.resize(s.find('\0'));
     return s;
   }
+  // residual report (vc_report_*): compute once at the current state, then read
+  struct ReportViews { std::vector<int> frame, camera, count, removed; std::vector<double> sum_sq, max_err; std::vector<long long> worst_corner; };
+  void ReportCompute(int bins_x = 16, int bins_y = 12) { vc_checked(vc_report_compute(h_, bins_x, bins_y), "ReportCompute"); }
+  void ReportCorners(long long first, long long n, double* r, int* frame, int* camera, unsigned char* flags) {
+    vc_checked(vc_report_corners(h_, first, n, r, frame, camera, flags), "ReportCorners");
+  }
+  ReportViews GetReportViews() {
+    const size_t n = (size_t)vc_checked(vc_report_num_views(h_), "ReportViews");
+    ReportViews v;
+    v.frame.resize(n); v.camera.resize(n); v.count.resize(n); v.removed.resize(n); v.sum_sq.resize(n); v.max_err.resize(n); v.worst_corner.resize(n);
+    vc_checked(vc_report_views(h_, v.frame.data(), v.camera.data(), v.count.data(), v.removed.data(), v.sum_sq.data(), v.max_err.data(), v.worst_corner.data()), "ReportViews");
+    return v;
+  }
+  std::vector<double> GetReportErrorMap(int camera, int bins_x, int bins_y) {      // bins_y x bins_x x 4, the bins of ReportCompute
+    std::vector<double> m((size_t)bins_x * bins_y * 4);
+    vc_checked(vc_report_error_map(h_, camera, m.data()), "ReportErrorMap");
+    return m;
+  }
+  size_t NumReportImuBlocks() { return (size_t)vc_checked(vc_report_num_imu_blocks(h_), "ReportImu"); }
+  void ReportImu(double* whitened, double* unwhitened, unsigned char* flags) { vc_checked(vc_report_imu(h_, whitened, unwhitened, flags), "ReportImu"); }
   vc_calibrator* handle() { return h_; }
 
  private:

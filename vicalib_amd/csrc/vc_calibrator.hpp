@@ -6,6 +6,7 @@
 // streams), vc_solve.cpp (ceres::Solve replacement: feeding passes, the stage machine, RMSE, outliers, gravity); the C entry points
 // are in vc_capi.cpp.
 #include "vc_host.hpp"
+#include "vc_report.hpp"
 
 // The run-time switches of the pass, read once per calibrator by vc_create: nothing else reads a pass switch from the environment
 struct Switches {
@@ -123,6 +124,37 @@ struct vc_calibrator {
   DBuf<unsigned char> d_mask;
   std::vector<int> h_tile_frame, h_tile_cam, h_tile_off, h_obs_index;   // h_obs_index: device corner -> host observation
   std::vector<int> cam_flags, cam_col0;
+  // ---- residual report (vc_report_*: vc_report.cpp, kernels in vc_report.hip).  Nothing here is allocated before the first
+  // vc_report_compute; `valid` falls with every upload and every solve (the state moved), reads also refuse while device_dirty
+  struct Report {
+    bool valid = false;
+    int bins_x = 0, bins_y = 0;
+    size_t n_all = 0;                          // corners the caller had added when the report was computed
+    DBuf<double2> d_res, d_dropped_uv;
+    DBuf<int> d_obs_index, d_marked, d_imu_flags;
+    DBuf<long long> d_worst;
+    DBuf<ReportDropped> d_dropped;
+    DBuf<double> d_view, d_map_part, d_map, d_imu, d_delta, d_grav;
+    DBuf<Ctrl> d_ctrl;                         // the record k_imu_block reads when it runs for the report
+    static constexpr size_t kStageCorners = 65536;      // read-out slice: 1 MiB of page-locked staging
+    double2* stage = nullptr;
+    std::vector<int> v_frame, v_cam, v_count, v_removed;      // view rows, ordered by frame, then camera
+    std::vector<double> v_sq, v_max, map, imu;
+    std::vector<long long> v_worst;
+    std::vector<int> imu_flags;
+    ReportView last{};                         // the sweeps' arguments of the last compute (vc_time_report_sweeps launches them again)
+    void release() {
+      valid = false; n_all = 0;
+      d_res.release(); d_dropped_uv.release(); d_obs_index.release(); d_marked.release(); d_imu_flags.release(); d_worst.release();
+      d_dropped.release(); d_view.release(); d_map_part.release(); d_map.release(); d_imu.release(); d_delta.release(); d_grav.release();
+      d_ctrl.release();
+      if (stage) (void)hipHostFree(stage);
+      stage = nullptr;
+    }
+    ~Report() { if (stage) (void)hipHostFree(stage); }
+  } rep;
+  int report_compute(int bins_x, int bins_y);
+  void report_launch_imu(const ReportView& r);      // k_imu_block on the report's buffers, then the tail sweep
 
   ~vc_calibrator() {
     stop();

@@ -70,6 +70,7 @@ int vc_clear(vc_calibrator* h) {
   h->mse = 0; h->num_iterations = 0; h->is_bias_active = false; h->is_scale_active = false; h->is_inertial_active = false;
   h->is_visual_active = true; h->rotation_only = true; h->is_finished = false; h->gravity_initialized = false;
   h->outliers_removed = false; h->vis_mult = 0; h->imu_mult = 0; h->wsqrt_frames = 0; h->imu_w.clear(); h->imu_a.clear(); h->imu_t.clear(); h->imu_uploaded = 0; h->imu_end_time = -1.0; h->trace.clear(); h->stage = 0; h->device_dirty = true; h->obs_dirty = true;
+  if (hipSetDevice(h->device) == hipSuccess) h->rep.release();
   return VC_OK;
 }
 

@@ -37,6 +37,7 @@ int vc_calibrator::upload() {
   HIP_OK(hipSetDevice(device));
   drop_graphs();
   pre_weights_fresh = false; pre_weights_pending = false;      // (the state is about to change under them)
+  rep.valid = false;                                           // (... and under a cached residual report)
   const bool up_timing = std::getenv("VICALIB_AMD_TIMING") != nullptr;
   const auto up_t0 = std::chrono::steady_clock::now();
   auto up_ms = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - up_t0).count(); };

@@ -32,6 +32,7 @@ SYMBOLS = [
     "vc_init_frame_poses_pnp", "vc_pnp_planar", "vc_pnp_planar_ransac", "vc_set_pnp_ransac", "vc_rccl_unique_id", "vc_set_shard_rccl", "vc_shard_comm_create", "vc_set_shard_comm", "vc_shard_comm_destroy", "vc_allreduce_calls", "vc_shard_info", "vc_pass_paths", "vc_last_error", "vc_get_imu_weights",
     "vc_solution_covariance_dim", "vc_get_solution_covariance", "vc_get_solution_covariance_names",
     "vc_target_make_pattern", "vc_target_find",
+    "vc_report_compute", "vc_report_num_corners", "vc_report_corners", "vc_report_num_views", "vc_report_views", "vc_report_error_map", "vc_report_num_imu_blocks", "vc_report_imu", "vc_time_report_sweeps",
     "vc_detector_create", "vc_detector_destroy", "vc_detector_set_params", "vc_detector_find", "vc_detector_find_conics",
 ]
 
@@ -94,6 +95,7 @@ def load():
         L.vc_get_num_iterations.restype = C.c_uint
         L.vc_get_stream.restype = C.c_void_p
         L.vc_num_observations.restype = C.c_longlong
+        L.vc_report_num_corners.restype = C.c_longlong
         L.vc_allreduce_calls.restype = C.c_longlong
         L.vc_last_error.restype = C.c_char_p
         for name in ("vc_destroy", "vc_detector_destroy", "vc_shard_comm_destroy"):
@@ -432,6 +434,41 @@ class ViCalibrator:
         H = np.zeros((ns, 33, 33)); g = np.zeros((ns, 33)); c = np.zeros(ns)
         _check(self.L.vc_get_imu_blocks(self.h, _d(H), _d(g), _d(c)), "imu_blocks")
         return H, g, c
+
+    def report(self, bins=(16, 12), corners=True):
+        """Residual report at the current state (vc_report_*): per corner (caller's order) r [n, 2], frame, camera, flags (bit 0 dropped by
+        the outlier stage, bit 1 kept with one copy fewer); per view frame, camera, count, removed, sum_sq, max_err, worst_corner; per
+        camera the error map [bins_y, bins_x, 4] = count, sum ru, sum rv, sum |r|^2; per IMU block whitened [9], unwhitened [9], flags."""
+        bx, by = int(bins[0]), int(bins[1])
+        _check(self.L.vc_report_compute(self.h, bx, by), "report_compute")
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)      # noqa: E731
+        out = {"bins": (bx, by)}
+        if corners:
+            n = _check(self.L.vc_report_num_corners(self.h), "report_num_corners")
+            r = np.zeros((n, 2)); fr = np.zeros(n, dtype=np.int32); cm = np.zeros(n, dtype=np.int32); fl = np.zeros(n, dtype=np.uint8)
+            _check(self.L.vc_report_corners(self.h, C.c_longlong(0), C.c_longlong(n), _d(r), vp(fr), vp(cm), vp(fl)), "report_corners")
+            out.update(r=r, frame=fr, camera=cm, flags=fl)
+        nv = _check(self.L.vc_report_num_views(self.h), "report_num_views")
+        v = dict(frame=np.zeros(nv, dtype=np.int32), camera=np.zeros(nv, dtype=np.int32), count=np.zeros(nv, dtype=np.int32), removed=np.zeros(nv, dtype=np.int32),
+                 sum_sq=np.zeros(nv), max_err=np.zeros(nv), worst_corner=np.zeros(nv, dtype=np.int64))
+        _check(self.L.vc_report_views(self.h, vp(v["frame"]), vp(v["camera"]), vp(v["count"]), vp(v["removed"]), vp(v["sum_sq"]), vp(v["max_err"]),
+                                      vp(v["worst_corner"])), "report_views")
+        out["views"] = v
+        maps = np.zeros((self.NumCameras(), by, bx, 4))
+        for c in range(self.NumCameras()):
+            _check(self.L.vc_report_error_map(self.h, c, vp(maps[c])), "report_error_map")
+        out["maps"] = maps
+        nb = _check(self.L.vc_report_num_imu_blocks(self.h), "report_num_imu_blocks")
+        w = np.zeros((nb, 9)); u = np.zeros((nb, 9)); f = np.zeros(nb, dtype=np.uint8)
+        _check(self.L.vc_report_imu(self.h, vp(w), vp(u), vp(f)), "report_imu")
+        out["imu"] = dict(whitened=w, unwhitened=u, flags=f)
+        return out
+
+    def time_report_sweeps(self, reps=20):
+        """Average ms per launch of the sweeps of the last report(): vision, error map, IMU (vc_time_report_sweeps)."""
+        out = np.zeros(3)
+        _check(self.L.vc_time_report_sweeps(self.h, int(reps), _d(out)), "time_report_sweeps")
+        return dict(vision=out[0], error_map=out[1], imu=out[2])
 
     def debug_stamps(self):
         out = np.zeros(32, dtype=np.int64)
