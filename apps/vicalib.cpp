@@ -20,6 +20,7 @@
 // -model_files, PnP seed pose per frame (vicalib-task.cc:335-348), Start(has_initial_guess) (vicalib-task.cc:226-234),
 // 30 ms polling loop (vicalib-engine.cc:376-431), WriteCalibration (:353-372), success test (vicalib-task.cc:831-856).
 #include <vicalib_amd.hpp>
+#include "../vicalib_amd/csrc/vc_holdout_select.hpp"      // which frames -holdout_every keeps out (host arithmetic, no device code)
 
 #include <algorithm>
 #include <chrono>
@@ -123,6 +124,9 @@ static void DefineFlags() {
   Define("report_dir", "string", "", "Directory for the residual report of the result: views.csv, corners.csv, error_map_cam<c>.csv, imu_blocks.csv (empty: none).");
   Define("report_bins", "string", "16x12", "Cells of the report's error maps, WIDTHxHEIGHT, each 1..32.");
   Define("report_worst", "int32", "0", "Print the N views with the largest reprojection RMSE of every camera behind the results (0: none).");
+  // held-out scoring (vc_holdout_*): off unless asked for
+  Define("holdout_every", "int32", "0", "Keep every Nth of the frames that survive -frame_skip and -num_vicalib_frames out of the calibration and score the result on "
+         "them: held-out RMSE per camera behind the results, holdout_views.csv and holdout_corners.csv with -report_dir (0: off; N >= 2).");
 }
 
 static int Usage(int code) {
@@ -395,6 +399,18 @@ static bool ParseBins(const std::string& s, int* bx, int* by) {
   return true;
 }
 
+// -holdout_every N: 0 or N >= 2
+static bool ParseHoldoutEvery(const std::string& s, int* every) {
+  int a = 0; char tail = 0;
+  if (std::sscanf(s.c_str(), "%d%c", &a, &tail) != 1 || a < 0 || a == 1) return false;
+  *every = a;
+  return true;
+}
+static const char* HoldoutStatusName(int s) {
+  static const char* names[] = {"converged", "max_iters", "underdetermined", "no_seed", "failed"};
+  return s >= 0 && s < 5 ? names[s] : "?";
+}
+
 int main(int argc, char** argv) {
   DefineFlags();
   std::string err;
@@ -409,6 +425,11 @@ int main(int argc, char** argv) {
     return 1;
   }
   const bool want_report = !FlagString("report_dir").empty() || FlagInt("report_worst") > 0;
+  int holdout_every = 0;
+  if (!ParseHoldoutEvery(FlagString("holdout_every"), &holdout_every)) {
+    std::fprintf(stderr, "ERROR: illegal value '%s' specified for flag 'holdout_every': expected 0 (off) or N >= 2 (N = 1 would leave no frame to calibrate from)\n", FlagString("holdout_every").c_str());
+    return 1;
+  }
   if (FlagString("cam").empty()) { std::fprintf(stderr, "F No camera URI given\n"); return 1; }      // vicalib-engine.cc:445
   // ---- grid (vicalib-engine.cc:449-464): the detections already carry X,Y,Z; the preset only bounds the dot ids ----
   int grid_w = (int)FlagInt("grid_width"), grid_h = (int)FlagInt("grid_height");
@@ -508,6 +529,18 @@ int main(int argc, char** argv) {
     }
   }
   if (frame_ids.empty()) { std::fprintf(stderr, "F no usable frames in the detections\n"); return 1; }
+  // ---- -holdout_every N: every Nth surviving frame is not a frame of the problem (vc_holdout_select.hpp); it is scored afterwards.  The IMU
+  // stream is unchanged: the blocks simply span the gaps
+  std::vector<long> held_ids;
+  if (holdout_every > 0) {
+    if (!vc::holdout_every_ok((long long)frame_ids.size(), holdout_every)) {
+      std::fprintf(stderr, "ERROR: illegal value '%d' specified for flag 'holdout_every': it leaves fewer than 2 of the %zu frames to calibrate from\n", holdout_every, frame_ids.size());
+      return 1;
+    }
+    std::vector<long> fit;
+    for (size_t i = 0; i < frame_ids.size(); ++i) (vc::holdout_is_held((long long)i, holdout_every) ? held_ids : fit).push_back(frame_ids[i]);
+    frame_ids.swap(fit);
+  }
 
   // ---- one calibrator per GPU; frames sharded contiguously, the library's own RCCL communicator does the per-iteration
   // all-reduces (-gpus 1: plain single-device run, no communicator) -----------------------------------------------------
@@ -730,6 +763,78 @@ int main(int argc, char** argv) {
         for (size_t k = 0; k < of.size() && k < (size_t)FlagInt("report_worst"); ++k)
           std::printf("  frame %ld: rmse %.6g px, max %.6g px at dot %d, %d corners, %d removed\n", of[k]->frame, of[k]->rmse, of[k]->max_err, of[k]->worst_dot, of[k]->count, of[k]->removed);
       }
+  }
+
+  // ---- held-out scoring (-holdout_every): rank 0's calibrator refits the poses of the frames kept out, cameras frozen at the result (the
+  // shared parameters are identical on every rank), and reports how well the calibration predicts views it has not seen ---------------------
+  if (!held_ids.empty()) {
+    try {
+      std::map<long, int> held_index;
+      for (size_t i = 0; i < held_ids.size(); ++i) held_index[held_ids[i]] = (int)i;
+      std::vector<int> tile_frame, tile_cam, point_id;
+      std::vector<long long> tile_off(1, 0);
+      std::vector<double> points, pc;
+      std::vector<const Detection*> dets;
+      for (size_t c = 0; c < n_cam; ++c) {
+        std::map<int, std::vector<const Detection*>> per_frame;
+        for (const Detection& d : channels[c].det) {
+          auto it = held_index.find(d.frame);
+          if (it == held_index.end() || d.dot >= grid_w * grid_h) continue;
+          per_frame[it->second].push_back(&d);
+        }
+        for (const auto& kv : per_frame) {
+          for (const Detection* d : kv.second) {
+            point_id.push_back((int)dets.size());
+            points.insert(points.end(), {d->X, d->Y, d->Z}); pc.insert(pc.end(), {d->u, d->v});
+            dets.push_back(d);
+          }
+          tile_frame.push_back(kv.first); tile_cam.push_back((int)c); tile_off.push_back((long long)dets.size());
+        }
+      }
+      // (a held-out frame nobody detected the target in still is a frame of the set)
+      tile_frame.push_back((int)held_ids.size() - 1); tile_cam.push_back(0); tile_off.push_back((long long)dets.size());
+      cal.HoldoutClear();
+      cal.HoldoutAddTiles((int)tile_frame.size(), tile_frame.data(), tile_cam.data(), tile_off.data(), points.data(), (int)dets.size(), point_id.data(), pc.data());
+      cal.HoldoutCompute(nullptr, 0);
+      const vic::ViCalibrator::HoldoutFrames hf = cal.GetHoldoutFrames();
+      const vic::ViCalibrator::HoldoutViews hv = cal.GetHoldoutViews();
+      const vic::ViCalibrator::HoldoutCameraRmse hr = cal.GetHoldoutCameraRmse();
+      for (size_t c = 0; c < n_cam; ++c) {
+        int k = 0;
+        for (size_t i = 0; i < hv.frame.size(); ++i) k += (hv.camera[i] == (int)c && hf.status[hv.frame[i]] <= 1) ? 1 : 0;
+        std::printf("Camera %zu: fitted RMSE %.6g px, held-out RMSE %.6g px over %d views, %lld corners\n", c, rmse[c], hr.rmse[c], k, hr.count[c]);
+      }
+      int by_status[5] = {0, 0, 0, 0, 0};
+      for (int st : hf.status) if (st >= 0 && st < 5) ++by_status[st];
+      std::printf("held-out frames: %zu (every %d.)", held_ids.size(), holdout_every);
+      for (int st = 0; st < 5; ++st) if (by_status[st] || st == 0) std::printf("%s %d %s", st ? "," : ":", by_status[st], HoldoutStatusName(st));
+      std::printf("\n");
+      const std::string dir = FlagString("report_dir");
+      if (!dir.empty()) {
+        (void)mkdir(dir.c_str(), 0777);
+        if (FILE* f = std::fopen((dir + "/holdout_views.csv").c_str(), "w")) {
+          std::fprintf(f, "frame,camera,corners,rmse_px,max_px,status,iterations\n");
+          for (size_t i = 0; i < hv.frame.size(); ++i)
+            std::fprintf(f, "%ld,%d,%d,%.10g,%.10g,%s,%d\n", held_ids[(size_t)hv.frame[i]], hv.camera[i], hv.count[i],
+                         hv.count[i] > 0 ? std::sqrt(hv.sum_sq[i] / (2.0 * hv.count[i])) : 0.0, hv.max_err[i], HoldoutStatusName(hf.status[hv.frame[i]]), hf.iterations[hv.frame[i]]);
+          std::fclose(f);
+        } else std::fprintf(stderr, "E cannot write the held-out scores into %s\n", dir.c_str());
+        if (FILE* f = std::fopen((dir + "/holdout_corners.csv").c_str(), "w")) {
+          std::fprintf(f, "frame,camera,dot,u,v,ru,rv\n");
+          const size_t kSlice = 65536;
+          std::vector<double> res(2 * kSlice); std::vector<int> cam(kSlice);
+          for (size_t first = 0; first < dets.size(); first += kSlice) {
+            const size_t n = std::min(kSlice, dets.size() - first);
+            cal.HoldoutCorners((long long)first, (long long)n, res.data(), nullptr, cam.data());
+            for (size_t k = 0; k < n; ++k) {
+              const Detection* d = dets[first + k];
+              std::fprintf(f, "%ld,%d,%d,%.10g,%.10g,%.10g,%.10g\n", d->frame, cam[k], d->dot, d->u, d->v, res[2 * k], res[2 * k + 1]);
+            }
+          }
+          std::fclose(f);
+        }
+      }
+    } catch (const std::exception& e) { std::fprintf(stderr, "E held-out scoring failed: %s\n", e.what()); }
   }
 
   // ---- WriteCalibration (vicalib-engine.cc:353-372) + poses.csv (:407-421) ----------------------------------------------

@@ -283,6 +283,50 @@ int vc_report_imu(vc_calibrator* h, double* whitened /* x 9 */, double* unwhiten
 /* Times the sweeps of the last vc_report_compute with HIP events on the calibrator's stream, `reps` launches each: out_ms[0] the vision
  * sweep, [1] the error map's two passes, [2] the IMU sweep (the blocks' deltas + the residuals' tail; 0 without IMU blocks). */
 int vc_time_report_sweeps(vc_calibrator* h, int reps, double out_ms[3]);
+/* ---- held-out scoring: how well does the calibration predict views it has NOT seen? ----------------------------------------------
+ * The hold-out set lives beside the problem, not in it: (frame, camera) groups of corners of held-out frames, numbered 0..n-1 in a
+ * numbering of their own, that have no pose in the problem.  vc_holdout_compute freezes the cameras at the host state (what
+ * vc_get_camera returns: after a solve, after vc_download_state, or on a calibrator that only had cameras added), refits the rig pose
+ * of every held-out frame on the device -- one pose-only robust least-squares problem per frame, 1/2 sum SoftLOne(0.5)(|r|^2) over all
+ * the frame's views jointly, Levenberg-Marquardt by the solver's own rules, first-order robustification (no Triggs correction) -- and
+ * evaluates the residuals at the refitted poses.  It never uploads or invalidates the solve's problem and never touches vc_trace_len,
+ * the iteration counters or the residual report; nothing is allocated or launched for a calibrator that never asks.  Tolerances are
+ * those of vc_set_function_tolerance and vc_set_tolerances; max_iters <= 0 means 50, values above 200 mean 200.  Not collective: on
+ * a sharded calibrator it is a local computation on whichever rank is asked.  VC_ERR_RUNNING while a solve runs.  The readers return
+ * VC_ERR_BAD_ARG, never stale data, before a compute and after vc_holdout_add_tiles, vc_holdout_clear, vc_clear, vc_add_camera,
+ * vc_fix_camera_intrinsics, a solve or anything else that changes what vc_get_camera returns.
+ * Frame status: 0 converged, 1 max_iters (the pose is the last accepted one), 2 underdetermined (fewer than 4 corners over all of the
+ * frame's views: not fitted, residuals evaluated at the seed), 3 no_seed (nothing evaluated: residuals and view sums are zero),
+ * 4 failed (five steps in a row without a usable factorisation or model decrease, or a seed the cost is not finite at).  Only frames
+ * of status 0 and 1 count as fitted. */
+int vc_holdout_clear(vc_calibrator* h);
+/* Same layout as vc_add_observation_tiles; tile_frame numbers the held-out frames; may be called repeatedly (appends; frame numbers
+ * continue to mean the same frames; corners of one (frame, camera) given in several groups form one view, in order of arrival).  A
+ * group of no corners still names its frame.  VC_ERR_BAD_ARG for a camera >= vc_num_cameras, a point id >= n_points or tile_off not
+ * monotone; VC_ERR_TOO_MANY_POINTS beyond 32768 distinct points in the set, as for the problem (the set is then left unchanged). */
+int vc_holdout_add_tiles(vc_calibrator* h, int n_tiles, const int* tile_frame, const int* tile_cam, const long long* tile_off /* n_tiles + 1 */,
+                         const double* points, int n_points, const int* point_id, const double* p_c /* x 2 */);
+/* seeds: n_frames x 7 T_wk, or NULL = seed every frame like vc_init_frame_poses_pnp does (camera 0 if it has >= 4 corners, else the
+ * last camera that has; plain or RANSAC per vc_set_pnp_ransac); a frame no view of which gives a pose is no_seed. */
+int vc_holdout_compute(vc_calibrator* h, const double* seeds, int max_iters);
+int vc_holdout_num_frames(vc_calibrator* h);           /* 1 + the largest frame number named (< 0: a status) */
+int vc_holdout_num_views(vc_calibrator* h);            /* (frame, camera) pairs that have corners */
+long long vc_holdout_num_corners(vc_calibrator* h);
+/* Per held-out frame (any pointer may be NULL): the refitted T_wk (the seed for status 2, identity for 3), status, LM iterations (steps
+ * tried), cost = 1/2 sum rho at the seed and at the returned pose, behind = corners at camera-frame depth <= 0 at the returned pose
+ * (such a corner enters no sum of the sweep that finds it there). */
+int vc_holdout_frames(vc_calibrator* h, double* T_wk /* x 7 */, int* status, int* iterations, double* cost0, double* cost, int* behind);
+/* One row per (frame, camera) that has corners, ordered by frame, then camera: count, sum |r|^2, max |r| and the corner that has it (index
+ * as in vc_holdout_corners, the lowest on ties).  Views of flagged frames keep their rows; their status is the frame's. */
+int vc_holdout_views(vc_calibrator* h, int* frame, int* camera, int* count, double* sum_sq, double* max_err, long long* worst_corner);
+/* Corners [first, first + n) in the order the caller added them: r = n x 2 (ru, rv) = projection - detection in pixels. */
+int vc_holdout_corners(vc_calibrator* h, long long first, long long n, double* r /* x 2 */, int* frame, int* camera);
+/* Per camera sqrt(sum sum_sq / (2 sum count)) over its views of fitted frames (status 0 or 1) -- the convention of
+ * vc_get_camera_proj_rmse -- and that corner count; 0 for a camera without such views. */
+int vc_holdout_camera_rmse(vc_calibrator* h, double* rmse /* n_cameras */, long long* count /* n_cameras */);
+/* Times the kernels of the last vc_holdout_compute with HIP events on the calibrator's stream, `reps` launches each, like
+ * vc_time_report_sweeps: out_ms[0] the pose refit (from the seeds, every time), [1] the residual sweep. */
+int vc_time_holdout(vc_calibrator* h, int reps, double out_ms[2]);
 int vc_get_debug_stamps(vc_calibrator* h, long long out[32]);   /* shader-clock stamps of the last k_reduced (profiling aid) */
 long long vc_num_observations(vc_calibrator* h);
 int vc_num_tiles(vc_calibrator* h);

@@ -175,6 +175,42 @@ class ViCalibrator {
   }
   size_t NumReportImuBlocks() { return (size_t)vc_checked(vc_report_num_imu_blocks(h_), "ReportImu"); }
   void ReportImu(double* whitened, double* unwhitened, unsigned char* flags) { vc_checked(vc_report_imu(h_, whitened, unwhitened, flags), "ReportImu"); }
+  // held-out scoring (vc_holdout_*): add the held-out views, compute at the current cameras, then read
+  struct HoldoutFrames { std::vector<Se3> T_wk; std::vector<int> status, iterations, behind; std::vector<double> cost0, cost; };
+  struct HoldoutViews { std::vector<int> frame, camera, count; std::vector<double> sum_sq, max_err; std::vector<long long> worst_corner; };
+  struct HoldoutCameraRmse { std::vector<double> rmse; std::vector<long long> count; };
+  void HoldoutClear() { vc_checked(vc_holdout_clear(h_), "HoldoutClear"); }
+  void HoldoutAddTiles(int n_tiles, const int* tile_frame, const int* tile_cam, const long long* tile_off, const double* points, int n_points,
+                       const int* point_id, const double* p_c) {
+    vc_checked(vc_holdout_add_tiles(h_, n_tiles, tile_frame, tile_cam, tile_off, points, n_points, point_id, p_c), "HoldoutAddTiles");
+  }
+  void HoldoutCompute(const double* seeds = nullptr, int max_iters = 0) { vc_checked(vc_holdout_compute(h_, seeds, max_iters), "HoldoutCompute"); }
+  HoldoutFrames GetHoldoutFrames() {
+    const size_t n = (size_t)vc_checked(vc_holdout_num_frames(h_), "HoldoutFrames");
+    HoldoutFrames f;
+    std::vector<double> T(7 * n);
+    f.T_wk.resize(n); f.status.resize(n); f.iterations.resize(n); f.behind.resize(n); f.cost0.resize(n); f.cost.resize(n);
+    vc_checked(vc_holdout_frames(h_, T.data(), f.status.data(), f.iterations.data(), f.cost0.data(), f.cost.data(), f.behind.data()), "HoldoutFrames");
+    for (size_t i = 0; i < n; ++i) std::memcpy(f.T_wk[i].data(), &T[7 * i], 56);
+    return f;
+  }
+  HoldoutViews GetHoldoutViews() {
+    const size_t n = (size_t)vc_checked(vc_holdout_num_views(h_), "HoldoutViews");
+    HoldoutViews v;
+    v.frame.resize(n); v.camera.resize(n); v.count.resize(n); v.sum_sq.resize(n); v.max_err.resize(n); v.worst_corner.resize(n);
+    vc_checked(vc_holdout_views(h_, v.frame.data(), v.camera.data(), v.count.data(), v.sum_sq.data(), v.max_err.data(), v.worst_corner.data()), "HoldoutViews");
+    return v;
+  }
+  long long NumHoldoutCorners() { const long long n = vc_holdout_num_corners(h_); vc_checked(n < 0 ? (int)n : 0, "HoldoutCorners"); return n; }
+  void HoldoutCorners(long long first, long long n, double* r, int* frame, int* camera) {
+    vc_checked(vc_holdout_corners(h_, first, n, r, frame, camera), "HoldoutCorners");
+  }
+  HoldoutCameraRmse GetHoldoutCameraRmse() {
+    HoldoutCameraRmse c;
+    c.rmse.resize(NumCameras()); c.count.resize(NumCameras());
+    vc_checked(vc_holdout_camera_rmse(h_, c.rmse.data(), c.count.data()), "HoldoutCameraRmse");
+    return c;
+  }
   vc_calibrator* handle() { return h_; }
 
  private:

@@ -1,0 +1,342 @@
+"""Held-out scoring (vc_holdout_*: pose refit of held-out frames on the device with the cameras frozen, then their residuals) through the C
+ABI, against a float64 host restatement of the per-frame problem (holdout_ref, projection from the CPU oracle) and numpy restatements of
+its own sums.  Tolerances are the project's: 1e-6 relative on recovered parameters (translation, floored at 1e-9 m; 1e-6 rad on the
+rotation) and on residuals at identical parameters (floor 1e-9 px), 1e-12 relative for sums that repeat the device's own arithmetic,
+0 ulp where a fixed reduction order promises the same bits."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import holdout_cases as hc
+import holdout_ref as hr
+import oracle_lib as ol
+from vicalib_amd import synth
+from vicalib_amd.lib import ViCalibrator
+
+pytestmark = pytest.mark.gpu
+CONVERGED, MAX_ITERS, UNDERDETERMINED, NO_SEED, FAILED = range(5)
+BAD_ARG = -2
+
+
+def _calibrator(case, cams=None, tight=True):
+    cal = ViCalibrator(0)
+    for (m, K, T) in (cams if cams is not None else case["cams"]):
+        cal.AddCamera(m, K, T, case["width"], case["height"])
+    if tight:
+        cal.SetFunctionTolerance(1e-12); cal.SetTolerances(1e-14, 1e-14)
+    return cal
+
+
+def _add(cal, case, frames=None, tiles=None):
+    tf, tc, off, ids, pix = hc.flat(tiles if tiles is not None else case["tiles"], frames)
+    cal.HoldoutAddTiles(tf, tc, off, case["grid_points"], ids, pix)
+
+
+def _corner_index(tiles):
+    """{frame: caller's indices of its corners, in tile order} for tiles added in list order."""
+    out, k = {}, 0
+    for (f, c, ids, px) in tiles:
+        out.setdefault(f, []).extend(range(k, k + len(ids))); k += len(ids)
+    return {f: np.array(v, dtype=int) for f, v in out.items()}
+
+
+def _check_views(res):
+    """Every view row from the returned corner residuals (the manner of test_report_gpu._check_views)."""
+    r, v = res["r"], res["views"]
+    mag = np.sqrt(r[:, 0] * r[:, 0] + r[:, 1] * r[:, 1])
+    keys = sorted(set(zip(res["frame"].tolist(), res["camera"].tolist())))
+    assert list(zip(v["frame"].tolist(), v["camera"].tolist())) == keys
+    for i, (f, c) in enumerate(keys):
+        idx = np.nonzero((res["frame"] == f) & (res["camera"] == c))[0]
+        assert v["count"][i] == len(idx)
+        ref_sq = float((r[idx, 0] * r[idx, 0] + r[idx, 1] * r[idx, 1]).sum())
+        assert abs(v["sum_sq"][i] - ref_sq) <= 1e-12 * ref_sq
+        w = idx[np.argmax(mag[idx])]
+        if mag[w] > 0:
+            assert v["worst_corner"][i] == w
+            assert abs(v["max_err"][i] - mag[w]) <= 1e-15 * mag[w]      # (the device's square root is specified to 1 ulp)
+    assert v["count"].sum() == len(r)
+
+
+def _check_against_reference(name, case, res, frames=None, label=""):
+    """Poses against holdout_ref, residuals and gradient against the oracle at the device's own poses; prints the worst of each."""
+    ref = hc.reference(name)
+    index = _corner_index(case["tiles"])
+    worst = dict(t=0.0, rot=0.0, res=0.0, grad=0.0)
+    for f in (frames if frames is not None else case["fitted"]):
+        T = res["frames"]["T_wk"][f]
+        Tr, _ = ref[f]
+        dt, dr = hr.pose_distance(T, Tr)
+        bound_t = max(1e-6 * np.linalg.norm(Tr[4:]), 1e-9)
+        worst["t"] = max(worst["t"], dt / bound_t); worst["rot"] = max(worst["rot"], dr / 1e-6)
+        fr = hc.ref_frame(case, f)
+        ro = fr.residuals(T)
+        err = np.abs(res["r"][index[f]] - ro); bound = 1e-6 * np.abs(ro) + 1e-9
+        worst["res"] = max(worst["res"], float((err / bound).max()))
+        g_here, g_seed = fr.gradient_max_norm(T), fr.gradient_max_norm(case["seeds"][f])
+        worst["grad"] = max(worst["grad"], g_here / (1e-6 * g_seed))
+    print("%s%s: worst of value / bound -- translation %.3e, rotation %.3e, residuals %.3e, gradient %.3e" % (name, label, worst["t"], worst["rot"], worst["res"], worst["grad"]))
+    assert worst["t"] <= 1.0 and worst["rot"] <= 1.0 and worst["res"] <= 1.0 and worst["grad"] <= 1.0
+
+
+# ------------------------------------------------------------------------------------------------ 1. optimum, all six models
+@pytest.mark.parametrize("model", hc.ALL_MODELS)
+def test_optimum_of_every_model_against_the_host_reference(model):
+    case = hc.models_case(model)
+    cal = _calibrator(case)
+    _add(cal, case)
+    res = cal.HoldoutCompute(case["seeds"], max_iters=100)
+    f = res["frames"]
+    print("%s: iterations %s, cost %s -> %s" % (model, f["iterations"].tolist(), np.array2string(f["cost0"], precision=4), np.array2string(f["cost"], precision=6)))
+    assert f["status"].tolist() == [CONVERGED] * 5 and not f["behind"].any()
+    assert np.all(f["cost"] < f["cost0"]) and np.all(f["iterations"] >= 1)
+    _check_against_reference("model-" + model, case, res)
+    _check_views(res)
+    for i in range(5):          # the returned cost is 1/2 sum rho of the returned residuals
+        idx = np.nonzero(res["frame"] == i)[0]
+        c = 0.5 * hr.rho((res["r"][idx] ** 2).sum(axis=1))[0].sum()
+        assert abs(f["cost"][i] - c) <= 1e-9 * c
+    rm = np.sqrt(res["views"]["sum_sq"].sum() / (2.0 * res["views"]["count"].sum()))
+    assert abs(res["rmse"][0] - rm) <= 1e-12 * rm and res["count"][0] == len(res["r"])
+
+
+# ------------------------------------------------------------------------------------------------ 2. rigs
+@pytest.mark.parametrize("models", [("fov", "kb4"), ("poly3", "rational6", "linear")])
+def test_rig_poses_come_from_the_joint_problem_seeded_and_from_pnp(models):
+    name = "rig%d" % len(models)
+    case = hc.rig_case(models)
+    cal = _calibrator(case)
+    _add(cal, case)
+    res = cal.HoldoutCompute(case["seeds"], max_iters=100)
+    assert res["frames"]["status"].tolist() == [CONVERGED] * 4
+    counts = {(f, c): n for f, c, n in zip(res["views"]["frame"], res["views"]["camera"], res["views"]["count"])}
+    assert (1, 0) not in counts and counts[(2, 0)] == 3 and counts[(2, 1)] == 150
+    _check_against_reference(name, case, res, label=" (seeded)")
+    _check_views(res)
+    # a pose from camera 1 alone would differ: frame 2's three corners of camera 0 and, in the 3-camera rig, camera 2 pull on it
+    pnp = cal.HoldoutCompute(None, max_iters=100)
+    assert pnp["frames"]["status"].tolist() == [CONVERGED] * 4
+    _check_against_reference(name, case, pnp, label=" (PnP seeds)")
+    _check_views(pnp)
+
+
+# ------------------------------------------------------------------------------------------------ 3. ragged and tail shapes
+def test_ragged_frames_in_one_launch_equal_their_one_frame_runs_bit_for_bit():
+    case = hc.ragged_case()
+    cal = _calibrator(case)
+    _add(cal, case)
+    res = cal.HoldoutCompute(case["seeds"], max_iters=100)
+    fa = res["frames"]
+    counts = [int(res["views"]["count"][res["views"]["frame"] == f].sum()) for f in range(7)]
+    assert counts == list(hc.RAGGED_COUNTS) + [380]
+    assert fa["status"].tolist() == [CONVERGED] * 7
+    print("ragged: iterations per frame", fa["iterations"].tolist())
+    assert len(set(fa["iterations"][:4].tolist())) > 1 or len(set(fa["iterations"][4:].tolist())) > 1      # different counts inside a workgroup
+    _check_against_reference("ragged", case, res)
+    _check_views(res)
+    index = _corner_index(case["tiles"])
+    one = _calibrator(case)
+    for f in range(7):
+        one.HoldoutClear()
+        _add(one, case, frames=[f])
+        r1 = one.HoldoutCompute(case["seeds"][f:f + 1], max_iters=100)
+        for k in ("T_wk", "status", "iterations", "cost0", "cost", "behind"):
+            np.testing.assert_array_equal(r1["frames"][k][0], fa[k][f], err_msg="frame %d: %s" % (f, k))
+        np.testing.assert_array_equal(r1["r"], res["r"][index[f]])
+        m = res["views"]["frame"] == f
+        for k in ("sum_sq", "max_err", "count", "camera"):
+            np.testing.assert_array_equal(r1["views"][k], res["views"][k][m])
+    # and twice the same set: the same bits
+    again = cal.HoldoutCompute(case["seeds"], max_iters=100)
+    for k in fa:
+        np.testing.assert_array_equal(again["frames"][k], fa[k])
+    np.testing.assert_array_equal(again["r"], res["r"])
+    for k in res["views"]:
+        np.testing.assert_array_equal(again["views"][k], res["views"][k])
+
+
+# ------------------------------------------------------------------------------------------------ 4. flagged frames
+def test_frames_that_cannot_be_fitted_are_flagged_not_fitted():
+    base = hc.ragged_case()
+    t = {(f, c): (ids, px) for (f, c, ids, px) in base["p"].tiles}
+    ids0, px0 = t[(0, 0)]; ids1, px1 = t[(1, 0)]; ids2, px2 = t[(2, 0)]
+    three = np.array([0, 9, 189])
+    tiles = [(0, 0, ids0[three], px0[three]),                 # 3 corners in all
+             (1, 0, ids1, px1),                               # a plain good frame
+             (2, 0, ids2, px2), (2, 1, ids2[:0], px2[:0]),    # a tile of no corners beside a good one
+             (3, 1, ids0[:0], px0[:0])]                       # a frame that is named and has nothing
+    case = dict(base, tiles=tiles, n_frames=4, seeds=np.array([hc.perturbed(base["p"].frame_T_wk_gt[f], 90 + f) for f in (0, 1, 2, 2)]))
+    cal = _calibrator(case)
+    _add(cal, case)
+    res = cal.HoldoutCompute(case["seeds"], max_iters=100)
+    f = res["frames"]
+    assert f["status"].tolist() == [UNDERDETERMINED, CONVERGED, CONVERGED, UNDERDETERMINED]
+    np.testing.assert_array_equal(f["T_wk"][0], case["seeds"][0])              # not fitted: the seed, residuals at the seed
+    assert f["iterations"][0] == 0 and f["cost"][0] == f["cost0"][0]
+    ro = hc.ref_frame(case, 0).residuals(case["seeds"][0])
+    assert np.all(np.abs(res["r"][:3] - ro) <= 1e-6 * np.abs(ro) + 1e-9)
+    assert list(zip(res["views"]["frame"].tolist(), res["views"]["camera"].tolist())) == [(0, 0), (1, 0), (2, 0)]
+    _check_views(res)
+    # only the fitted frames enter the camera sums; the counts add up
+    m = res["views"]["frame"] != 0
+    rm = np.sqrt(res["views"]["sum_sq"][m].sum() / (2.0 * res["views"]["count"][m].sum()))
+    assert abs(res["rmse"][0] - rm) <= 1e-12 * rm and res["rmse"][1] == 0.0
+    assert res["count"].tolist() == [380, 0] and len(res["r"]) == 383 == res["views"]["count"].sum()
+    # without seeds: the frame whose only view has 3 corners has no seed, nothing of it is evaluated
+    pnp = cal.HoldoutCompute(None, max_iters=100)
+    assert pnp["frames"]["status"].tolist() == [NO_SEED, CONVERGED, CONVERGED, NO_SEED]
+    assert not pnp["r"][:3].any() and pnp["views"]["sum_sq"][0] == 0.0 and pnp["views"]["worst_corner"][0] == -1 and pnp["views"]["count"][0] == 3
+    assert pnp["count"].tolist() == [380, 0]
+    for i in (1, 2):
+        dt, dr = hr.pose_distance(pnp["frames"]["T_wk"][i], f["T_wk"][i])
+        assert dt <= 1e-6 * np.linalg.norm(f["T_wk"][i][4:]) and dr <= 1e-6
+
+
+# ------------------------------------------------------------------------------------------------ 5. nothing else moves
+def _readers(cal):
+    L, h = cal.L, cal.h
+    z = C.c_void_p(None)
+    return [L.vc_holdout_num_frames(h), L.vc_holdout_num_views(h), int(L.vc_holdout_num_corners(h)), L.vc_holdout_frames(h, z, z, z, z, z, z),
+            L.vc_holdout_views(h, z, z, z, z, z, z), L.vc_holdout_corners(h, C.c_longlong(0), C.c_longlong(0), z, z, z), L.vc_holdout_camera_rmse(h, z, z),
+            L.vc_time_holdout(h, 1, z)]
+
+
+def test_the_solve_and_the_report_do_not_notice_a_holdout_compute():
+    p = synth.generate(synth.Config(models=("poly3",), n_frames=11, seed=21, pixel_sigma=0.1))
+    case = hc.models_case("poly3")
+    held = [t for t in p.tiles if t[0] >= 6]
+    p.tiles = [t for t in p.tiles if t[0] < 6]
+    p.frame_time = p.frame_time[:6]
+    cals = [ViCalibrator(0).load_problem(p), ViCalibrator(0).load_problem(p)]
+    for cal in cals:
+        cal.SetCalibrateImu(False); cal.SetMaxIters(6); cal.Solve()
+    a, b = cals
+    np.testing.assert_array_equal(a.trace(), b.trace())
+    # before a compute every reader refuses
+    assert all(rc == BAD_ARG for rc in _readers(a))
+    rep = a.report(); b.report()
+    n_trace, n_it = len(a.trace()), a.GetNumIterations()
+    tf, tc, off, ids, pix = hc.flat([(f - 6, c, i, px) for (f, c, i, px) in held])
+    a.HoldoutAddTiles(tf, tc, off, p.grid_points, ids, pix)
+    assert all(rc == BAD_ARG for rc in _readers(a))
+    res = a.HoldoutCompute(None)
+    assert set(res["frames"]["status"].tolist()) <= {CONVERGED, MAX_ITERS}
+    assert len(a.trace()) == n_trace and a.GetNumIterations() == n_it
+    # the report's readers still answer, with what they held
+    assert a.L.vc_report_num_views(a.h) == len(rep["views"]["frame"])
+    r2 = np.zeros_like(rep["r"])
+    assert a.L.vc_report_corners(a.h, C.c_longlong(0), C.c_longlong(len(r2)), r2.ctypes.data_as(C.c_void_p), None, None, None) == 0
+    np.testing.assert_array_equal(r2, rep["r"])
+    # two computes of the same set: the same bits
+    res2 = a.HoldoutCompute(None)
+    np.testing.assert_array_equal(res2["r"], res["r"]); np.testing.assert_array_equal(res2["frames"]["T_wk"], res["frames"]["T_wk"])
+    # stale after more tiles, after a camera setter, after a solve, after Clear
+    a.HoldoutAddTiles(tf[:1], tc[:1], off[:2], p.grid_points, ids, pix)
+    assert all(rc == BAD_ARG for rc in _readers(a))
+    a.HoldoutClear(); a.HoldoutAddTiles(tf, tc, off, p.grid_points, ids, pix); a.HoldoutCompute(None)
+    assert a.L.vc_holdout_num_frames(a.h) == 5
+    a.FixCameraIntrinsics(False); b.FixCameraIntrinsics(False)
+    assert all(rc == BAD_ARG for rc in _readers(a))
+    a.HoldoutCompute(None)
+    assert a.L.vc_holdout_num_frames(a.h) == 5
+    # the second solve: the same trace rows and state as the calibrator that never computed a hold-out, bit for bit
+    for cal in cals:
+        cal.Resume(); cal.SetMaxIters(25); cal.Solve()
+    assert all(rc == BAD_ARG for rc in _readers(a))
+    np.testing.assert_array_equal(a.trace(), b.trace())
+    np.testing.assert_array_equal(a.GetFrames(), b.GetFrames())
+    np.testing.assert_array_equal(a.GetCamera(0)[0], b.GetCamera(0)[0]); np.testing.assert_array_equal(a.GetCamera(0)[1], b.GetCamera(0)[1])
+    np.testing.assert_array_equal(a.GetCameraProjRMSE(), b.GetCameraProjRMSE())
+    assert a.GetNumIterations() == b.GetNumIterations()
+    a.HoldoutCompute(None)
+    assert a.L.vc_holdout_num_frames(a.h) == 5
+    a.Clear()
+    assert all(rc == BAD_ARG for rc in _readers(a))
+    del case
+
+
+def test_bad_indices_are_refused():
+    case = hc.models_case("poly3")
+    cal = _calibrator(case)
+    tf, tc, off, ids, pix = hc.flat(case["tiles"])
+    vp = lambda x: x.ctypes.data_as(C.c_void_p)      # noqa: E731
+    pts = np.ascontiguousarray(case["grid_points"])
+    add = lambda tf_, tc_, off_, ids_, n_pts: cal.L.vc_holdout_add_tiles(cal.h, len(tf_), vp(tf_), vp(tc_), vp(off_), vp(pts), n_pts, vp(ids_), vp(pix))      # noqa: E731
+    assert add(tf, tc + 1, off, ids, len(pts)) == BAD_ARG                         # camera >= vc_num_cameras
+    assert add(tf, tc, off, ids, int(ids.max())) == BAD_ARG                       # point id >= n_points
+    bad = off.copy(); bad[2] = bad[1] - 1
+    assert add(tf, tc, bad, ids, len(pts)) == BAD_ARG                             # tile_off not monotone
+    assert add(tf, tc, off, ids, len(pts)) == 0
+    many = np.arange(40000, dtype=np.float64)[:, None] * np.array([[1e-3, 0.0, 0.0]])
+    rc = cal.L.vc_holdout_add_tiles(cal.h, 1, vp(np.zeros(1, dtype=np.int32)), vp(np.zeros(1, dtype=np.int32)), vp(np.array([0, 40000], dtype=np.int64)), vp(many), 40000,
+                                    vp(np.arange(40000, dtype=np.int32)), vp(np.zeros((40000, 2))))
+    assert rc == -5                                                               # VC_ERR_TOO_MANY_POINTS, the set left as it was
+    res = cal.HoldoutCompute(case["seeds"], max_iters=100)
+    assert len(res["r"]) == int(off[-1]) and res["frames"]["status"].tolist() == [CONVERGED] * 5
+
+
+# ------------------------------------------------------------------------------------------------ 6. it detects what it is for
+def test_a_model_that_is_too_poor_shows_on_held_out_views_that_reach_the_image_corners():
+    """A poly3 camera calibrated as linear and as poly3 on 20 frames whose dots are kept within 0.8 of the half-diagonal of the image centre,
+    scored on 10 held-out frames that reach 0.96 of it.  (With a much smaller fitting region poly3 itself extrapolates badly -- at 0.4 its
+    held-out RMSE on the oracle path is 8 px: the r^6 term is not determined by the centre of the image.)
+    poly3: the held-out residuals are detection noise.  A frame of n corners has 2 n residual components of variance sigma^2 and 6 fitted
+    pose parameters, so E[sum |r|^2] = sigma^2 (2 n - 6) and, in the convention rmse^2 = sum |r|^2 / (2 M) over M corners of F frames,
+    E[rmse^2] = sigma^2 (1 - 6 F / (2 M)); the error of the estimated camera adds to it: the bound is 1.5 x that expectation.
+    linear: its held-out RMSE exceeds its fitted RMSE by a factor that is first measured on the oracle path (the oracle's own linear
+    calibration, held-out poses by holdout_ref); the device must show at least half of it."""
+    sigma = 0.1
+    p = synth.generate(synth.Config(models=("poly3",), n_frames=30, seed=31, pixel_sigma=sigma))
+    cx, cy = p.cfg.width / 2.0, p.cfg.height / 2.0
+    fit_tiles, held_tiles = [], []
+    for (f, c, ids, px) in p.tiles:
+        if f < 20:
+            m = np.hypot(px[:, 0] - cx, px[:, 1] - cy) < 0.8 * np.hypot(cx, cy)
+            assert m.sum() >= 30
+            fit_tiles.append((f, c, ids[m], px[m]))
+        else:
+            held_tiles.append((f - 20, c, ids, px))
+    reach = max(np.hypot(px[:, 0] - cx, px[:, 1] - cy).max() for (_, _, _, px) in held_tiles)
+    assert reach > 0.95 * np.hypot(cx, cy)
+    n_held = sum(len(t[2]) for t in held_tiles)
+    tf, tc, off, ids, pix = hc.flat(held_tiles)
+
+    def calibrate(model):
+        K0 = [300.0, 300.0, cx, cy] + [0.0] * (synth.MODEL_NK[synth.MODEL_IDS[model]] - 4)
+        cal = ViCalibrator(0); orc = ol.Oracle()
+        cal.AddCamera(model, K0, p.cam_T_ck_init[0], p.cfg.width, p.cfg.height); orc.add_camera(synth.MODEL_IDS[model], K0, p.cam_T_ck_init[0], p.cfg.width, p.cfg.height)
+        for n in range(20):
+            cal.AddFrame(p.frame_T_wk_init[n], p.frame_time[n]); orc.add_frame(p.frame_T_wk_init[n], p.frame_time[n])
+        for (f, c, i, px) in fit_tiles:
+            cal.AddObservations(f, c, p.grid_points[i], px); orc.add_observations(f, c, p.grid_points[i], px)
+        cal.SetCalibrateImu(False); cal.SetMaxIters(100); cal.Solve()
+        return cal, orc
+
+    # poly3: within the noise level
+    cal, _ = calibrate("poly3")
+    cal.HoldoutAddTiles(tf, tc, off, p.grid_points, ids, pix)
+    res = cal.HoldoutCompute(None)
+    assert set(res["frames"]["status"].tolist()) <= {CONVERGED, MAX_ITERS} and res["count"][0] == n_held
+    expected = sigma * np.sqrt(1.0 - 6.0 * 10 / (2.0 * n_held))
+    print("poly3: fitted RMSE %.4f px, held-out RMSE %.4f px, expectation from the noise %.4f px" % (cal.GetCameraProjRMSE()[0], res["rmse"][0], expected))
+    assert res["rmse"][0] <= 1.5 * expected
+    # linear: the oracle path first
+    cal, orc = calibrate("linear")
+    orc.set_options(calibrate_imu=False, max_iters=100); orc.solve()
+    Ko, To = orc.camera(0)
+    cams_o = [(synth.MODEL_IDS["linear"], Ko, To)]
+    sq = 0.0
+    for f in range(10):
+        fr = hr.Frame(cams_o, [(c, p.grid_points[i], px) for (ff, c, i, px) in held_tiles if ff == f])
+        T, info = hr.refine(fr, p.frame_T_wk_gt[20 + f])
+        assert info["g"] <= 1e-9 * info["g0"]
+        sq += float((fr.residuals(T) ** 2).sum())
+    factor_oracle = np.sqrt(sq / (2.0 * n_held)) / orc.rmse()[0]
+    cal.HoldoutAddTiles(tf, tc, off, p.grid_points, ids, pix)
+    res = cal.HoldoutCompute(None)
+    assert set(res["frames"]["status"].tolist()) <= {CONVERGED, MAX_ITERS}
+    factor = res["rmse"][0] / cal.GetCameraProjRMSE()[0]
+    print("linear: fitted RMSE %.4f px, held-out RMSE %.4f px: factor %.2f (oracle path: %.2f)" % (cal.GetCameraProjRMSE()[0], res["rmse"][0], factor, factor_oracle))
+    assert factor_oracle > 1.5                      # the case shows the effect at all (1.63 on the oracle path)
+    assert factor >= 0.5 * factor_oracle

@@ -7,6 +7,7 @@
 // are in vc_capi.cpp.
 #include "vc_host.hpp"
 #include "vc_report.hpp"
+#include "vc_validate.hpp"
 
 // The run-time switches of the pass, read once per calibrator by vc_create: nothing else reads a pass switch from the environment
 struct Switches {
@@ -155,6 +156,39 @@ struct vc_calibrator {
   } rep;
   int report_compute(int bins_x, int bins_y);
   void report_launch_imu(const ReportView& r);      // k_imu_block on the report's buffers, then the tail sweep
+  // ---- held-out scoring (vc_holdout_*: vc_validate.cpp, kernels in vc_validate.hip).  The hold-out set lives beside the problem: its
+  // own corners, point table and device buffers, none of them allocated before the first vc_holdout_compute.  `valid` falls with every
+  // change of the set, with vc_clear, with a camera setter and with a solve; reads also refuse once the host cameras differ from
+  // `cams_used`
+  struct Holdout {
+    bool valid = false;
+    int n_frames = 0;                            // 1 + the largest frame number a tile has named
+    std::vector<int> o_frame, o_cam, o_pid;      // the corners in the caller's order
+    std::vector<double> o_pc;
+    PointTable pts;
+    std::vector<HostCam> cams_used;              // the cameras of the last compute
+    DBuf<double> d_cams, d_points, d_seeds, d_pose, d_cost, d_view;
+    DBuf<int> d_frame_tile_off, d_tile_frame, d_tile_cam, d_tile_off, d_pt, d_obs_index, d_seed_ok, d_frame_int;
+    DBuf<double2> d_uv, d_res;
+    DBuf<long long> d_worst;
+    static constexpr size_t kStageCorners = 65536;      // read-out slice: 1 MiB of page-locked staging
+    double2* stage = nullptr;
+    std::vector<double> f_pose, f_cost0, f_cost, v_sq, v_max;
+    std::vector<int> f_status, f_iters, f_behind, v_frame, v_cam, v_count;
+    std::vector<long long> v_worst;
+    HoldoutView last{};                          // the kernels' arguments of the last compute (vc_time_holdout launches them again)
+    void release() {
+      valid = false; n_frames = 0;
+      o_frame.clear(); o_cam.clear(); o_pid.clear(); o_pc.clear(); pts.clear(); cams_used.clear();
+      d_cams.release(); d_points.release(); d_seeds.release(); d_pose.release(); d_cost.release(); d_view.release();
+      d_frame_tile_off.release(); d_tile_frame.release(); d_tile_cam.release(); d_tile_off.release(); d_pt.release(); d_obs_index.release();
+      d_seed_ok.release(); d_frame_int.release(); d_uv.release(); d_res.release(); d_worst.release();
+      if (stage) (void)hipHostFree(stage);
+      stage = nullptr;
+    }
+    ~Holdout() { if (stage) (void)hipHostFree(stage); }
+  } hold;
+  int holdout_compute(const double* seeds, int max_iters);
 
   ~vc_calibrator() {
     stop();

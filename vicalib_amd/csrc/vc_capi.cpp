@@ -70,7 +70,7 @@ int vc_clear(vc_calibrator* h) {
   h->mse = 0; h->num_iterations = 0; h->is_bias_active = false; h->is_scale_active = false; h->is_inertial_active = false;
   h->is_visual_active = true; h->rotation_only = true; h->is_finished = false; h->gravity_initialized = false;
   h->outliers_removed = false; h->vis_mult = 0; h->imu_mult = 0; h->wsqrt_frames = 0; h->imu_w.clear(); h->imu_a.clear(); h->imu_t.clear(); h->imu_uploaded = 0; h->imu_end_time = -1.0; h->trace.clear(); h->stage = 0; h->device_dirty = true; h->obs_dirty = true;
-  if (hipSetDevice(h->device) == hipSuccess) h->rep.release();
+  if (hipSetDevice(h->device) == hipSuccess) { h->rep.release(); h->hold.release(); }
   return VC_OK;
 }
 
@@ -87,10 +87,10 @@ int vc_add_camera(vc_calibrator* h, int model, const double* params, int nparams
   HostCam c; std::memset(&c, 0, sizeof(c));
   c.model = model; c.nk = nk; c.width = width; c.height = height;
   std::memcpy(c.K, params, nk * 8); std::memcpy(c.T_ck, T_ck, 56);
-  h->cams.push_back(c); h->cam_rmse.resize(h->cams.size(), 0.0); h->device_dirty = true;
+  h->cams.push_back(c); h->cam_rmse.resize(h->cams.size(), 0.0); h->device_dirty = true; h->hold.valid = false;
   return (int)h->cams.size() - 1;
 }
-int vc_fix_camera_intrinsics(vc_calibrator* h, int should_fix) { NOT_RUNNING(h); h->fix_intrinsics = should_fix != 0; h->device_dirty = true; return VC_OK; }
+int vc_fix_camera_intrinsics(vc_calibrator* h, int should_fix) { NOT_RUNNING(h); h->fix_intrinsics = should_fix != 0; h->device_dirty = true; h->hold.valid = false; return VC_OK; }
 int vc_add_frame(vc_calibrator* h, const double T_wk[7], double time) {
   NOT_RUNNING(h);
   if (!T_wk) return VC_ERR_BAD_ARG;

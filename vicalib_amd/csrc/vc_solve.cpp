@@ -58,6 +58,7 @@ int vc_calibrator::solve_once(Termination* term, double* final_cost, long* nres)
   RoctxRange rr("vicalib_amd: solve (ceres::Solve of one stage)");
   if (device_dirty) { int rc = upload(); if (rc) return rc; }
   rep.valid = false;                  // (a cached residual report describes the state this solve moves)
+  hold.valid = false;                 // (... and held-out scores describe the cameras it moves)
   *nres = 2L * ((long)dv.n_obs * vis_mult - n_one_less) + (dv.imu_on ? 9L * imu_mult * std::max(0, dv.n_frames - 1) : 0L);
   if (sharded()) {
     // The global residual count changes with the observation set and with the multiplicities.  The test for a fresh collective

@@ -33,6 +33,8 @@ SYMBOLS = [
     "vc_solution_covariance_dim", "vc_get_solution_covariance", "vc_get_solution_covariance_names",
     "vc_target_make_pattern", "vc_target_find",
     "vc_report_compute", "vc_report_num_corners", "vc_report_corners", "vc_report_num_views", "vc_report_views", "vc_report_error_map", "vc_report_num_imu_blocks", "vc_report_imu", "vc_time_report_sweeps",
+    "vc_holdout_clear", "vc_holdout_add_tiles", "vc_holdout_compute", "vc_holdout_num_frames", "vc_holdout_num_views", "vc_holdout_num_corners", "vc_holdout_frames", "vc_holdout_views",
+    "vc_holdout_corners", "vc_holdout_camera_rmse", "vc_time_holdout",
     "vc_detector_create", "vc_detector_destroy", "vc_detector_set_params", "vc_detector_find", "vc_detector_find_conics",
 ]
 
@@ -96,6 +98,7 @@ def load():
         L.vc_get_stream.restype = C.c_void_p
         L.vc_num_observations.restype = C.c_longlong
         L.vc_report_num_corners.restype = C.c_longlong
+        L.vc_holdout_num_corners.restype = C.c_longlong
         L.vc_allreduce_calls.restype = C.c_longlong
         L.vc_last_error.restype = C.c_char_p
         for name in ("vc_destroy", "vc_detector_destroy", "vc_shard_comm_destroy"):
@@ -469,6 +472,57 @@ class ViCalibrator:
         out = np.zeros(3)
         _check(self.L.vc_time_report_sweeps(self.h, int(reps), _d(out)), "time_report_sweeps")
         return dict(vision=out[0], error_map=out[1], imu=out[2])
+
+    HOLDOUT_STATUS = ("converged", "max_iters", "underdetermined", "no_seed", "failed")
+
+    def HoldoutClear(self): _check(self.L.vc_holdout_clear(self.h), "HoldoutClear")
+
+    def HoldoutAddTiles(self, tile_frame, tile_cam, tile_off, points, point_id, p_c):
+        """Held-out views in the layout of AddObservationTiles; tile_frame numbers the held-out frames (vc_holdout_add_tiles)."""
+        tf = np.ascontiguousarray(tile_frame, dtype=np.int32); tc = np.ascontiguousarray(tile_cam, dtype=np.int32)
+        off = np.ascontiguousarray(tile_off, dtype=np.int64); pid = np.ascontiguousarray(point_id, dtype=np.int32)
+        pts = np.ascontiguousarray(points, dtype=np.float64); pc = np.ascontiguousarray(p_c, dtype=np.float64)
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)      # noqa: E731
+        _check(self.L.vc_holdout_add_tiles(self.h, len(tf), vp(tf), vp(tc), vp(off), vp(pts), len(pts), vp(pid), vp(pc)), "HoldoutAddTiles")
+
+    def HoldoutCompute(self, seeds=None, max_iters=0, corners=True):
+        """Refit the held-out frames' poses with the cameras frozen and score them (vc_holdout_*).  seeds: [n_frames, 7] T_wk or None
+        (PnP seeds).  Returns frames = T_wk [n, 7], status, iterations, cost0, cost, behind; views = frame, camera, count, sum_sq, max_err,
+        worst_corner; per corner (caller's order) r [n, 2], frame, camera; per camera rmse and count over the fitted frames."""
+        sp = None
+        if seeds is not None:
+            seeds = np.ascontiguousarray(seeds, dtype=np.float64).reshape(-1, 7)
+            sp = seeds.ctypes.data_as(C.c_void_p)
+        _check(self.L.vc_holdout_compute(self.h, sp, int(max_iters)), "HoldoutCompute")
+        return self.HoldoutResults(corners)
+
+    def HoldoutResults(self, corners=True):
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)      # noqa: E731
+        nf = _check(self.L.vc_holdout_num_frames(self.h), "holdout_num_frames")
+        f = dict(T_wk=np.zeros((nf, 7)), status=np.zeros(nf, dtype=np.int32), iterations=np.zeros(nf, dtype=np.int32), cost0=np.zeros(nf), cost=np.zeros(nf),
+                 behind=np.zeros(nf, dtype=np.int32))
+        _check(self.L.vc_holdout_frames(self.h, vp(f["T_wk"]), vp(f["status"]), vp(f["iterations"]), vp(f["cost0"]), vp(f["cost"]), vp(f["behind"])), "holdout_frames")
+        nv = _check(self.L.vc_holdout_num_views(self.h), "holdout_num_views")
+        v = dict(frame=np.zeros(nv, dtype=np.int32), camera=np.zeros(nv, dtype=np.int32), count=np.zeros(nv, dtype=np.int32), sum_sq=np.zeros(nv), max_err=np.zeros(nv),
+                 worst_corner=np.zeros(nv, dtype=np.int64))
+        _check(self.L.vc_holdout_views(self.h, vp(v["frame"]), vp(v["camera"]), vp(v["count"]), vp(v["sum_sq"]), vp(v["max_err"]), vp(v["worst_corner"])), "holdout_views")
+        out = dict(frames=f, views=v)
+        if corners:
+            n = _check(self.L.vc_holdout_num_corners(self.h), "holdout_num_corners")
+            r = np.zeros((n, 2)); fr = np.zeros(n, dtype=np.int32); cm = np.zeros(n, dtype=np.int32)
+            _check(self.L.vc_holdout_corners(self.h, C.c_longlong(0), C.c_longlong(n), vp(r), vp(fr), vp(cm)), "holdout_corners")
+            out.update(r=r, frame=fr, camera=cm)
+        nc = self.NumCameras()
+        rm = np.zeros(max(nc, 1)); cnt = np.zeros(max(nc, 1), dtype=np.int64)
+        _check(self.L.vc_holdout_camera_rmse(self.h, vp(rm), vp(cnt)), "holdout_camera_rmse")
+        out.update(rmse=rm[:nc], count=cnt[:nc])
+        return out
+
+    def time_holdout(self, reps=20):
+        """Average ms per launch of the kernels of the last HoldoutCompute: pose refit, residual sweep (vc_time_holdout)."""
+        out = np.zeros(2)
+        _check(self.L.vc_time_holdout(self.h, int(reps), _d(out)), "time_holdout")
+        return dict(pose=out[0], residuals=out[1])
 
     def debug_stamps(self):
         out = np.zeros(32, dtype=np.int64)
