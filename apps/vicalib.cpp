@@ -127,6 +127,10 @@ static void DefineFlags() {
   // held-out scoring (vc_holdout_*): off unless asked for
   Define("holdout_every", "int32", "0", "Keep every Nth of the frames that survive -frame_skip and -num_vicalib_frames out of the calibration and score the result on "
          "them: held-out RMSE per camera behind the results, holdout_views.csv and holdout_corners.csv with -report_dir (0: off; N >= 2).");
+  // undistortion of the input images with the result (vc_undistort*): off unless asked for
+  Define("undistort_dir", "string", "", "(image input) Directory for the input images undistorted with the result, cam<i>_<name>.pgm, and cameras.xml with the "
+         "pinhole cameras they belong to (empty: none).  Its parent must exist; if the images cannot be written the tool says so and exits with status 1.");
+  Define("undistort_alpha", "double", "0", "Destination intrinsics of -undistort_dir: 0 = every pixel of an undistorted image is valid ... 1 = every source pixel is kept.");
 }
 
 static int Usage(int code) {
@@ -214,14 +218,19 @@ static bool ReadPgm(const std::string& path, int* w, int* h, std::vector<unsigne
   *w = (int)W; *h = (int)H;
   return true;
 }
+static bool GlobSorted(const std::string& pattern_glob, std::vector<std::string>* files) {
+  glob_t g; std::memset(&g, 0, sizeof(g));
+  const bool ok = glob(pattern_glob.c_str(), 0, nullptr, &g) == 0 && g.gl_pathc > 0;
+  if (ok) files->assign(g.gl_pathv, g.gl_pathv + g.gl_pathc);
+  globfree(&g);
+  std::sort(files->begin(), files->end());
+  return ok;
+}
 struct TargetSpec { std::vector<int> pattern; int rows = 0, cols = 0; double spacing = 0.0; };
 // one camera channel from a glob of images: frame k = k-th file (sorted); detections carry the target dot's index and position
 static bool ReadImages(const std::string& pattern_glob, const TargetSpec& tg, int device, Channel* ch, int* width, int* height, std::string* err) {
-  glob_t g; std::memset(&g, 0, sizeof(g));
-  if (glob(pattern_glob.c_str(), 0, nullptr, &g) != 0 || g.gl_pathc == 0) { globfree(&g); *err = "no images match " + pattern_glob; return false; }
-  std::vector<std::string> files(g.gl_pathv, g.gl_pathv + g.gl_pathc);
-  globfree(&g);
-  std::sort(files.begin(), files.end());
+  std::vector<std::string> files;
+  if (!GlobSorted(pattern_glob, &files)) { *err = "no images match " + pattern_glob; return false; }
   vc_detector* det = nullptr;
   std::vector<unsigned char> px;
   const int kMax = 4096;
@@ -409,6 +418,62 @@ static bool ParseHoldoutEvery(const std::string& s, int* every) {
 static const char* HoldoutStatusName(int s) {
   static const char* names[] = {"converged", "max_iters", "underdetermined", "no_seed", "failed"};
   return s >= 0 && s < 5 ? names[s] : "?";
+}
+
+// -undistort_dir: every input image of every camera through the calibrated model into a pinhole camera of the same size (intrinsics from
+// vc_undistort_fit_linear at -undistort_alpha), in batches of at most 64 images per call; dir/cameras.xml is the rig with every camera
+// replaced by that pinhole camera, T_ck kept, written by the calibrator's own XML writer
+static bool UndistortInputs(vic::ViCalibrator& cal, const std::vector<std::string>& cam_globs, const std::vector<vic::CameraAndPose>& input_cameras,
+                            bool calibrate_imu, int device, const std::string& dir, double alpha, std::string* err) {
+  struct stat st;
+  if (mkdir(dir.c_str(), 0777) != 0 && !(stat(dir.c_str(), &st) == 0 && S_ISDIR(st.st_mode))) {      // (one level: parents must exist)
+    *err = "cannot create the directory " + dir;
+    return false;
+  }
+  vic::ViCalibrator rig(device);
+  rig.SetCalibrateImu(calibrate_imu);                 // (the XML writer's axis convention follows it)
+  const int kBatch = 64;
+  for (size_t c = 0; c < cam_globs.size(); ++c) {
+    vic::CameraAndPose cam = cal.GetCamera(c);
+    cam.model = input_cameras[c].model; cam.width = input_cameras[c].width; cam.height = input_cameras[c].height;
+    const int w = cam.width, h = cam.height;
+    const vic::LinearCamera dst = vic::Undistorter::FitLinear(cam, w, h, alpha);
+    vic::Undistorter und(cal, (int)c, dst);
+    std::vector<std::string> files;
+    if (!GlobSorted(cam_globs[c], &files)) { *err = "no images match " + cam_globs[c]; return false; }
+    std::vector<unsigned char> in, out, px;
+    for (size_t first = 0; first < files.size(); first += kBatch) {
+      const size_t n = std::min((size_t)kBatch, files.size() - first), np = (size_t)w * h;
+      in.resize(n * np); out.resize(n * np);
+      for (size_t k = 0; k < n; ++k) {
+        int iw = 0, ih = 0;
+        if (!ReadPgm(files[first + k], &iw, &ih, &px, err)) return false;
+        if (iw != w || ih != h) { *err = files[first + k] + ": image size differs from the camera's"; return false; }
+        std::memcpy(in.data() + k * np, px.data(), np);
+      }
+      und.Images((int)n, in.data(), w, (long long)np, out.data(), w, (long long)np);
+      for (size_t k = 0; k < n; ++k) {
+        std::string name = files[first + k];
+        const size_t slash = name.find_last_of('/');
+        if (slash != std::string::npos) name = name.substr(slash + 1);
+        const size_t dot = name.find_last_of('.');
+        if (dot != std::string::npos && dot > 0) name = name.substr(0, dot);
+        const std::string path = dir + "/cam" + std::to_string(c) + "_" + name + ".pgm";
+        FILE* f = std::fopen(path.c_str(), "wb");
+        if (!f) { *err = "cannot write " + path; return false; }
+        std::fprintf(f, "P5\n%d %d\n255\n", w, h);
+        std::fwrite(out.data() + k * np, 1, np, f);
+        std::fclose(f);
+      }
+    }
+    vic::CameraAndPose lin;
+    lin.model = VC_MODEL_LINEAR; lin.params.assign(dst.fu_fv_u0_v0.begin(), dst.fu_fv_u0_v0.end()); lin.width = w; lin.height = h; lin.T_ck = cam.T_ck;
+    rig.AddCamera(lin);
+    std::fprintf(stderr, "I camera %zu: %zu images undistorted into %s (pinhole fu %.6g fv %.6g u0 %.6g v0 %.6g)\n", c, files.size(), dir.c_str(),
+                 dst.fu_fv_u0_v0[0], dst.fu_fv_u0_v0[1], dst.fu_fv_u0_v0[2], dst.fu_fv_u0_v0[3]);
+  }
+  rig.WriteCameraModels(dir + "/cameras.xml");
+  return true;
 }
 
 int main(int argc, char** argv) {
@@ -839,6 +904,16 @@ int main(int argc, char** argv) {
 
   // ---- WriteCalibration (vicalib-engine.cc:353-372) + poses.csv (:407-421) ----------------------------------------------
   cal.WriteCameraModels(FlagString("output"));
+  bool undistort_failed = false;
+  if (!FlagString("undistort_dir").empty()) {
+    if (!from_images) std::fprintf(stderr, "W -undistort_dir needs image input (-cam file://...): nothing to undistort\n");
+    else {
+      try {
+        if (!UndistortInputs(cal, cam_files, input_cameras, calibrate_imu, (int)FlagInt("device"), FlagString("undistort_dir"), FlagDouble("undistort_alpha"), &err))
+          { std::fprintf(stderr, "E undistortion failed: %s\n", err.c_str()); undistort_failed = true; }
+      } catch (const std::exception& e) { std::fprintf(stderr, "E undistortion failed: %s\n", e.what()); undistort_failed = true; }
+    }
+  }
   if (FlagBool("print_poses")) {
     if (FILE* f = std::fopen("poses.txt", "w")) {
       for (size_t i = 0; i < all_frames.size(); ++i) { double c[6]; T2Cart(all_frames[i].t_wp_.data(), c); std::fprintf(f, "%f\t%f\t%f\t%f\t%f\t%f\n", c[0], c[1], c[2], c[3], c[4], c[5]); }
@@ -873,5 +948,6 @@ int main(int argc, char** argv) {
     if (IMUCalibrationDiffer(input_imu_biases, bias_now.data(), FlagString("imu_diff_sense") != "corrected")) success = false;
   }
   std::printf("calibration %s -> %s\n", success ? "succeeded" : "FAILED", FlagString("output").c_str());
-  return success ? 0 : 2;
+  if (undistort_failed) std::fprintf(stderr, "E -undistort_dir: the undistorted images are incomplete (exit status %d)\n", success ? 1 : 2);
+  return success ? (undistort_failed ? 1 : 0) : 2;
 }

@@ -365,6 +365,53 @@ int vc_detector_find_conics(vc_detector* d, const unsigned char* image, int pitc
 int vc_target_make_pattern(int rows, int cols, unsigned seed, int* pattern);
 int vc_target_find(const double* centres, const double* conics, int n, const int* pattern, int rows, int cols, int* dot_index, int* n_matched);
 
+/* ---- using the calibration: undistortion on the device ----------------------------------------------------------------------------
+ * What a caller of the reference does with cameras.xml through Calibu (Unproject, lookup-table rectification; tracker.cc:82-85 works with
+ * a loaded model and K().inverse()): images and pixels of a calibrated SOURCE camera (any of the six models) mapped into an ideal pinhole
+ * DESTINATION camera dst_linear = [fu fv u0 v0] of dst_w x dst_h pixels, rotated against the source by R_ds (row-major; maps source-camera
+ * rays to destination-camera rays: pass a rectifying rotation for a stereo pair; NULL = identity).  Pixel centres are at integers, as in
+ * the detector.  The handle builds its lookup table once (destination pixel -> source coordinate, fp32), owns a stream and pinned
+ * staging buffers, and is single-threaded like a detector: one call in flight per handle.  No CPU fallback: VC_ERR_NO_DEVICE without a HIP
+ * device.  VC_ERR_BAD_ARG: unknown model, wrong nparams, a size below 2 x 2 or above 8192, fill outside 0..255, an R_ds that is not a
+ * rotation to 1e-9.
+ * A destination pixel has NO source pixel -- it gets `fill` -- when its ray has z <= 0 in the source frame (any model but kb4), does not
+ * project to finite coordinates, or lands outside [0, src_w - 1] x [0, src_h - 1] (closed to rounding: within 1e-9 px it is on the border). */
+typedef struct vc_undistorter vc_undistorter;
+int vc_undistorter_create(int device, int model, const double* params, int nparams, int src_w, int src_h, const double dst_linear[4], int dst_w,
+                          int dst_h, const double R_ds[9], int fill, vc_undistorter** out);
+/* the same for camera `camera` of a calibrator as vc_get_camera returns it (model, intrinsics and size), on the calibrator's device */
+int vc_undistorter_create_for_camera(vc_calibrator* h, int camera, const double dst_linear[4], int dst_w, int dst_h, const double R_ds[9], int fill,
+                                     vc_undistorter** out);
+void vc_undistorter_destroy(vc_undistorter* u);
+/* Destination intrinsics for identity rotation (host code, no device).  The source image's border -- its corners and 64 points inside every
+ * edge -- is unprojected into the pinhole plane; samples without a pinhole image are dropped (fewer than 8 left: VC_ERR_NUMERIC).
+ * alpha = 0: the axis-aligned rectangle between the innermost samples of the four edges fills the destination image, drawn in until every
+ * destination pixel has a source pixel; alpha = 1: the bounding box of the samples fills it (every source pixel is kept); in between the
+ * two rectangles are interpolated linearly.  alpha outside [0, 1] is VC_ERR_BAD_ARG. */
+int vc_undistort_fit_linear(int model, const double* params, int nparams, int src_w, int src_h, int dst_w, int dst_h, double alpha, double dst_linear[4]);
+/* n images, HOST buffers: image k starts at src + k * src_stride, its rows are src_pitch bytes apart (likewise dst); pitches may exceed the
+ * widths, and a destination row's padding is not written.  Bilinear: x0 = min(floor(x), src_w - 2), ax = x - x0, likewise y; the value
+ * (1 - ay) ((1 - ax) p00 + ax p01) + ay ((1 - ax) p10 + ax p11) in double precision, rounded half-up.  One upload, one launch, one
+ * download and one synchronisation per call. */
+int vc_undistort_images(vc_undistorter* u, int n, const unsigned char* src, int src_pitch, long long src_stride, unsigned char* dst, int dst_pitch,
+                        long long dst_stride);
+/* the same on DEVICE pointers, enqueued on the handle's stream (vc_undistort_stream, a hipStream_t) without synchronisation */
+int vc_undistort_images_device(vc_undistorter* u, int n, const unsigned char* d_src, int src_pitch, long long src_stride, unsigned char* d_dst,
+                               int dst_pitch, long long dst_stride);
+void* vc_undistort_stream(vc_undistorter* u);
+/* n distorted source pixels (x, y) -> pixels of the destination camera: the inverse the lookup table avoids.  Newton on the model's radial
+ * profile r_d = f(r_u) (in theta for kb4) from r_u = r_d, analytic slope, at most 40 steps, stop at |f - r_d| <= 1e-14 (1 + r_d); then R_ds and
+ * the pinhole projection.  valid (nullable) = 0 and a NaN pair: the iteration does not converge, leaves the positive range or meets a
+ * non-positive slope (the pixel is beyond the model's image), the result is not finite, or the rotated ray has z <= 0. */
+int vc_undistort_points(vc_undistorter* u, int n, const double* src_px /* n x 2 */, double* dst_px /* n x 2 */, unsigned char* valid /* n */);
+/* the lookup table: map = dst_h x dst_w x 2 floats (x, y in the source image; a NaN pair where there is no source pixel), valid = dst_h x
+ * dst_w bytes; either may be NULL */
+int vc_undistort_get_map(vc_undistorter* u, float* map, unsigned char* valid);
+int vc_undistort_get_linear(vc_undistorter* u, double dst_linear[4], int dst_size[2]);
+/* HIP events on the handle's stream, `reps` launches each, like vc_time_report_sweeps: out_ms[0] the map build, [1] the remap of n_images
+ * device-resident images, [2] 65536 points (a lattice over the source image). */
+int vc_time_undistort(vc_undistorter* u, int n_images, int reps, double out_ms[3]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -217,4 +217,42 @@ class ViCalibrator {
   vc_calibrator* h_ = nullptr;
 };
 
+// Using a calibration (vc_undistort*): a source camera's images and pixels mapped into a pinhole destination camera on the device.
+struct LinearCamera { std::array<double, 4> fu_fv_u0_v0{{0, 0, 0, 0}}; int width = 0, height = 0; };
+class Undistorter {
+ public:
+  // R_ds: row-major 3 x 3, source-camera rays -> destination-camera rays; nullptr = identity
+  Undistorter(const CameraAndPose& src, const LinearCamera& dst, const double* R_ds = nullptr, int fill = 0, int device = 0) {
+    vc_checked(vc_undistorter_create(device, src.model, src.params.data(), (int)src.params.size(), src.width, src.height, dst.fu_fv_u0_v0.data(), dst.width,
+                                     dst.height, R_ds, fill, &u_), "Undistorter");
+  }
+  Undistorter(ViCalibrator& cal, int camera, const LinearCamera& dst, const double* R_ds = nullptr, int fill = 0) {
+    vc_checked(vc_undistorter_create_for_camera(cal.handle(), camera, dst.fu_fv_u0_v0.data(), dst.width, dst.height, R_ds, fill, &u_), "Undistorter");
+  }
+  ~Undistorter() { vc_undistorter_destroy(u_); }
+  Undistorter(const Undistorter&) = delete;
+  Undistorter& operator=(const Undistorter&) = delete;
+  // destination intrinsics for identity rotation: alpha = 0 every destination pixel has a source pixel, alpha = 1 every source pixel is kept
+  static LinearCamera FitLinear(const CameraAndPose& src, int dst_width, int dst_height, double alpha = 0.0) {
+    LinearCamera d; d.width = dst_width; d.height = dst_height;
+    vc_checked(vc_undistort_fit_linear(src.model, src.params.data(), (int)src.params.size(), src.width, src.height, dst_width, dst_height, alpha, d.fu_fv_u0_v0.data()), "FitLinear");
+    return d;
+  }
+  LinearCamera Linear() { LinearCamera d; int s[2] = {0, 0}; vc_checked(vc_undistort_get_linear(u_, d.fu_fv_u0_v0.data(), s), "Linear"); d.width = s[0]; d.height = s[1]; return d; }
+  void Images(int n, const unsigned char* src, int src_pitch, long long src_stride, unsigned char* dst, int dst_pitch, long long dst_stride) {
+    vc_checked(vc_undistort_images(u_, n, src, src_pitch, src_stride, dst, dst_pitch, dst_stride), "Images");
+  }
+  void ImagesDevice(int n, const unsigned char* d_src, int src_pitch, long long src_stride, unsigned char* d_dst, int dst_pitch, long long dst_stride) {
+    vc_checked(vc_undistort_images_device(u_, n, d_src, src_pitch, src_stride, d_dst, dst_pitch, dst_stride), "ImagesDevice");
+  }
+  void* Stream() { return vc_undistort_stream(u_); }      // hipStream_t
+  void Points(int n, const double* src_px, double* dst_px, unsigned char* valid = nullptr) { vc_checked(vc_undistort_points(u_, n, src_px, dst_px, valid), "Points"); }
+  void Map(float* map, unsigned char* valid = nullptr) { vc_checked(vc_undistort_get_map(u_, map, valid), "Map"); }
+  std::array<double, 3> Time(int n_images = 64, int reps = 20) { std::array<double, 3> ms{{0, 0, 0}}; vc_checked(vc_time_undistort(u_, n_images, reps, ms.data()), "Time"); return ms; }
+  vc_undistorter* handle() { return u_; }
+
+ private:
+  vc_undistorter* u_ = nullptr;
+};
+
 }  // namespace visual_inertial_calibration

@@ -315,6 +315,14 @@ int vc_get_camera(vc_calibrator* h, int c, double* params, int* nparams, double 
   if (T_ck) std::memcpy(T_ck, h->cams[c].T_ck, 56);
   return VC_OK;
 }
+// an undistorter (vc_undistort.hip) for camera c as vc_get_camera returns it, on the calibrator's device
+int vc_undistorter_create_for_camera(vc_calibrator* h, int c, const double dst_linear[4], int dst_w, int dst_h, const double R_ds[9], int fill,
+                                     vc_undistorter** out) {
+  if (!h || c < 0 || c >= (int)h->cams.size()) return VC_ERR_BAD_ARG;
+  HostCam cm;
+  { std::lock_guard<std::mutex> lk(h->result_mutex); cm = h->cams[c]; }
+  return vc_undistorter_create(h->device, cm.model, cm.K, cm.nk, cm.width, cm.height, dst_linear, dst_w, dst_h, R_ds, fill, out);
+}
 int vc_get_frame(vc_calibrator* h, int f, double T_wk[7], double v_w[3], double* time) {
   if (!h || f < 0 || f >= (int)h->frames.size()) return VC_ERR_BAD_ARG;
   std::lock_guard<std::mutex> lk(h->result_mutex);

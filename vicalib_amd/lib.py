@@ -36,6 +36,8 @@ SYMBOLS = [
     "vc_holdout_clear", "vc_holdout_add_tiles", "vc_holdout_compute", "vc_holdout_num_frames", "vc_holdout_num_views", "vc_holdout_num_corners", "vc_holdout_frames", "vc_holdout_views",
     "vc_holdout_corners", "vc_holdout_camera_rmse", "vc_time_holdout",
     "vc_detector_create", "vc_detector_destroy", "vc_detector_set_params", "vc_detector_find", "vc_detector_find_conics",
+    "vc_undistorter_create", "vc_undistorter_create_for_camera", "vc_undistorter_destroy", "vc_undistort_fit_linear", "vc_undistort_images",
+    "vc_undistort_images_device", "vc_undistort_stream", "vc_undistort_points", "vc_undistort_get_map", "vc_undistort_get_linear", "vc_time_undistort",
 ]
 
 
@@ -96,12 +98,13 @@ def load():
         L.vc_mean_squared_error.restype = C.c_double
         L.vc_get_num_iterations.restype = C.c_uint
         L.vc_get_stream.restype = C.c_void_p
+        L.vc_undistort_stream.restype = C.c_void_p
         L.vc_num_observations.restype = C.c_longlong
         L.vc_report_num_corners.restype = C.c_longlong
         L.vc_holdout_num_corners.restype = C.c_longlong
         L.vc_allreduce_calls.restype = C.c_longlong
         L.vc_last_error.restype = C.c_char_p
-        for name in ("vc_destroy", "vc_detector_destroy", "vc_shard_comm_destroy"):
+        for name in ("vc_destroy", "vc_detector_destroy", "vc_shard_comm_destroy", "vc_undistorter_destroy"):
             getattr(L, name).restype = None
         _lib = L
     return _lib
@@ -572,3 +575,161 @@ class ConicDetector:
                                               box.ctypes.data_as(C.c_void_p), int(max_conics), C.byref(n)), "detector_find_conics")
         k = min(n.value, max_conics)
         return out[:k], con[:k].reshape(-1, 3, 3), box[:k]
+
+
+_hip = None
+
+
+def hip_runtime():
+    """The HIP runtime the library itself is linked against, for the few runtime calls tests and tools make beside the C ABI (device buffers,
+    a reference copy): the very shared object that is mapped into this process, with argument types declared."""
+    global _hip
+    if _hip is None:
+        load()
+        with open("/proc/self/maps") as f:
+            path = next((line.split()[-1] for line in f if "libamdhip64" in line), None)
+        if path is None:
+            raise VicalibError("the HIP runtime is not mapped into this process")
+        H = C.CDLL(path)
+        vp, sz = C.c_void_p, C.c_size_t
+        H.hipMalloc.argtypes = [C.POINTER(vp), sz]
+        H.hipFree.argtypes = [vp]
+        H.hipMemcpy.argtypes = [vp, vp, sz, C.c_int]
+        H.hipMemcpyAsync.argtypes = [vp, vp, sz, C.c_int, vp]
+        H.hipMemset.argtypes = [vp, C.c_int, sz]
+        H.hipDeviceSynchronize.argtypes = []
+        H.hipEventCreate.argtypes = [C.POINTER(vp)]
+        H.hipEventDestroy.argtypes = [vp]
+        H.hipEventRecord.argtypes = [vp, vp]
+        H.hipEventSynchronize.argtypes = [vp]
+        H.hipEventElapsedTime.argtypes = [C.POINTER(C.c_float), vp, vp]
+        _hip = H
+    return _hip
+
+
+class DeviceBuffer:
+    """A device allocation that holds a numpy array's bytes (hipMalloc + hipMemcpy): what a caller of the *_device entry points has."""
+
+    def __init__(self, arr):
+        arr = np.ascontiguousarray(arr)
+        self.shape, self.dtype, self.nbytes, self.ptr = arr.shape, arr.dtype, arr.nbytes, C.c_void_p()
+        H = hip_runtime()
+        if H.hipMalloc(C.byref(self.ptr), arr.nbytes) != 0 or H.hipMemcpy(self.ptr, arr.ctypes.data, arr.nbytes, 1) != 0:      # 1 = hipMemcpyHostToDevice
+            raise VicalibError("DeviceBuffer: hipMalloc / hipMemcpy failed")
+
+    def numpy(self):
+        """the buffer's content, after a device-wide synchronisation"""
+        out = np.zeros(self.shape, dtype=self.dtype)
+        H = hip_runtime()
+        if H.hipDeviceSynchronize() != 0 or H.hipMemcpy(out.ctypes.data, self.ptr, self.nbytes, 2) != 0:      # 2 = hipMemcpyDeviceToHost
+            raise VicalibError("DeviceBuffer: hipMemcpy failed")
+        return out
+
+    def free(self):
+        if self.ptr:
+            hip_runtime().hipFree(self.ptr)
+            self.ptr = C.c_void_p()
+
+
+def _model_id(model):
+    from .synth import MODEL_IDS
+    return MODEL_IDS[model] if isinstance(model, str) else int(model)
+
+
+class Undistorter:
+    """Using a calibration (include/vicalib_amd.h: vc_undistort*): images and pixels of a calibrated source camera mapped into an ideal
+    pinhole destination camera dst_linear = [fu, fv, u0, v0] of dst_size = (w, h), rotated against the source by R_ds (3 x 3, source rays ->
+    destination rays; None = identity).  The lookup table is built once, on the GPU.  map() -> (map [h, w, 2] float32, valid [h, w] bool);
+    images(arr) -> undistorted uint8 images; points(px) -> (destination pixels [n, 2], valid [n] bool)."""
+
+    def __init__(self, model, params, src_size, dst_linear, dst_size=None, R_ds=None, fill=0, device=0, _camera_of=None):
+        self.L = load()
+        self.h = C.c_void_p()
+        dst_size = tuple(src_size if dst_size is None else dst_size)
+        dl = np.ascontiguousarray(dst_linear, dtype=np.float64)
+        assert dl.shape == (4,)
+        R = None if R_ds is None else np.ascontiguousarray(R_ds, dtype=np.float64).reshape(3, 3)
+        Rp = None if R is None else _d(R)
+        if _camera_of is not None:
+            cal, cam = _camera_of
+            _check(self.L.vc_undistorter_create_for_camera(cal.h, int(cam), _d(dl), int(dst_size[0]), int(dst_size[1]), Rp, int(fill), C.byref(self.h)),
+                   "undistorter_create_for_camera")
+        else:
+            params = np.ascontiguousarray(params, dtype=np.float64)
+            _check(self.L.vc_undistorter_create(int(device), _model_id(model), _d(params), len(params), int(src_size[0]), int(src_size[1]), _d(dl),
+                                                int(dst_size[0]), int(dst_size[1]), Rp, int(fill), C.byref(self.h)), "undistorter_create")
+        self.src_size = (int(src_size[0]), int(src_size[1]))
+        self.dst_size = (int(dst_size[0]), int(dst_size[1]))
+
+    @classmethod
+    def for_camera(cls, cal, camera, src_size, dst_linear, dst_size=None, R_ds=None, fill=0):
+        """For camera `camera` of a ViCalibrator as GetCamera returns it (src_size: the size it was added with)."""
+        return cls(None, None, src_size, dst_linear, dst_size, R_ds, fill, _camera_of=(cal, camera))
+
+    @staticmethod
+    def fit_linear(model, params, src_size, dst_size=None, alpha=0.0):
+        """Destination intrinsics [fu, fv, u0, v0] for identity rotation (vc_undistort_fit_linear; host code, needs no GPU): alpha = 0 every
+        destination pixel has a source pixel, alpha = 1 every source pixel is kept."""
+        dst_size = src_size if dst_size is None else dst_size
+        params = np.ascontiguousarray(params, dtype=np.float64)
+        out = np.zeros(4)
+        _check(load().vc_undistort_fit_linear(_model_id(model), _d(params), len(params), int(src_size[0]), int(src_size[1]), int(dst_size[0]), int(dst_size[1]),
+                                              C.c_double(alpha), _d(out)), "undistort_fit_linear")
+        return out
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.vc_undistorter_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+    def linear(self):
+        dl = np.zeros(4); sz = (C.c_int * 2)()
+        _check(self.L.vc_undistort_get_linear(self.h, _d(dl), sz), "undistort_get_linear")
+        return dl, (sz[0], sz[1])
+
+    def map(self):
+        w, h = self.dst_size
+        m = np.zeros((h, w, 2), dtype=np.float32); v = np.zeros((h, w), dtype=np.uint8)
+        _check(self.L.vc_undistort_get_map(self.h, m.ctypes.data_as(C.c_void_p), v.ctypes.data_as(C.c_void_p)), "undistort_get_map")
+        return m, v.astype(bool)
+
+    def images(self, arr, out=None):
+        """arr: uint8 [h, w] or [n, h, w]; rows and images may be strided (pixels of a row contiguous).  out: likewise at the destination size;
+        only its pixels are written."""
+        arr = np.asarray(arr)
+        single = arr.ndim == 2
+        a = arr[None] if single else arr
+        assert a.dtype == np.uint8 and a.ndim == 3 and a.shape[1:] == (self.src_size[1], self.src_size[0]), a.shape
+        if a.strides[2] != 1 or a.strides[1] < a.shape[2] or (len(a) > 1 and a.strides[0] < a.strides[1] * a.shape[1]):
+            a = np.ascontiguousarray(a)
+        n = len(a)
+        if out is None:
+            o = np.zeros((n, self.dst_size[1], self.dst_size[0]), dtype=np.uint8)
+        else:
+            o = out[None] if out.ndim == 2 else out
+            assert o.dtype == np.uint8 and o.shape == (n, self.dst_size[1], self.dst_size[0]) and o.strides[2] == 1 and o.flags.writeable
+        _check(self.L.vc_undistort_images(self.h, n, C.c_void_p(a.ctypes.data), int(a.strides[1]), C.c_longlong(a.strides[0]), C.c_void_p(o.ctypes.data),
+                                          int(o.strides[1]), C.c_longlong(o.strides[0])), "undistort_images")
+        return o[0] if single else o
+
+    def images_device(self, n, d_src, src_pitch, src_stride, d_dst, dst_pitch, dst_stride):
+        """Device pointers (integers), enqueued on stream() without synchronisation (vc_undistort_images_device)."""
+        _check(self.L.vc_undistort_images_device(self.h, int(n), C.c_void_p(int(d_src)), int(src_pitch), C.c_longlong(src_stride), C.c_void_p(int(d_dst)),
+                                                 int(dst_pitch), C.c_longlong(dst_stride)), "undistort_images_device")
+
+    def stream(self): return self.L.vc_undistort_stream(self.h)
+
+    def points(self, px):
+        px = np.ascontiguousarray(px, dtype=np.float64).reshape(-1, 2)
+        out = np.zeros_like(px); valid = np.zeros(len(px), dtype=np.uint8)
+        _check(self.L.vc_undistort_points(self.h, len(px), _d(px), out.ctypes.data_as(C.c_void_p), valid.ctypes.data_as(C.c_void_p)), "undistort_points")
+        return out, valid.astype(bool)
+
+    def time(self, n_images=64, reps=20):
+        """Average ms per launch: map build, remap of n_images device-resident images, 65536 points (vc_time_undistort)."""
+        out = np.zeros(3)
+        _check(self.L.vc_time_undistort(self.h, int(n_images), int(reps), _d(out)), "time_undistort")
+        return dict(map=out[0], remap=out[1], points=out[2])
