@@ -131,6 +131,11 @@ static void DefineFlags() {
   Define("undistort_dir", "string", "", "(image input) Directory for the input images undistorted with the result, cam<i>_<name>.pgm, and cameras.xml with the "
          "pinhole cameras they belong to (empty: none).  Its parent must exist; if the images cannot be written the tool says so and exits with status 1.");
   Define("undistort_alpha", "double", "0", "Destination intrinsics of -undistort_dir: 0 = every pixel of an undistorted image is valid ... 1 = every source pixel is kept.");
+  // stereo rectification with the result and its consistency check (vc_rectif*): off unless asked for
+  Define("rectify_dir", "string", "", "Directory for the stereo rectification of two cameras with the result: cameras.xml (the two rectified pinhole cameras), "
+         "stereo_check.csv (row misalignment and metric consistency of the calibration's own matched detections, per frame) and, with image input, the rectified images cam<i>_<name>.pgm.");
+  Define("rectify_cams", "string", "0,1", "The two cameras -rectify_dir rectifies: a,b.");
+  Define("rectify_alpha", "double", "0", "Destination intrinsics of -rectify_dir: 0 = every pixel of both rectified images is valid ... 1 = every source pixel of both cameras is kept.");
 }
 
 static int Usage(int code) {
@@ -476,6 +481,135 @@ static bool UndistortInputs(vic::ViCalibrator& cal, const std::vector<std::strin
   return true;
 }
 
+// -rectify_cams a,b: two different cameras of the n_cam channels
+static bool ParseRectifyCams(const std::string& s, size_t n_cam, int* a, int* b) {
+  char tail = 0;
+  if (std::sscanf(s.c_str(), "%d,%d%c", a, b, &tail) != 2) return false;
+  return *a >= 0 && *b >= 0 && *a != *b && (size_t)*a < n_cam && (size_t)*b < n_cam;
+}
+static bool WritePgm(const std::string& path, int w, int h, const unsigned char* px, std::string* err) {
+  FILE* f = std::fopen(path.c_str(), "wb");
+  if (!f) { *err = "cannot write " + path; return false; }
+  std::fprintf(f, "P5\n%d %d\n255\n", w, h);
+  std::fwrite(px, 1, (size_t)w * h, f);
+  std::fclose(f);
+  return true;
+}
+static std::string BaseName(std::string name) {
+  const size_t slash = name.find_last_of('/');
+  if (slash != std::string::npos) name = name.substr(slash + 1);
+  const size_t dot = name.find_last_of('.');
+  if (dot != std::string::npos && dot > 0) name = name.substr(0, dot);
+  return name;
+}
+
+// -rectify_dir: cameras a and b of the result rectified (vc_rectifier: the rotations of vc_stereo_rectify_rotations, one pinhole camera of
+// a's size for both from vc_stereo_fit_linear at -rectify_alpha).  dir/cameras.xml holds the two rectified cameras (T_ck_rect: they differ by
+// a translation along x), dir/stereo_check.csv the stereo consistency check over the corners both cameras detected in the frames the
+// calibration used, and with image input the i-th sorted image of a and of b are rectified as a pair, in batches of at most 64.
+static bool RectifyOutputs(vic::ViCalibrator& cal, const std::vector<Channel>& channels, const std::vector<long>& frame_ids, int grid_n,
+                           const std::vector<std::string>& cam_globs, bool from_images, const std::vector<vic::CameraAndPose>& input_cameras, bool calibrate_imu,
+                           int device, const std::string& dir, int a, int b, double alpha, std::string* err) {
+  struct stat st;
+  if (mkdir(dir.c_str(), 0777) != 0 && !(stat(dir.c_str(), &st) == 0 && S_ISDIR(st.st_mode))) {      // (one level: parents must exist)
+    *err = "cannot create the directory " + dir;
+    return false;
+  }
+  const int cams[2] = {a, b};
+  vic::LinearCamera dst;                                 // intrinsics left zero: fitted at alpha
+  dst.width = input_cameras[a].width; dst.height = input_cameras[a].height;
+  vic::Rectifier rect(cal, a, b, dst, alpha);
+  dst = rect.Linear();
+  const double baseline = rect.Baseline();
+  // ---- cameras.xml
+  {
+    vic::ViCalibrator rig(device);
+    rig.SetCalibrateImu(calibrate_imu);                  // (the XML writer's axis convention follows it)
+    vic::Se3 T[2];
+    rect.RectifiedPoses(&T[0], &T[1]);
+    for (int s = 0; s < 2; ++s) {
+      vic::CameraAndPose lin;
+      lin.model = VC_MODEL_LINEAR; lin.params.assign(dst.fu_fv_u0_v0.begin(), dst.fu_fv_u0_v0.end()); lin.width = dst.width; lin.height = dst.height; lin.T_ck = T[s];
+      rig.AddCamera(lin);
+    }
+    rig.WriteCameraModels(dir + "/cameras.xml");
+  }
+  // ---- stereo_check.csv: the two cameras' detections of the calibration's frames in the layout of vc_add_observation_tiles, matched by vc_match_tiles
+  std::map<long, int> frame_index;
+  for (size_t k = 0; k < frame_ids.size(); ++k) frame_index[frame_ids[k]] = (int)k;
+  std::vector<int> tile_frame, tile_cam, point_id;
+  std::vector<long long> tile_off(1, 0);
+  std::vector<const Detection*> dets;
+  for (int s = 0; s < 2; ++s) {
+    std::map<int, std::vector<const Detection*>> per_frame;
+    for (const Detection& d : channels[(size_t)cams[s]].det) {
+      auto it = frame_index.find(d.frame);
+      if (it == frame_index.end() || d.dot >= grid_n) continue;
+      per_frame[it->second].push_back(&d);
+    }
+    for (const auto& kv : per_frame) {
+      for (const Detection* d : kv.second) { point_id.push_back(d->dot); dets.push_back(d); }
+      tile_frame.push_back(kv.first); tile_cam.push_back(s); tile_off.push_back((long long)dets.size());
+    }
+  }
+  const vic::TileMatches m = vic::Rectifier::MatchTiles((int)tile_frame.size(), tile_frame.data(), tile_cam.data(), tile_off.data(), point_id.data(), 0, 1);
+  const size_t n = m.pos_a.size(), nf = m.frame.size();
+  std::vector<double> px_a(2 * n + 2), px_b(2 * n + 2), target(3 * n + 3);
+  for (size_t k = 0; k < n; ++k) {
+    const Detection* da = dets[(size_t)m.pos_a[k]]; const Detection* db = dets[(size_t)m.pos_b[k]];
+    px_a[2 * k] = da->u; px_a[2 * k + 1] = da->v; px_b[2 * k] = db->u; px_b[2 * k + 1] = db->v;
+    target[3 * k] = da->X; target[3 * k + 1] = da->Y; target[3 * k + 2] = da->Z;
+  }
+  const vic::StereoCheck chk = rect.Check(m.frame_off, px_a.data(), px_b.data(), target.data());
+  FILE* f = std::fopen((dir + "/stereo_check.csv").c_str(), "w");
+  if (!f) { *err = "cannot write " + dir + "/stereo_check.csv"; return false; }
+  std::fprintf(f, "frame,pairs,invalid,mean_dv,rms_dv,max_abs_dv,mean_z_m,rigid_rms_m\n");
+  double sum2 = 0.0, worst = 0.0; long long valid = 0;
+  std::vector<double> rms;
+  for (size_t k = 0; k < nf; ++k) {
+    const int cnt = chk.count[k];
+    std::fprintf(f, "%ld,%d,%d,%.10g,%.10g,%.10g,%.10g,%.10g\n", frame_ids[(size_t)m.frame[k]], cnt + chk.n_invalid[k], chk.n_invalid[k], cnt > 0 ? chk.sum_dv[k] / cnt : 0.0,
+                 cnt > 0 ? std::sqrt(chk.sum_dv2[k] / cnt) : 0.0, chk.max_abs_dv[k], chk.mean_z[k], chk.rigid_rms[k]);
+    sum2 += chk.sum_dv2[k]; valid += cnt; worst = std::max(worst, chk.max_abs_dv[k]);
+    if (chk.rigid_rms[k] == chk.rigid_rms[k]) rms.push_back(chk.rigid_rms[k]);
+  }
+  std::fclose(f);
+  std::sort(rms.begin(), rms.end());
+  std::fprintf(stderr, "I cameras %d,%d rectified into %s: baseline %.6g m, %zu frames with %lld matched corners, rms dv %.4g px, worst |dv| %.4g px, median rigid_rms_m %.4g\n",
+               a, b, dir.c_str(), baseline, nf, valid, valid > 0 ? std::sqrt(sum2 / (double)valid) : 0.0, worst, rms.empty() ? 0.0 : rms[rms.size() / 2]);
+  if (!from_images) return true;
+  // ---- the rectified images
+  std::vector<std::string> files[2];
+  for (int s = 0; s < 2; ++s)
+    if (!GlobSorted(cam_globs[(size_t)cams[s]], &files[s])) { *err = "no images match " + cam_globs[(size_t)cams[s]]; return false; }
+  const size_t n_img = std::min(files[0].size(), files[1].size());
+  if (files[0].size() != files[1].size()) std::fprintf(stderr, "W cameras %d and %d have %zu and %zu images: the first %zu are rectified as pairs\n", a, b, files[0].size(), files[1].size(), n_img);
+  const int kBatch = 64;
+  const int sw[2] = {input_cameras[a].width, input_cameras[b].width}, sh[2] = {input_cameras[a].height, input_cameras[b].height};
+  const size_t snp[2] = {(size_t)sw[0] * sh[0], (size_t)sw[1] * sh[1]}, dnp = (size_t)dst.width * dst.height;
+  std::vector<unsigned char> in[2], out[2], px;
+  for (size_t first = 0; first < n_img; first += kBatch) {
+    const size_t nb = std::min((size_t)kBatch, n_img - first);
+    for (int s = 0; s < 2; ++s) {
+      in[s].resize(nb * snp[s]); out[s].resize(nb * dnp);
+      for (size_t k = 0; k < nb; ++k) {
+        int iw = 0, ih = 0;
+        if (!ReadPgm(files[s][first + k], &iw, &ih, &px, err)) return false;
+        if (iw != sw[s] || ih != sh[s]) { *err = files[s][first + k] + ": image size differs from the camera's"; return false; }
+        std::memcpy(in[s].data() + k * snp[s], px.data(), snp[s]);
+      }
+    }
+    rect.Pairs((int)nb, in[0].data(), sw[0], (long long)snp[0], in[1].data(), sw[1], (long long)snp[1], out[0].data(), dst.width, (long long)dnp, out[1].data(), dst.width,
+               (long long)dnp);
+    for (int s = 0; s < 2; ++s)
+      for (size_t k = 0; k < nb; ++k)
+        if (!WritePgm(dir + "/cam" + std::to_string(cams[s]) + "_" + BaseName(files[s][first + k]) + ".pgm", dst.width, dst.height, out[s].data() + k * dnp, err)) return false;
+  }
+  std::fprintf(stderr, "I %zu image pairs rectified into %s (pinhole fu %.6g fv %.6g u0 %.6g v0 %.6g)\n", n_img, dir.c_str(), dst.fu_fv_u0_v0[0], dst.fu_fv_u0_v0[1],
+               dst.fu_fv_u0_v0[2], dst.fu_fv_u0_v0[3]);
+  return true;
+}
+
 int main(int argc, char** argv) {
   DefineFlags();
   std::string err;
@@ -544,6 +678,15 @@ int main(int argc, char** argv) {
   for (size_t c = 0; c < cam_files.size(); ++c)
     if (!ReadDetections(cam_files[c], &channels[c], &err)) { std::fprintf(stderr, "F %s\n", err.c_str()); return 1; }
   const size_t n_cam = channels.size();
+  int rectify_a = 0, rectify_b = 1;
+  if (!FlagString("rectify_dir").empty()) {
+    if (n_cam < 2) { std::fprintf(stderr, "E -rectify_dir needs two cameras (-cam has %zu)\n", n_cam); return 1; }
+    if (!ParseRectifyCams(FlagString("rectify_cams"), n_cam, &rectify_a, &rectify_b)) {
+      std::fprintf(stderr, "E illegal value '%s' specified for flag 'rectify_cams': expected a,b, two different cameras below %zu\n", FlagString("rectify_cams").c_str(), n_cam);
+      return 1;
+    }
+    if (!(FlagDouble("rectify_alpha") >= 0.0 && FlagDouble("rectify_alpha") <= 1.0)) { std::fprintf(stderr, "E illegal value for flag 'rectify_alpha': expected 0 ... 1\n"); return 1; }
+  }
   ImuData imu;
   const bool have_imu = !FlagString("imu").empty();
   if (have_imu && !ReadImu(StripScheme(FlagString("imu")), FlagBool("use_system_time"), &imu, &err)) { std::fprintf(stderr, "F %s\n", err.c_str()); return 1; }
@@ -914,6 +1057,14 @@ int main(int argc, char** argv) {
       } catch (const std::exception& e) { std::fprintf(stderr, "E undistortion failed: %s\n", e.what()); undistort_failed = true; }
     }
   }
+  bool rectify_failed = false;
+  if (!FlagString("rectify_dir").empty()) {
+    try {
+      if (!RectifyOutputs(cal, channels, frame_ids, grid_w * grid_h, cam_files, from_images, input_cameras, calibrate_imu, (int)FlagInt("device"), FlagString("rectify_dir"),
+                          rectify_a, rectify_b, FlagDouble("rectify_alpha"), &err))
+        { std::fprintf(stderr, "E rectification failed: %s\n", err.c_str()); rectify_failed = true; }
+    } catch (const std::exception& e) { std::fprintf(stderr, "E rectification failed: %s\n", e.what()); rectify_failed = true; }
+  }
   if (FlagBool("print_poses")) {
     if (FILE* f = std::fopen("poses.txt", "w")) {
       for (size_t i = 0; i < all_frames.size(); ++i) { double c[6]; T2Cart(all_frames[i].t_wp_.data(), c); std::fprintf(f, "%f\t%f\t%f\t%f\t%f\t%f\n", c[0], c[1], c[2], c[3], c[4], c[5]); }
@@ -949,5 +1100,6 @@ int main(int argc, char** argv) {
   }
   std::printf("calibration %s -> %s\n", success ? "succeeded" : "FAILED", FlagString("output").c_str());
   if (undistort_failed) std::fprintf(stderr, "E -undistort_dir: the undistorted images are incomplete (exit status %d)\n", success ? 1 : 2);
-  return success ? (undistort_failed ? 1 : 0) : 2;
+  if (rectify_failed) std::fprintf(stderr, "E -rectify_dir: the rectification's files are incomplete (exit status %d)\n", success ? 1 : 2);
+  return success ? ((undistort_failed || rectify_failed) ? 1 : 0) : 2;
 }

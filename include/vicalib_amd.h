@@ -412,6 +412,73 @@ int vc_undistort_get_linear(vc_undistorter* u, double dst_linear[4], int dst_siz
  * device-resident images, [2] 65536 points (a lattice over the source image). */
 int vc_time_undistort(vc_undistorter* u, int n_images, int reps, double out_ms[3]);
 
+/* ---- using the calibration of a PAIR: stereo rectification and the stereo consistency check ---------------------------------------
+ * What the owner of a calibrated rig does with cameras.xml first: rotate both cameras into a common frame in which a point lies on the same
+ * image row of both, with one pinhole camera dst_linear = [fu fv u0 v0] of dst_w x dst_h pixels for both sides, and see whether rows line
+ * up and depth comes out in metres.  With p_c = R_ck p_k + t_ck, for cameras a and b: R = R_bk R_ak^T, t = t_bk - R t_ak (p_b = R p_a + t),
+ * centre of b in a's frame c = -R^T t.
+ * Rotations (row-major, source-camera rays -> rectified rays, what vc_undistorter_create takes as R_ds): e1 = c / |c|, negated if
+ * e1 . xm < 0 with xm = x + R^T x the summed x axes (b to the left of a: the images stay upright); e2 = normalize(zm x e1) with
+ * zm = z + R^T z the summed optical axes; e3 = e1 x e2; R_ds_a has the rows e1 e2 e3, R_ds_b = R_ds_a R^T.  The signed baseline is e1 . c
+ * (negative when the sign flipped), and R_ds_b p_b = R_ds_a p_a - (baseline, 0, 0): same row, same depth Z, u_a - u_b = fu baseline / Z.
+ * VC_ERR_NUMERIC: |c| < 1e-9.  VC_ERR_UNSUPPORTED: the baseline is closer to the images' vertical than to their horizontal
+ * (|e1 . ym| > |e1 . xm|, ym = y + R^T y): column rectification is not provided.  VC_ERR_BAD_ARG: a pose that is not finite or whose
+ * quaternion is not of unit length to 1e-6.  Host code, no device.  Any output pointer may be NULL. */
+int vc_stereo_rectify_rotations(const double T_ck_a[7], const double T_ck_b[7], double R_ds_a[9], double R_ds_b[9], double* baseline);
+/* One destination camera for both sides (host code, no device): the procedure of vc_undistort_fit_linear with each side's border samples
+ * rotated by its R_ds (NULL = identity) before they enter the pinhole plane.  alpha = 1: the union of the two sides' bounding boxes fills
+ * the destination image; alpha = 0: the intersection of the two inner rectangles, drawn in until every pixel of the destination border has
+ * a source pixel on BOTH sides; in between the two rectangles are interpolated linearly.  VC_ERR_NUMERIC: an empty intersection, or fewer
+ * than 8 samples of a side with a pinhole image. */
+int vc_stereo_fit_linear(int model_a, const double* params_a, int nparams_a, int w_a, int h_a, const double R_ds_a[9], int model_b, const double* params_b,
+                         int nparams_b, int w_b, int h_b, const double R_ds_b[9], int dst_w, int dst_h, double alpha, double dst_linear[4]);
+/* Matched corners of two cameras in the layout of vc_add_observation_tiles (host code): for every frame that has a group of cam_a and a
+ * group of cam_b, ordered by frame, the positions (indices into point_id / p_c) of the corners with equal point_id, ordered by point id;
+ * of a point id given twice in one view the first position counts.  A frame with both cameras and no common corner keeps its (empty) row.
+ * Two calls: with frame, frame_off, pos_a and pos_b NULL it only counts (*n_frames, *n_pairs); with arrays, *n_frames and *n_pairs hold
+ * their capacities on entry (frame: n_frames, nullable; frame_off: n_frames + 1; pos_a, pos_b: n_pairs) and the counts on return;
+ * VC_ERR_BAD_ARG if they do not fit. */
+int vc_match_tiles(int n_tiles, const int* tile_frame, const int* tile_cam, const long long* tile_off /* n_tiles + 1 */, const int* point_id, int cam_a,
+                   int cam_b, int* n_frames, long long* n_pairs, int* frame, long long* frame_off, long long* pos_a, long long* pos_b);
+/* A rectifier: the rotations above, dst_linear (NULL = vc_stereo_fit_linear at alpha; alpha is not read otherwise) and one undistorter per
+ * side, on `device`.  Single-threaded like an undistorter; no CPU fallback (VC_ERR_NO_DEVICE).  Argument errors are VC_ERR_BAD_ARG as in
+ * vc_undistorter_create; they, the rotations' and the fit's statuses come before the device is looked for. */
+typedef struct vc_rectifier vc_rectifier;
+int vc_rectifier_create(int device, int model_a, const double* params_a, int nparams_a, int w_a, int h_a, const double T_ck_a[7], int model_b,
+                        const double* params_b, int nparams_b, int w_b, int h_b, const double T_ck_b[7], const double dst_linear[4], int dst_w, int dst_h,
+                        double alpha, int fill, vc_rectifier** out);
+/* the same for cameras cam_a and cam_b of a calibrator as vc_get_camera returns them, on the calibrator's device */
+int vc_rectifier_create_for_cameras(vc_calibrator* h, int cam_a, int cam_b, const double dst_linear[4], int dst_w, int dst_h, double alpha, int fill,
+                                    vc_rectifier** out);
+void vc_rectifier_destroy(vc_rectifier* r);
+/* side 0 = a, 1 = b: that side's undistorter, BORROWED (never destroy it): its map, points, images and stream work as they do for any
+ * undistorter.  NULL for another side. */
+vc_undistorter* vc_rectifier_side(vc_rectifier* r, int side);
+/* any pointer may be NULL.  T_ck_rect = (R_ds R_ck, R_ds t_ck): the rectified cameras' poses, which differ by a translation along x. */
+int vc_rectifier_get(vc_rectifier* r, double R_ds_a[9], double R_ds_b[9], double dst_linear[4], int dst_size[2], double* baseline, double T_ck_rect_a[7],
+                     double T_ck_rect_b[7]);
+/* n image pairs, HOST buffers laid out as for vc_undistort_images: the same remap on the two sides' streams, both enqueued before either is
+ * waited for, one synchronisation of each. */
+int vc_rectify_pairs(vc_rectifier* r, int n, const unsigned char* src_a, int src_pitch_a, long long src_stride_a, const unsigned char* src_b, int src_pitch_b,
+                     long long src_stride_b, unsigned char* dst_a, int dst_pitch_a, long long dst_stride_a, unsigned char* dst_b, int dst_pitch_b,
+                     long long dst_stride_b);
+/* The stereo consistency check, one device sweep over matched corner pairs: frame f holds pairs [frame_off[f], frame_off[f + 1]) of px_a /
+ * px_b (n x 2 distorted pixels of the same target point in a and b; frame_off[0] = 0, at most 32768 pairs per frame) and of target (n x 3
+ * target points in metres, or NULL).  A pair: both pixels through vc_undistort_points' arithmetic of their side -> (ua, va), (ub, vb);
+ * dv = va - vb, d = ua - ub, Z = fu baseline / d, P = ((ua - u0) Z / fu, ((va + vb) / 2 - v0) Z / fv, Z) in the rectified frame of a.
+ * pairs_out (n x 6, nullable): dv, d, P, (va + vb) / 2.  flags (n, nullable): 1 = INVALID pair -- an inversion failed or d baseline <= 0 --,
+ * whose row is NaN and which enters no sum.  Per frame over its valid pairs (every array n_frames long and nullable): count, invalid,
+ * sum dv, sum dv^2, max |dv| and the pair that has it (index into px_a, the lowest on ties, -1 without a valid pair), mean Z, and
+ * rigid_rms: the RMS residual in metres of the best rigid fit (rotation + translation, NO scale: a wrong baseline shows) of the P onto
+ * their target points; NaN without target or with fewer than 3 valid pairs.  A frame of no pairs has a zero row (worst -1, rms NaN).
+ * Sums are formed in a fixed order: two runs, and a frame alone or among others, give the same bits.  n_frames = 0: VC_OK, no launch. */
+int vc_rectify_check(vc_rectifier* r, int n_frames, const long long* frame_off /* n_frames + 1 */, const double* px_a, const double* px_b, const double* target,
+                     double* pairs_out, unsigned char* flags, int* count, int* invalid, double* sum_dv, double* sum_dv2, double* max_abs_dv, long long* worst,
+                     double* mean_z, double* rigid_rms);
+/* HIP events on the rectifier's stream like vc_time_undistort: average ms of `reps` launches of the last vc_rectify_check's sweep on its
+ * device-resident data (VC_ERR_BAD_ARG before a check). */
+int vc_time_rectify_check(vc_rectifier* r, int reps, double* out_ms);
+
 #ifdef __cplusplus
 }
 #endif

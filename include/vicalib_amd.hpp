@@ -255,4 +255,78 @@ class Undistorter {
   vc_undistorter* u_ = nullptr;
 };
 
+// Using the calibration of a pair (vc_stereo_*, vc_rectif*): both cameras rotated into a common frame with one pinhole camera, image pairs
+// remapped through the two sides' undistorters, and the stereo consistency check over matched corner pairs.
+struct StereoCheck {                                   // vc_rectify_check: per pair, then per frame
+  std::vector<double> pairs;                           // n x 6: dv, d, P (3), mean row
+  std::vector<unsigned char> invalid;                  // n: 1 = the pair enters no sum
+  std::vector<int> count, n_invalid;
+  std::vector<double> sum_dv, sum_dv2, max_abs_dv, mean_z, rigid_rms;
+  std::vector<long long> worst;
+};
+struct TileMatches { std::vector<int> frame; std::vector<long long> frame_off, pos_a, pos_b; };
+class Rectifier {
+ public:
+  // dst.fu_fv_u0_v0 all zero: fitted at alpha (vc_stereo_fit_linear); dst.width / height are the destination size
+  Rectifier(const CameraAndPose& a, const CameraAndPose& b, const LinearCamera& dst, double alpha = 0.0, int fill = 0, int device = 0) {
+    vc_checked(vc_rectifier_create(device, a.model, a.params.data(), (int)a.params.size(), a.width, a.height, a.T_ck.data(), b.model, b.params.data(),
+                                   (int)b.params.size(), b.width, b.height, b.T_ck.data(), Given(dst), dst.width, dst.height, alpha, fill, &r_), "Rectifier");
+  }
+  Rectifier(ViCalibrator& cal, int cam_a, int cam_b, const LinearCamera& dst, double alpha = 0.0, int fill = 0) {
+    vc_checked(vc_rectifier_create_for_cameras(cal.handle(), cam_a, cam_b, Given(dst), dst.width, dst.height, alpha, fill, &r_), "Rectifier");
+  }
+  ~Rectifier() { vc_rectifier_destroy(r_); }
+  Rectifier(const Rectifier&) = delete;
+  Rectifier& operator=(const Rectifier&) = delete;
+  // host code, no device: R_ds_a, R_ds_b (row-major) and the signed baseline
+  static double Rotations(const Se3& T_ck_a, const Se3& T_ck_b, double R_ds_a[9], double R_ds_b[9]) {
+    double b = 0.0;
+    vc_checked(vc_stereo_rectify_rotations(T_ck_a.data(), T_ck_b.data(), R_ds_a, R_ds_b, &b), "Rotations");
+    return b;
+  }
+  static LinearCamera FitLinear(const CameraAndPose& a, const double R_ds_a[9], const CameraAndPose& b, const double R_ds_b[9], int dst_width, int dst_height,
+                                double alpha = 0.0) {
+    LinearCamera d; d.width = dst_width; d.height = dst_height;
+    vc_checked(vc_stereo_fit_linear(a.model, a.params.data(), (int)a.params.size(), a.width, a.height, R_ds_a, b.model, b.params.data(), (int)b.params.size(), b.width,
+                                    b.height, R_ds_b, dst_width, dst_height, alpha, d.fu_fv_u0_v0.data()), "FitLinear");
+    return d;
+  }
+  static TileMatches MatchTiles(int n_tiles, const int* tile_frame, const int* tile_cam, const long long* tile_off, const int* point_id, int cam_a, int cam_b) {
+    TileMatches m; int nf = 0; long long n = 0;
+    vc_checked(vc_match_tiles(n_tiles, tile_frame, tile_cam, tile_off, point_id, cam_a, cam_b, &nf, &n, nullptr, nullptr, nullptr, nullptr), "MatchTiles");
+    m.frame.resize((size_t)nf); m.frame_off.resize((size_t)nf + 1); m.pos_a.resize((size_t)n + 1); m.pos_b.resize((size_t)n + 1);
+    vc_checked(vc_match_tiles(n_tiles, tile_frame, tile_cam, tile_off, point_id, cam_a, cam_b, &nf, &n, m.frame.data(), m.frame_off.data(), m.pos_a.data(), m.pos_b.data()), "MatchTiles");
+    m.pos_a.resize((size_t)n); m.pos_b.resize((size_t)n);
+    return m;
+  }
+  vc_undistorter* Side(int side) { return vc_rectifier_side(r_, side); }      // borrowed
+  LinearCamera Linear() { LinearCamera d; int s[2] = {0, 0}; vc_checked(vc_rectifier_get(r_, nullptr, nullptr, d.fu_fv_u0_v0.data(), s, nullptr, nullptr, nullptr), "Linear"); d.width = s[0]; d.height = s[1]; return d; }
+  double Baseline() { double b = 0.0; vc_checked(vc_rectifier_get(r_, nullptr, nullptr, nullptr, nullptr, &b, nullptr, nullptr), "Baseline"); return b; }
+  void RectifiedPoses(Se3* T_ck_rect_a, Se3* T_ck_rect_b) { vc_checked(vc_rectifier_get(r_, nullptr, nullptr, nullptr, nullptr, nullptr, T_ck_rect_a->data(), T_ck_rect_b->data()), "RectifiedPoses"); }
+  void RotationMatrices(double R_ds_a[9], double R_ds_b[9]) { vc_checked(vc_rectifier_get(r_, R_ds_a, R_ds_b, nullptr, nullptr, nullptr, nullptr, nullptr), "RotationMatrices"); }
+  void Pairs(int n, const unsigned char* src_a, int src_pitch_a, long long src_stride_a, const unsigned char* src_b, int src_pitch_b, long long src_stride_b,
+             unsigned char* dst_a, int dst_pitch_a, long long dst_stride_a, unsigned char* dst_b, int dst_pitch_b, long long dst_stride_b) {
+    vc_checked(vc_rectify_pairs(r_, n, src_a, src_pitch_a, src_stride_a, src_b, src_pitch_b, src_stride_b, dst_a, dst_pitch_a, dst_stride_a, dst_b, dst_pitch_b,
+                                dst_stride_b), "Pairs");
+  }
+  // px_a, px_b: n x 2 distorted pixels, target: n x 3 or nullptr, n = frame_off.back()
+  StereoCheck Check(const std::vector<long long>& frame_off, const double* px_a, const double* px_b, const double* target) {
+    StereoCheck c;
+    const size_t nf = frame_off.empty() ? 0 : frame_off.size() - 1, n = nf ? (size_t)frame_off.back() : 0;
+    c.pairs.resize(6 * n + 1); c.invalid.resize(n + 1); c.count.resize(nf + 1); c.n_invalid.resize(nf + 1); c.worst.resize(nf + 1);
+    for (std::vector<double>* v : {&c.sum_dv, &c.sum_dv2, &c.max_abs_dv, &c.mean_z, &c.rigid_rms}) v->resize(nf + 1);
+    vc_checked(vc_rectify_check(r_, (int)nf, frame_off.data(), px_a, px_b, target, c.pairs.data(), c.invalid.data(), c.count.data(), c.n_invalid.data(), c.sum_dv.data(),
+                                c.sum_dv2.data(), c.max_abs_dv.data(), c.worst.data(), c.mean_z.data(), c.rigid_rms.data()), "Check");
+    c.pairs.resize(6 * n); c.invalid.resize(n); c.count.resize(nf); c.n_invalid.resize(nf); c.worst.resize(nf);
+    for (std::vector<double>* v : {&c.sum_dv, &c.sum_dv2, &c.max_abs_dv, &c.mean_z, &c.rigid_rms}) v->resize(nf);
+    return c;
+  }
+  double Time(int reps = 20) { double ms = 0.0; vc_checked(vc_time_rectify_check(r_, reps, &ms), "Time"); return ms; }
+  vc_rectifier* handle() { return r_; }
+
+ private:
+  static const double* Given(const LinearCamera& d) { return (d.fu_fv_u0_v0[0] == 0.0 && d.fu_fv_u0_v0[1] == 0.0) ? nullptr : d.fu_fv_u0_v0.data(); }
+  vc_rectifier* r_ = nullptr;
+};
+
 }  // namespace visual_inertial_calibration

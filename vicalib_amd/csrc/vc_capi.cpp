@@ -323,6 +323,14 @@ int vc_undistorter_create_for_camera(vc_calibrator* h, int c, const double dst_l
   { std::lock_guard<std::mutex> lk(h->result_mutex); cm = h->cams[c]; }
   return vc_undistorter_create(h->device, cm.model, cm.K, cm.nk, cm.width, cm.height, dst_linear, dst_w, dst_h, R_ds, fill, out);
 }
+// a rectifier (vc_rectify.hip) for cameras a and b as vc_get_camera returns them, on the calibrator's device
+int vc_rectifier_create_for_cameras(vc_calibrator* h, int a, int b, const double dst_linear[4], int dst_w, int dst_h, double alpha, int fill, vc_rectifier** out) {
+  if (!h || a < 0 || b < 0 || a == b || a >= (int)h->cams.size() || b >= (int)h->cams.size()) return VC_ERR_BAD_ARG;
+  HostCam ca, cb;
+  { std::lock_guard<std::mutex> lk(h->result_mutex); ca = h->cams[a]; cb = h->cams[b]; }
+  return vc_rectifier_create(h->device, ca.model, ca.K, ca.nk, ca.width, ca.height, ca.T_ck, cb.model, cb.K, cb.nk, cb.width, cb.height, cb.T_ck, dst_linear,
+                             dst_w, dst_h, alpha, fill, out);
+}
 int vc_get_frame(vc_calibrator* h, int f, double T_wk[7], double v_w[3], double* time) {
   if (!h || f < 0 || f >= (int)h->frames.size()) return VC_ERR_BAD_ARG;
   std::lock_guard<std::mutex> lk(h->result_mutex);

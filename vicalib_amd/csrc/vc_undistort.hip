@@ -205,46 +205,53 @@ void vc_undistorter_destroy(vc_undistorter* u) {
   delete u;
 }
 
-int vc_undistort_fit_linear(int model, const double* params, int nparams, int src_w, int src_h, int dst_w, int dst_h, double alpha, double dst_linear[4]) {
-  if (!model_args_ok(model, params, nparams, src_w, src_h) || !dst_linear || dst_w < 2 || dst_h < 2 || dst_w > kMaxSize || dst_h > kMaxSize) return VC_ERR_BAD_ARG;
-  if (!(alpha >= 0.0 && alpha <= 1.0)) return VC_ERR_BAD_ARG;
-  UndistPlan p;
-  std::memset(&p, 0, sizeof(p));
-  p.model = model; p.src_w = src_w; p.src_h = src_h; p.dst_w = dst_w; p.dst_h = dst_h;
-  for (int k = 0; k < nparams; ++k) p.K[k] = params[k];
-  vc::model_precompute(model, p.K, &p.pre);
-  for (int i = 0; i < 3; ++i) p.R_sd[4 * i] = 1.0;
-  // the source border in the pinhole plane: the corners and 64 points inside every edge.  Edge e: 0 left, 1 right, 2 top, 3 bottom; a corner
+}  // extern "C"
+
+// The fit behind vc_undistort_fit_linear (one side, identity rotation) and vc_stereo_fit_linear (two sides, their rectifying rotations):
+// one destination camera for all sides.  side[k] holds the source model, its size and R_sd; dst_w / dst_h / dl are filled in here.  With one
+// side and the identity rotation every product with R is exact, so the single-camera fit returns what it did before it was shared.
+int vc::undist_fit_sides(int n_sides, UndistPlan* side, int dst_w, int dst_h, double alpha, double dst_linear[4]) {
+  // the source borders in the pinhole plane: the corners and 64 points inside every edge.  Edge e: 0 left, 1 right, 2 top, 3 bottom; a corner
   // belongs to both of its edges.
-  const double xm = src_w - 1.0, ym = src_h - 1.0;
-  double lo[4] = {-HUGE_VAL, HUGE_VAL, -HUGE_VAL, HUGE_VAL};      // innermost coordinate seen on every edge: max of the left edge's x, min of the right's, ...
-  double box[4] = {HUGE_VAL, -HUGE_VAL, HUGE_VAL, -HUGE_VAL};     // bounding box x0 x1 y0 y1
-  int kept = 0;
-  auto sample = [&](double u, double v, int e0, int e1) {
-    double r[3];
-    if (!vc::undist_unproject(model, p.K, p.pre, u, v, r) || !(r[2] > 0.0)) return;        // no pinhole image
-    const double x = r[0] / r[2], y = r[1] / r[2];
-    if (!std::isfinite(x) || !std::isfinite(y)) return;
-    ++kept;
-    box[0] = std::min(box[0], x); box[1] = std::max(box[1], x); box[2] = std::min(box[2], y); box[3] = std::max(box[3], y);
-    for (int e : {e0, e1}) {
-      if (e == 0) lo[0] = std::max(lo[0], x);
-      if (e == 1) lo[1] = std::min(lo[1], x);
-      if (e == 2) lo[2] = std::max(lo[2], y);
-      if (e == 3) lo[3] = std::min(lo[3], y);
+  double lo[4] = {-HUGE_VAL, HUGE_VAL, -HUGE_VAL, HUGE_VAL};      // innermost coordinate seen on every edge: max of the left edges' x, min of the right, ...
+  double box[4] = {HUGE_VAL, -HUGE_VAL, HUGE_VAL, -HUGE_VAL};     // bounding box x0 x1 y0 y1 (of all sides: their union)
+  for (int k = 0; k < n_sides; ++k) {
+    UndistPlan& p = side[k];
+    p.dst_w = dst_w; p.dst_h = dst_h;
+    const double xm = p.src_w - 1.0, ym = p.src_h - 1.0;
+    const double* R = p.R_sd;
+    int kept = 0;
+    auto sample = [&](double u, double v, int e0, int e1) {
+      double s[3];
+      if (!vc::undist_unproject(p.model, p.K, p.pre, u, v, s)) return;
+      const double r[3] = {R[0] * s[0] + R[3] * s[1] + R[6] * s[2], R[1] * s[0] + R[4] * s[1] + R[7] * s[2], R[2] * s[0] + R[5] * s[1] + R[8] * s[2]};      // R_ds s
+      if (!(r[2] > 0.0)) return;        // no pinhole image
+      const double x = r[0] / r[2], y = r[1] / r[2];
+      if (!std::isfinite(x) || !std::isfinite(y)) return;
+      ++kept;
+      box[0] = std::min(box[0], x); box[1] = std::max(box[1], x); box[2] = std::min(box[2], y); box[3] = std::max(box[3], y);
+      for (int e : {e0, e1}) {
+        if (e == 0) lo[0] = std::max(lo[0], x);
+        if (e == 1) lo[1] = std::min(lo[1], x);
+        if (e == 2) lo[2] = std::max(lo[2], y);
+        if (e == 3) lo[3] = std::min(lo[3], y);
+      }
+    };
+    sample(0, 0, 0, 2); sample(xm, 0, 1, 2); sample(0, ym, 0, 3); sample(xm, ym, 1, 3);
+    for (int i = 1; i <= 64; ++i) {
+      const double s = i / 65.0;
+      sample(0, s * ym, 0, -1); sample(xm, s * ym, 1, -1); sample(s * xm, 0, 2, -1); sample(s * xm, ym, 3, -1);
     }
-  };
-  sample(0, 0, 0, 2); sample(xm, 0, 1, 2); sample(0, ym, 0, 3); sample(xm, ym, 1, 3);
-  for (int k = 1; k <= 64; ++k) {
-    const double s = k / 65.0;
-    sample(0, s * ym, 0, -1); sample(xm, s * ym, 1, -1); sample(s * xm, 0, 2, -1); sample(s * xm, ym, 3, -1);
+    if (kept < 8) return VC_ERR_NUMERIC;
   }
-  if (kept < 8 || !(lo[0] < lo[1]) || !(lo[2] < lo[3]) || !(box[0] < box[1]) || !(box[2] < box[3])) return VC_ERR_NUMERIC;
+  if (!(lo[0] < lo[1]) || !(lo[2] < lo[3]) || !(box[0] < box[1]) || !(box[2] < box[3])) return VC_ERR_NUMERIC;      // (two sides: an empty intersection)
   // alpha = 0: the rectangle between the edges' innermost samples.  The samples miss an edge's true innermost point by a little, so the
-  // rectangle is then drawn in until every pixel of the destination image's border has a source pixel (same test as the map kernel's).
-  auto to_linear = [&](const double* r, double* dl) {
-    dl[0] = (dst_w - 1.0) / (r[1] - r[0]); dl[2] = -r[0] * dl[0];
-    dl[1] = (dst_h - 1.0) / (r[3] - r[2]); dl[3] = -r[2] * dl[1];
+  // rectangle is then drawn in until every pixel of the destination image's border has a source pixel on every side (same test as the map
+  // kernel's).
+  double dl[4];
+  auto to_linear = [&](const double* r, double* d) {
+    d[0] = (dst_w - 1.0) / (r[1] - r[0]); d[2] = -r[0] * d[0];
+    d[1] = (dst_h - 1.0) / (r[3] - r[2]); d[3] = -r[2] * d[1];
   };
   // Only the destination image's border is probed: the destination pixels that have a source pixel are the preimage of the source rectangle
   // under a map that is continuous and one-to-one on the field the border samples span, a region without holes, so a closed border inside it
@@ -252,27 +259,35 @@ int vc_undistort_fit_linear(int model, const double* params, int nparams, int sr
   double in[4] = {lo[0], lo[1], lo[2], lo[3]}, gain[4] = {1.5, 1.5, 1.5, 1.5};
   bool inside = false;
   for (int round = 0; round < 64 && !inside; ++round) {
-    to_linear(in, p.dl);
-    // by how far (source pixels) the worst pixel of each side of the destination border misses the source image
-    double miss[4] = {0, 0, 0, 0};
-    auto probe = [&](int i, int j, int side) {
-      const double a = ((double)i - p.dl[2]) / p.dl[0], b = ((double)j - p.dl[3]) / p.dl[1];
-      const double ray[3] = {a, b, 1.0};
-      double pix[2];
-      vc::project_any<false>(model, ray, p.K, p.pre, pix, nullptr, nullptr);
-      double d = std::max(std::max(-pix[0], pix[0] - xm), std::max(-pix[1], pix[1] - ym));
-      if (!std::isfinite(d)) d = 1.0;
-      if (d > vc::kUndistBorderTol) miss[side] = std::max(miss[side], d);
-    };
-    for (int j = 0; j < dst_h; ++j) { probe(0, j, 0); probe(dst_w - 1, j, 1); }
-    for (int i = 0; i < dst_w; ++i) { probe(i, 0, 2); probe(i, dst_h - 1, 3); }
-    if (miss[0] == 0.0 && miss[1] == 0.0 && miss[2] == 0.0 && miss[3] == 0.0) { inside = true; break; }
-    // a side moves by its miss over the focal length, times a gain that doubles while the side keeps missing: far off the axis of a
-    // fisheye a step in the pinhole plane moves the source pixel by a small fraction of what it does at the centre
-    const double f[4] = {std::fabs(p.K[0]), std::fabs(p.K[0]), std::fabs(p.K[1]), std::fabs(p.K[1])};
+    to_linear(in, dl);
+    // by how far the worst pixel of each side of the destination border misses a source image, as the step it asks for in the pinhole plane:
+    // the miss in source pixels over that source's focal length, times a gain that doubles while the side keeps missing (far off the axis of a
+    // fisheye a step in the pinhole plane moves the source pixel by a small fraction of what it does at the centre)
+    double step[4] = {0, 0, 0, 0};
+    for (int k = 0; k < n_sides; ++k) {
+      const UndistPlan& p = side[k];
+      const double xm = p.src_w - 1.0, ym = p.src_h - 1.0;
+      const double* R = p.R_sd;
+      double miss[4] = {0, 0, 0, 0};
+      auto probe = [&](int i, int j, int e) {
+        const double a = ((double)i - dl[2]) / dl[0], b = ((double)j - dl[3]) / dl[1];
+        const double ray[3] = {R[0] * a + R[1] * b + R[2], R[3] * a + R[4] * b + R[5], R[6] * a + R[7] * b + R[8]};
+        double pix[2];
+        vc::project_any<false>(p.model, ray, p.K, p.pre, pix, nullptr, nullptr);
+        double d = std::max(std::max(-pix[0], pix[0] - xm), std::max(-pix[1], pix[1] - ym));
+        if (!std::isfinite(d) || (!(ray[2] > 0.0) && p.model != vc::kKb4)) d = 1.0;
+        if (d > vc::kUndistBorderTol) miss[e] = std::max(miss[e], d);
+      };
+      for (int j = 0; j < dst_h; ++j) { probe(0, j, 0); probe(dst_w - 1, j, 1); }
+      for (int i = 0; i < dst_w; ++i) { probe(i, 0, 2); probe(i, dst_h - 1, 3); }
+      const double f[4] = {std::fabs(p.K[0]), std::fabs(p.K[0]), std::fabs(p.K[1]), std::fabs(p.K[1])};
+      for (int e = 0; e < 4; ++e)
+        if (miss[e] != 0.0) step[e] = std::max(step[e], gain[e] * miss[e] / f[e]);
+    }
+    if (step[0] == 0.0 && step[1] == 0.0 && step[2] == 0.0 && step[3] == 0.0) { inside = true; break; }
     for (int e = 0; e < 4; ++e) {
-      if (miss[e] == 0.0) continue;
-      in[e] += ((e & 1) ? -1.0 : 1.0) * gain[e] * miss[e] / f[e];
+      if (step[e] == 0.0) continue;
+      in[e] += ((e & 1) ? -1.0 : 1.0) * step[e];
       gain[e] *= 2.0;
     }
     if (!(in[0] < in[1]) || !(in[2] < in[3])) return VC_ERR_NUMERIC;
@@ -282,6 +297,28 @@ int vc_undistort_fit_linear(int model, const double* params, int nparams, int sr
   for (int k = 0; k < 4; ++k) r[k] = (1.0 - alpha) * in[k] + alpha * box[k];
   to_linear(r, dst_linear);
   return VC_OK;
+}
+void vc::undist_source_plan(UndistPlan* p, int model, const double* params, int nparams, int src_w, int src_h, const double* R_ds) {
+  std::memset(p, 0, sizeof(*p));
+  p->model = model; p->src_w = src_w; p->src_h = src_h;
+  for (int k = 0; k < nparams; ++k) p->K[k] = params[k];
+  vc::model_precompute(model, p->K, &p->pre);
+  for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) p->R_sd[3 * i + j] = R_ds ? R_ds[3 * j + i] : (i == j ? 1.0 : 0.0);
+}
+bool vc::undist_source_args_ok(int model, const double* params, int nparams, int w, int h) { return model_args_ok(model, params, nparams, w, h); }
+bool vc::undist_dest_args_ok(const double* dst_linear /* nullable */, int dst_w, int dst_h, int fill) {
+  return (!dst_linear || linear_ok(dst_linear)) && dst_w >= 2 && dst_h >= 2 && dst_w <= kMaxSize && dst_h <= kMaxSize && fill >= 0 && fill <= 255;
+}
+const vc::UndistPlan& vc::undist_plan_of(const vc_undistorter* u) { return u->p; }
+
+extern "C" {
+
+int vc_undistort_fit_linear(int model, const double* params, int nparams, int src_w, int src_h, int dst_w, int dst_h, double alpha, double dst_linear[4]) {
+  if (!model_args_ok(model, params, nparams, src_w, src_h) || !dst_linear || dst_w < 2 || dst_h < 2 || dst_w > kMaxSize || dst_h > kMaxSize) return VC_ERR_BAD_ARG;
+  if (!(alpha >= 0.0 && alpha <= 1.0)) return VC_ERR_BAD_ARG;
+  UndistPlan p;
+  vc::undist_source_plan(&p, model, params, nparams, src_w, src_h, nullptr);
+  return vc::undist_fit_sides(1, &p, dst_w, dst_h, alpha, dst_linear);
 }
 
 int vc_undistort_images_device(vc_undistorter* u, int n, const unsigned char* d_src, int src_pitch, long long src_stride, unsigned char* d_dst, int dst_pitch,
@@ -294,7 +331,11 @@ int vc_undistort_images_device(vc_undistorter* u, int n, const unsigned char* d_
   launch_remap(u, n, d_src, src_pitch, (size_t)src_stride, d_dst, dst_pitch, (size_t)dst_stride);
   return hipGetLastError() == hipSuccess ? VC_OK : VC_ERR_NO_DEVICE;
 }
-int vc_undistort_images(vc_undistorter* u, int n, const unsigned char* src, int src_pitch, long long src_stride, unsigned char* dst, int dst_pitch, long long dst_stride) {
+}  // extern "C"
+
+// vc_undistort_images in two halves, so that a rectifier (vc_rectify.hip) has both sides' batches in flight before it waits for either:
+// begin stages and enqueues upload, remap and download on the handle's stream; end waits for the stream and hands the pixels out.
+int vc::undist_images_begin(vc_undistorter* u, int n, const unsigned char* src, int src_pitch, long long src_stride, unsigned char* dst, int dst_pitch, long long dst_stride) {
   if (!u || n < 0 || (n > 0 && (!src || !dst)) || src_pitch < u->p.src_w || dst_pitch < u->p.dst_w) return VC_ERR_BAD_ARG;
   if (n > 1 && (src_stride < (long long)src_pitch * u->p.src_h || dst_stride < (long long)dst_pitch * u->p.dst_h)) return VC_ERR_BAD_ARG;
   if (n > 65535) return VC_ERR_BAD_ARG;
@@ -304,17 +345,28 @@ int vc_undistort_images(vc_undistorter* u, int n, const unsigned char* src, int 
   if (u->in_flight) (void)hipStreamSynchronize(u->stream);
   if (!reserve_images(u, n)) return VC_ERR_NO_DEVICE;
   u->in_flight = true;
-  const int sw = u->p.src_w, sh = u->p.src_h, dw = u->p.dst_w, dh = u->p.dst_h, dp = u->p.map_pitch;
+  const int sw = u->p.src_w, sh = u->p.src_h, dp = u->p.map_pitch;
   for (int k = 0; k < n; ++k)
     for (int y = 0; y < sh; ++y) std::memcpy(u->h_src + ((size_t)k * sh + y) * sw, src + (size_t)k * src_stride + (size_t)y * src_pitch, (size_t)sw);
   if (hipMemcpyAsync(u->d_src, u->h_src, u->src_bytes() * n, hipMemcpyHostToDevice, u->stream) != hipSuccess) return VC_ERR_NO_DEVICE;
   launch_remap(u, n, u->d_src, sw, u->src_bytes(), u->d_dst, dp, u->dst_bytes());
-  if (hipGetLastError() != hipSuccess || hipMemcpyAsync(u->h_dst, u->d_dst, u->dst_bytes() * n, hipMemcpyDeviceToHost, u->stream) != hipSuccess ||
-      hipStreamSynchronize(u->stream) != hipSuccess) return VC_ERR_NO_DEVICE;
+  if (hipGetLastError() != hipSuccess || hipMemcpyAsync(u->h_dst, u->d_dst, u->dst_bytes() * n, hipMemcpyDeviceToHost, u->stream) != hipSuccess) return VC_ERR_NO_DEVICE;
+  return VC_OK;
+}
+int vc::undist_images_end(vc_undistorter* u, int n, unsigned char* dst, int dst_pitch, long long dst_stride) {
+  if (n == 0) return VC_OK;
+  if (hipSetDevice(u->device) != hipSuccess || hipStreamSynchronize(u->stream) != hipSuccess) return VC_ERR_NO_DEVICE;
   u->in_flight = false;
+  const int dw = u->p.dst_w, dh = u->p.dst_h, dp = u->p.map_pitch;
   for (int k = 0; k < n; ++k)                          // only the pixels: a destination row's padding is the caller's
     for (int y = 0; y < dh; ++y) std::memcpy(dst + (size_t)k * dst_stride + (size_t)y * dst_pitch, u->h_dst + ((size_t)k * dh + y) * dp, (size_t)dw);
   return VC_OK;
+}
+extern "C" {
+
+int vc_undistort_images(vc_undistorter* u, int n, const unsigned char* src, int src_pitch, long long src_stride, unsigned char* dst, int dst_pitch, long long dst_stride) {
+  const int rc = vc::undist_images_begin(u, n, src, src_pitch, src_stride, dst, dst_pitch, dst_stride);
+  return rc != VC_OK ? rc : vc::undist_images_end(u, n, dst, dst_pitch, dst_stride);
 }
 void* vc_undistort_stream(vc_undistorter* u) { return u ? (void*)u->stream : nullptr; }
 

@@ -95,3 +95,18 @@ VC_HD bool undist_point(const UndistPlan& p, double u, double v, double* ou, dou
 }
 
 }  // namespace vc
+
+// ---- host side of vc_undistort.hip that the rectifier (vc_rectify.hip) builds on; defined there
+struct vc_undistorter;
+namespace vc {
+// model, K, pre, source size and R_sd = R_ds^T (NULL = identity) of a plan; everything else zero
+void undist_source_plan(UndistPlan* p, int model, const double* params, int nparams, int src_w, int src_h, const double* R_ds);
+// one destination camera for n_sides sources (vc_undistort_fit_linear: one side; vc_stereo_fit_linear: two); a status of the C ABI
+int undist_fit_sides(int n_sides, UndistPlan* side, int dst_w, int dst_h, double alpha, double dst_linear[4]);
+bool undist_source_args_ok(int model, const double* params, int nparams, int w, int h);      // the checks of vc_undistorter_create
+bool undist_dest_args_ok(const double* dst_linear /* nullable */, int dst_w, int dst_h, int fill);
+const UndistPlan& undist_plan_of(const vc_undistorter* u);
+// vc_undistort_images in two halves: everything enqueued on the handle's stream / the wait and the copy to the caller
+int undist_images_begin(vc_undistorter* u, int n, const unsigned char* src, int src_pitch, long long src_stride, unsigned char* dst, int dst_pitch, long long dst_stride);
+int undist_images_end(vc_undistorter* u, int n, unsigned char* dst, int dst_pitch, long long dst_stride);
+}  // namespace vc

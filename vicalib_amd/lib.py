@@ -38,6 +38,8 @@ SYMBOLS = [
     "vc_detector_create", "vc_detector_destroy", "vc_detector_set_params", "vc_detector_find", "vc_detector_find_conics",
     "vc_undistorter_create", "vc_undistorter_create_for_camera", "vc_undistorter_destroy", "vc_undistort_fit_linear", "vc_undistort_images",
     "vc_undistort_images_device", "vc_undistort_stream", "vc_undistort_points", "vc_undistort_get_map", "vc_undistort_get_linear", "vc_time_undistort",
+    "vc_stereo_rectify_rotations", "vc_stereo_fit_linear", "vc_match_tiles", "vc_rectifier_create", "vc_rectifier_create_for_cameras", "vc_rectifier_destroy",
+    "vc_rectifier_side", "vc_rectifier_get", "vc_rectify_pairs", "vc_rectify_check", "vc_time_rectify_check",
 ]
 
 
@@ -99,12 +101,13 @@ def load():
         L.vc_get_num_iterations.restype = C.c_uint
         L.vc_get_stream.restype = C.c_void_p
         L.vc_undistort_stream.restype = C.c_void_p
+        L.vc_rectifier_side.restype = C.c_void_p
         L.vc_num_observations.restype = C.c_longlong
         L.vc_report_num_corners.restype = C.c_longlong
         L.vc_holdout_num_corners.restype = C.c_longlong
         L.vc_allreduce_calls.restype = C.c_longlong
         L.vc_last_error.restype = C.c_char_p
-        for name in ("vc_destroy", "vc_detector_destroy", "vc_shard_comm_destroy", "vc_undistorter_destroy"):
+        for name in ("vc_destroy", "vc_detector_destroy", "vc_shard_comm_destroy", "vc_undistorter_destroy", "vc_rectifier_destroy"):
             getattr(L, name).restype = None
         _lib = L
     return _lib
@@ -660,6 +663,16 @@ class Undistorter:
                                                 int(dst_size[0]), int(dst_size[1]), Rp, int(fill), C.byref(self.h)), "undistorter_create")
         self.src_size = (int(src_size[0]), int(src_size[1]))
         self.dst_size = (int(dst_size[0]), int(dst_size[1]))
+        self._borrowed = False
+
+    @classmethod
+    def _borrow(cls, handle, src_size, dst_size):
+        """A side of a Rectifier: the handle belongs to the rectifier and is never destroyed here."""
+        u = cls.__new__(cls)
+        u.L, u.h = load(), C.c_void_p(handle)
+        u.src_size = (int(src_size[0]), int(src_size[1])); u.dst_size = (int(dst_size[0]), int(dst_size[1]))
+        u._borrowed = True
+        return u
 
     @classmethod
     def for_camera(cls, cal, camera, src_size, dst_linear, dst_size=None, R_ds=None, fill=0):
@@ -679,7 +692,8 @@ class Undistorter:
 
     def close(self):
         if getattr(self, "h", None):
-            self.L.vc_undistorter_destroy(self.h)
+            if not getattr(self, "_borrowed", False):
+                self.L.vc_undistorter_destroy(self.h)
             self.h = None
 
     def __del__(self):
@@ -733,3 +747,136 @@ class Undistorter:
         out = np.zeros(3)
         _check(self.L.vc_time_undistort(self.h, int(n_images), int(reps), _d(out)), "time_undistort")
         return dict(map=out[0], remap=out[1], points=out[2])
+
+
+def _i64(a):
+    return np.ascontiguousarray(a, dtype=np.int64)
+
+
+class Rectifier:
+    """Using the calibration of a pair (include/vicalib_amd.h: vc_stereo_*, vc_rectif*): cameras a and b -- (model, params, (w, h), T_ck) each --
+    rotated into a common frame with one pinhole camera dst_linear of dst_size for both (dst_linear None: fitted at alpha).  rotations,
+    fit_linear and match_tiles are host code and need no GPU.  side(0 / 1) -> that side's Undistorter (borrowed); pairs(a, b) -> the two
+    rectified image batches; check(...) -> the stereo consistency check; time(reps) -> ms per launch of the last check's sweep."""
+
+    def __init__(self, cam_a, cam_b, dst_size=None, dst_linear=None, alpha=0.0, fill=0, device=0, _cameras_of=None):
+        self.L = load()
+        self.h = C.c_void_p()
+        dl = None if dst_linear is None else _d(np.ascontiguousarray(dst_linear, dtype=np.float64).reshape(4))
+        if _cameras_of is not None:
+            cal, a, b, size_a, size_b = _cameras_of
+            dst_size = size_a if dst_size is None else dst_size
+            _check(self.L.vc_rectifier_create_for_cameras(cal.h, int(a), int(b), dl, int(dst_size[0]), int(dst_size[1]), C.c_double(alpha), int(fill),
+                                                          C.byref(self.h)), "rectifier_create_for_cameras")
+        else:
+            (ma, Ka, size_a, Ta), (mb, Kb, size_b, Tb) = cam_a, cam_b
+            Ka = np.ascontiguousarray(Ka, dtype=np.float64); Kb = np.ascontiguousarray(Kb, dtype=np.float64)
+            dst_size = size_a if dst_size is None else dst_size
+            _check(self.L.vc_rectifier_create(int(device), _model_id(ma), _d(Ka), len(Ka), int(size_a[0]), int(size_a[1]), _d(Ta), _model_id(mb), _d(Kb), len(Kb),
+                                              int(size_b[0]), int(size_b[1]), _d(Tb), dl, int(dst_size[0]), int(dst_size[1]), C.c_double(alpha), int(fill),
+                                              C.byref(self.h)), "rectifier_create")
+        self.src_sizes = ((int(size_a[0]), int(size_a[1])), (int(size_b[0]), int(size_b[1])))
+        self.dst_size = (int(dst_size[0]), int(dst_size[1]))
+        self._sides = [None, None]
+
+    @classmethod
+    def for_cameras(cls, cal, cam_a, cam_b, size_a, size_b=None, dst_size=None, dst_linear=None, alpha=0.0, fill=0):
+        """For two cameras of a ViCalibrator as GetCamera returns them (size_a / size_b: the sizes they were added with)."""
+        return cls(None, None, dst_size, dst_linear, alpha, fill, _cameras_of=(cal, cam_a, cam_b, size_a, size_a if size_b is None else size_b))
+
+    @staticmethod
+    def rotations(T_ck_a, T_ck_b):
+        """-> (R_ds_a, R_ds_b, signed baseline) (vc_stereo_rectify_rotations)"""
+        Ra = np.zeros((3, 3)); Rb = np.zeros((3, 3)); b = C.c_double(0)
+        _check(load().vc_stereo_rectify_rotations(_d(T_ck_a), _d(T_ck_b), _d(Ra), _d(Rb), C.byref(b)), "stereo_rectify_rotations")
+        return Ra, Rb, b.value
+
+    @staticmethod
+    def fit_linear(cam_a, R_ds_a, cam_b, R_ds_b, dst_size=None, alpha=0.0):
+        """cam = (model, params, (w, h)) -> [fu, fv, u0, v0] common to both sides (vc_stereo_fit_linear)"""
+        (ma, Ka, size_a), (mb, Kb, size_b) = cam_a[:3], cam_b[:3]
+        Ka = np.ascontiguousarray(Ka, dtype=np.float64); Kb = np.ascontiguousarray(Kb, dtype=np.float64)
+        dst_size = size_a if dst_size is None else dst_size
+        out = np.zeros(4)
+        Ra = np.ascontiguousarray(R_ds_a, dtype=np.float64).reshape(3, 3); Rb = np.ascontiguousarray(R_ds_b, dtype=np.float64).reshape(3, 3)
+        _check(load().vc_stereo_fit_linear(_model_id(ma), _d(Ka), len(Ka), int(size_a[0]), int(size_a[1]), _d(Ra), _model_id(mb), _d(Kb), len(Kb), int(size_b[0]),
+                                           int(size_b[1]), _d(Rb), int(dst_size[0]), int(dst_size[1]), C.c_double(alpha), _d(out)), "stereo_fit_linear")
+        return out
+
+    @staticmethod
+    def match_tiles(tile_frame, tile_cam, tile_off, point_id, cam_a=0, cam_b=1):
+        """-> (frames [F], frame_off [F + 1], pos_a [n], pos_b [n]): per frame that has both cameras the positions of the corners with equal point
+        id, ordered by frame, then point id (vc_match_tiles)"""
+        L = load()
+        tf = np.ascontiguousarray(tile_frame, dtype=np.int32); tc = np.ascontiguousarray(tile_cam, dtype=np.int32)
+        off = _i64(tile_off); ids = np.ascontiguousarray(point_id, dtype=np.int32)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)      # noqa: E731
+        nf = C.c_int(0); n = C.c_longlong(0)
+        _check(L.vc_match_tiles(len(tf), p(tf), p(tc), p(off), p(ids), int(cam_a), int(cam_b), C.byref(nf), C.byref(n), None, None, None, None), "match_tiles")
+        frames = np.zeros(nf.value, dtype=np.int32); foff = np.zeros(nf.value + 1, dtype=np.int64)
+        pa = np.zeros(n.value, dtype=np.int64); pb = np.zeros(n.value, dtype=np.int64)
+        _check(L.vc_match_tiles(len(tf), p(tf), p(tc), p(off), p(ids), int(cam_a), int(cam_b), C.byref(nf), C.byref(n), p(frames), p(foff), p(pa), p(pb)), "match_tiles")
+        return frames, foff, pa, pb
+
+    def close(self):
+        if getattr(self, "h", None):
+            for u in self._sides:
+                if u is not None:
+                    u.close()
+            self.L.vc_rectifier_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+    def side(self, k):
+        if self._sides[k] is None:
+            self._sides[k] = Undistorter._borrow(self.L.vc_rectifier_side(self.h, int(k)), self.src_sizes[k], self.dst_size)
+        return self._sides[k]
+
+    def get(self):
+        """-> dict(R_ds_a, R_ds_b, dst_linear, dst_size, baseline, T_ck_rect_a, T_ck_rect_b)"""
+        Ra = np.zeros((3, 3)); Rb = np.zeros((3, 3)); dl = np.zeros(4); sz = (C.c_int * 2)(); b = C.c_double(0); Ta = np.zeros(7); Tb = np.zeros(7)
+        _check(self.L.vc_rectifier_get(self.h, _d(Ra), _d(Rb), _d(dl), sz, C.byref(b), _d(Ta), _d(Tb)), "rectifier_get")
+        return dict(R_ds_a=Ra, R_ds_b=Rb, dst_linear=dl, dst_size=(sz[0], sz[1]), baseline=b.value, T_ck_rect_a=Ta, T_ck_rect_b=Tb)
+
+    def pairs(self, a, b):
+        """a, b: uint8 [n, h, w] of the two sources (contiguous) -> the two rectified batches (vc_rectify_pairs)"""
+        a = np.ascontiguousarray(a, dtype=np.uint8); b = np.ascontiguousarray(b, dtype=np.uint8)
+        single = a.ndim == 2
+        if single:
+            a, b = a[None], b[None]
+        n = len(a)
+        assert len(b) == n and a.shape[1:] == self.src_sizes[0][::-1] and b.shape[1:] == self.src_sizes[1][::-1], (a.shape, b.shape)
+        oa = np.zeros((n, self.dst_size[1], self.dst_size[0]), dtype=np.uint8); ob = np.zeros_like(oa)
+        ll = C.c_longlong
+        _check(self.L.vc_rectify_pairs(self.h, n, C.c_void_p(a.ctypes.data), int(a.strides[1]), ll(a.strides[0]), C.c_void_p(b.ctypes.data), int(b.strides[1]),
+                                       ll(b.strides[0]), C.c_void_p(oa.ctypes.data), int(oa.strides[1]), ll(oa.strides[0]), C.c_void_p(ob.ctypes.data),
+                                       int(ob.strides[1]), ll(ob.strides[0])), "rectify_pairs")
+        return (oa[0], ob[0]) if single else (oa, ob)
+
+    def check(self, frame_off, px_a, px_b, target=None):
+        """The stereo consistency check (vc_rectify_check) -> dict: per pair `pairs` [n, 6] (dv, d, P, mean row) and `invalid` [n] bool; per frame
+        count, n_invalid, sum_dv, sum_dv2, max_abs_dv, worst, mean_z, rigid_rms."""
+        foff = _i64(frame_off); nf = len(foff) - 1
+        n = int(foff[-1]) if nf >= 0 and len(foff) else 0
+        pa = np.ascontiguousarray(px_a, dtype=np.float64).reshape(-1, 2); pb = np.ascontiguousarray(px_b, dtype=np.float64).reshape(-1, 2)
+        assert len(pa) == n and len(pb) == n, (len(pa), len(pb), n)
+        tg = None
+        if target is not None:
+            tg = np.ascontiguousarray(target, dtype=np.float64).reshape(-1, 3)
+            assert len(tg) == n
+        out = dict(pairs=np.zeros((n, 6)), invalid=np.zeros(n, dtype=np.uint8), count=np.zeros(nf, dtype=np.int32), n_invalid=np.zeros(nf, dtype=np.int32),
+                   sum_dv=np.zeros(nf), sum_dv2=np.zeros(nf), max_abs_dv=np.zeros(nf), worst=np.zeros(nf, dtype=np.int64), mean_z=np.zeros(nf),
+                   rigid_rms=np.zeros(nf))
+        p = lambda a: a.ctypes.data_as(C.c_void_p)      # noqa: E731
+        _check(self.L.vc_rectify_check(self.h, nf, p(foff), p(pa), p(pb), None if tg is None else p(tg), p(out["pairs"]), p(out["invalid"]), p(out["count"]),
+                                       p(out["n_invalid"]), p(out["sum_dv"]), p(out["sum_dv2"]), p(out["max_abs_dv"]), p(out["worst"]), p(out["mean_z"]),
+                                       p(out["rigid_rms"])), "rectify_check")
+        out["invalid"] = out["invalid"].astype(bool)
+        return out
+
+    def time(self, reps=20):
+        ms = C.c_double(0)
+        _check(self.L.vc_time_rectify_check(self.h, int(reps), C.byref(ms)), "time_rectify_check")
+        return ms.value
