@@ -136,6 +136,14 @@ static void DefineFlags() {
          "stereo_check.csv (row misalignment and metric consistency of the calibration's own matched detections, per frame) and, with image input, the rectified images cam<i>_<name>.pgm.");
   Define("rectify_cams", "string", "0,1", "The two cameras -rectify_dir rectifies: a,b.");
   Define("rectify_alpha", "double", "0", "Destination intrinsics of -rectify_dir: 0 = every pixel of both rectified images is valid ... 1 = every source pixel of both cameras is kept.");
+  // two calibrations compared in pixel space (vc_compar*): off unless asked for
+  Define("compare_models", "string", "", "a.xml,b.xml: compare the cameras of two rig files, camera by camera, into -compare_dir; needs no -cam, nothing is calibrated.");
+  Define("compare_to", "string", "", "b.xml: compare the calibration just computed (A) with the cameras of this rig file (B) into -compare_dir.");
+  Define("compare_dir", "string", "", "Directory for compare_cam<i>.csv (x, y, du, dv, flags per lattice sample, at the implied rotation), compare_summary.csv and, with more "
+         "than one camera, compare_extrinsics.csv.  Its parent must exist.");
+  Define("compare_grid", "string", "64x48", "Lattice of the comparison, GXxGY: 2 ... image width by 2 ... image height, at most 2^22 samples.");
+  Define("compare_fit_radius", "double", "0.5", "The implied rotation is fitted over the samples within this fraction of the half-diagonal of the image centre (> 0).");
+  Define("compare_rings", "int32", "8", "Rings of equal width in normalised radius in compare_summary.csv, 1 ... 64.");
 }
 
 static int Usage(int code) {
@@ -610,6 +618,188 @@ static bool RectifyOutputs(vic::ViCalibrator& cal, const std::vector<Channel>& c
   return true;
 }
 
+// ---- -compare_models / -compare_to: two calibrations compared in pixel space (vc_compar*) ---------------------------------------------
+// every <camera> of a calibu rig XML with its pose: the inverse of vc_write_camera_models.  T_wc = [M | t] with M = R_ck^T RDF^T and
+// t = -R_ck^T t_ck, RDF the matrix of the <right>, <down> and <forward> rows (the identity when they are missing).
+static bool ReadRigFile(const std::string& path, std::vector<vic::CameraAndPose>* cams, std::string* err) {
+  std::ifstream f(path);
+  if (!f) { *err = "cannot open rig file " + path; return false; }
+  std::stringstream ss; ss << f.rdbuf();
+  const std::string s = ss.str();
+  cams->clear();
+  auto numbers = [](std::string t, std::vector<double>* v) {
+    for (char& ch : t) if (ch == '[' || ch == ']') ch = ' ';
+    return ParseNumbers(t, v);
+  };
+  for (size_t from = 0;;) {
+    const size_t p = s.find("<camera>", from);
+    if (p == std::string::npos) break;
+    const size_t q = s.find("</camera>", p);
+    if (q == std::string::npos) { *err = path + ": <camera> without </camera>"; return false; }
+    const std::string c = s.substr(p, q - p);
+    from = q + 9;
+    const std::string where = path + ": camera " + std::to_string(cams->size());
+    vic::CameraAndPose cam;
+    const std::string head = Between(c, "<camera_model", ">");
+    cam.model = ModelId(Between(head, "type=\"", "\""));
+    if (cam.model < 0) { *err = where + ": unsupported camera model type '" + Between(head, "type=\"", "\"") + "'"; return false; }
+    std::vector<double> v;
+    if (!numbers(Between(c, "<width>", "</width>"), &v) || v.size() != 1 || !(v[0] >= 2 && v[0] <= 8192)) { *err = where + ": no usable <width>"; return false; }
+    cam.width = (int)v[0];
+    if (!numbers(Between(c, "<height>", "</height>"), &v) || v.size() != 1 || !(v[0] >= 2 && v[0] <= 8192)) { *err = where + ": no usable <height>"; return false; }
+    cam.height = (int)v[0];
+    static const int kParams[6] = {5, 6, 7, 8, 4, 10};
+    if (!numbers(Between(c, "<params>", "</params>"), &cam.params) || (int)cam.params.size() != kParams[cam.model]) {
+      *err = where + ": <params> does not hold the " + std::to_string(kParams[cam.model]) + " parameters of " + ModelName(cam.model); return false;
+    }
+    double rdf[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+    const char* rows[3] = {"right", "down", "forward"};
+    for (int r = 0; r < 3; ++r) {
+      const std::string t = Between(c, std::string("<") + rows[r] + ">", std::string("</") + rows[r] + ">");
+      if (t.empty()) continue;
+      if (!numbers(t, &v) || v.size() != 3) { *err = where + ": <" + rows[r] + "> does not hold 3 numbers"; return false; }
+      for (int k = 0; k < 3; ++k) rdf[3 * r + k] = v[k];
+    }
+    if (!numbers(Between(c, "<T_wc>", "</T_wc>"), &v) || v.size() != 12) { *err = where + ": <T_wc> does not hold 3 x 4 numbers"; return false; }
+    // R_ck^T = M RDF; R_ck = its transpose; t_ck = -R_ck t
+    double Rt[9], R[9];
+    for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) Rt[3 * i + j] = v[4 * i] * rdf[j] + v[4 * i + 1] * rdf[3 + j] + v[4 * i + 2] * rdf[6 + j];
+    for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) R[3 * i + j] = Rt[3 * j + i];
+    double ortho = 0.0;
+    for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j)
+      ortho = std::max(ortho, std::fabs(R[3 * i] * R[3 * j] + R[3 * i + 1] * R[3 * j + 1] + R[3 * i + 2] * R[3 * j + 2] - (i == j ? 1.0 : 0.0)));
+    const double det = R[0] * (R[4] * R[8] - R[5] * R[7]) - R[1] * (R[3] * R[8] - R[5] * R[6]) + R[2] * (R[3] * R[7] - R[4] * R[6]);
+    if (!(ortho <= 1e-6) || !(det > 0.0)) { *err = where + ": <T_wc> and the axis rows do not give a rotation"; return false; }
+    double* T = cam.T_ck.data();
+    // Shepperd: the unit quaternion [x y z w] of R_ck
+    const double tr = R[0] + R[4] + R[8];
+    if (tr > 0.0) { const double k = 2.0 * std::sqrt(tr + 1.0); T[3] = 0.25 * k; T[0] = (R[7] - R[5]) / k; T[1] = (R[2] - R[6]) / k; T[2] = (R[3] - R[1]) / k; }
+    else if (R[0] > R[4] && R[0] > R[8]) { const double k = 2.0 * std::sqrt(1.0 + R[0] - R[4] - R[8]); T[3] = (R[7] - R[5]) / k; T[0] = 0.25 * k; T[1] = (R[1] + R[3]) / k; T[2] = (R[2] + R[6]) / k; }
+    else if (R[4] > R[8]) { const double k = 2.0 * std::sqrt(1.0 + R[4] - R[0] - R[8]); T[3] = (R[2] - R[6]) / k; T[0] = (R[1] + R[3]) / k; T[1] = 0.25 * k; T[2] = (R[5] + R[7]) / k; }
+    else { const double k = 2.0 * std::sqrt(1.0 + R[8] - R[0] - R[4]); T[3] = (R[3] - R[1]) / k; T[0] = (R[2] + R[6]) / k; T[1] = (R[5] + R[7]) / k; T[2] = 0.25 * k; }
+    const double qn = std::sqrt(T[0] * T[0] + T[1] * T[1] + T[2] * T[2] + T[3] * T[3]);
+    for (int k = 0; k < 4; ++k) T[k] /= qn;
+    for (int i = 0; i < 3; ++i) T[4 + i] = -(R[3 * i] * v[3] + R[3 * i + 1] * v[7] + R[3 * i + 2] * v[11]);
+    cams->push_back(cam);
+  }
+  if (cams->empty()) { *err = path + ": no <camera>"; return false; }
+  return true;
+}
+// -compare_grid GXxGY
+static bool ParseCompareGrid(const std::string& s, int* gx, int* gy) {
+  int a = 0, b = 0; char tail = 0;
+  if (std::sscanf(s.c_str(), "%dx%d%c", &a, &b, &tail) != 2 || a < 2 || b < 2 || (long long)a * b > (1LL << 22)) return false;
+  *gx = a; *gy = b;
+  return true;
+}
+struct CompareOptions { std::string dir; int gx = 64, gy = 48, rings = 8; double fit_radius = 0.5; };
+// the flags of a comparison, checked before anything else runs
+static bool CompareFlags(CompareOptions* o, std::string* err) {
+  o->dir = FlagString("compare_dir");
+  if (o->dir.empty()) { *err = "-compare_models / -compare_to need -compare_dir"; return false; }
+  if (!ParseCompareGrid(FlagString("compare_grid"), &o->gx, &o->gy)) { *err = "illegal value '" + FlagString("compare_grid") + "' specified for flag 'compare_grid': expected GXxGY, both at least 2, at most 2^22 samples"; return false; }
+  o->fit_radius = FlagDouble("compare_fit_radius");
+  if (!(o->fit_radius > 0.0 && o->fit_radius <= 1e6)) { *err = "illegal value for flag 'compare_fit_radius': expected a radius above 0"; return false; }
+  o->rings = (int)FlagInt("compare_rings");
+  if (o->rings < 1 || o->rings > 64) { *err = "illegal value for flag 'compare_rings': expected 1 ... 64"; return false; }
+  return true;
+}
+// what can be said about two rigs before a device is looked for
+static bool ComparableRigs(const std::vector<vic::CameraAndPose>& A, const std::vector<vic::CameraAndPose>& B, const CompareOptions& o, std::string* err) {
+  if (A.size() != B.size()) { *err = "the two calibrations have " + std::to_string(A.size()) + " and " + std::to_string(B.size()) + " cameras"; return false; }
+  for (size_t c = 0; c < A.size(); ++c) {
+    if (A[c].width != B[c].width || A[c].height != B[c].height) {
+      *err = "camera " + std::to_string(c) + ": image sizes " + std::to_string(A[c].width) + "x" + std::to_string(A[c].height) + " and " + std::to_string(B[c].width) + "x" +
+             std::to_string(B[c].height) + " differ";
+      return false;
+    }
+    if (o.gx > A[c].width || o.gy > A[c].height) { *err = "camera " + std::to_string(c) + ": -compare_grid exceeds the image"; return false; }
+  }
+  return true;
+}
+// Compares A with B camera by camera and writes the files of -compare_dir.  Exit status: 0, 1 (an error, said in *err) or 3 (no device).
+static int CompareRigs(const std::vector<vic::CameraAndPose>& A, const std::vector<vic::CameraAndPose>& B, const CompareOptions& o, int device, std::string* err) {
+  if (!ComparableRigs(A, B, o, err)) return 1;
+  struct stat st;
+  if (mkdir(o.dir.c_str(), 0777) != 0 && !(stat(o.dir.c_str(), &st) == 0 && S_ISDIR(st.st_mode))) { *err = "cannot create the directory " + o.dir; return 1; }      // (one level)
+  FILE* fs = std::fopen((o.dir + "/compare_summary.csv").c_str(), "w");
+  if (!fs) { *err = "cannot write into " + o.dir; return 1; }
+  std::fprintf(fs, "camera,model_a,model_b,rx_deg,ry_deg,rz_deg,status,iterations,n_fit,count,invalid,rms_px,max_px,count_plain,rms_plain_px,max_plain_px\n");
+  std::vector<vic::CompareRings> rings(A.size());
+  std::vector<std::array<double, 9>> implied(A.size());
+  int rc = 0;
+  for (size_t c = 0; c < A.size() && rc == 0; ++c) {
+    vc_comparer* h = nullptr;
+    const int st_create = vc_comparer_create(device, A[c].model, A[c].params.data(), (int)A[c].params.size(), B[c].model, B[c].params.data(), (int)B[c].params.size(),
+                                             A[c].width, A[c].height, o.gx, o.gy, &h);
+    if (st_create == VC_ERR_NO_DEVICE) { *err = "no HIP device (there is no CPU fallback)"; rc = 3; break; }
+    if (st_create != VC_OK) { *err = "camera " + std::to_string(c) + ": the comparison refuses these cameras (status " + std::to_string(st_create) + ")"; rc = 1; break; }
+    const size_t n = (size_t)o.gx * o.gy;
+    std::vector<double> d(2 * n);
+    std::vector<unsigned char> fl(n);
+    vic::CompareFit fit;
+    vic::CompareSummary s, sp;
+    int q = vc_compare_run(h, o.fit_radius, 0, nullptr);
+    if (q == VC_OK) q = vc_compare_get_fit(h, fit.R_ba, &fit.status, &fit.iterations, &fit.n_fit, &fit.n_left_out, &fit.cost0, &fit.cost);
+    if (q == VC_OK) q = vc_compare_get_map(h, d.data(), fl.data());
+    if (q == VC_OK) q = vc_compare_summary(h, &s.count, &s.invalid, &s.sum_du, &s.sum_dv, &s.sum_sq, &s.max_err, &s.worst);
+    vic::CompareRings& r = rings[c];
+    r.count.resize(o.rings); r.invalid.resize(o.rings); r.sum_sq.resize(o.rings); r.max_err.resize(o.rings);
+    if (q == VC_OK) q = vc_compare_rings(h, o.rings, r.count.data(), r.invalid.data(), r.sum_sq.data(), r.max_err.data());
+    if (q == VC_OK) q = vc_compare_run(h, 0.0, 0, nullptr);                                  // ... and at R = I
+    if (q == VC_OK) q = vc_compare_summary(h, &sp.count, &sp.invalid, &sp.sum_du, &sp.sum_dv, &sp.sum_sq, &sp.max_err, &sp.worst);
+    vc_comparer_destroy(h);
+    if (q != VC_OK) {
+      *err = "camera " + std::to_string(c) + (q == VC_ERR_NUMERIC ? ": the implied rotation cannot be fitted (fewer than 3 samples within -compare_fit_radius that both calibrations have an image of, or a degenerate system)"
+                                                                  : ": the comparison failed (status " + std::to_string(q) + ")");
+      rc = q == VC_ERR_NO_DEVICE ? 3 : 1; break;
+    }
+    std::memcpy(implied[c].data(), fit.R_ba, 72);
+    FILE* fm = std::fopen((o.dir + "/compare_cam" + std::to_string(c) + ".csv").c_str(), "w");
+    if (!fm) { *err = "cannot write into " + o.dir; rc = 1; break; }
+    std::fprintf(fm, "x,y,du,dv,flags\n");
+    for (size_t k = 0; k < n; ++k) {
+      const int i = (int)(k % o.gx), j = (int)(k / o.gx);
+      std::fprintf(fm, "%.17g,%.17g,%.17g,%.17g,%d\n", (double)(i * (A[c].width - 1)) / (o.gx - 1), (double)(j * (A[c].height - 1)) / (o.gy - 1), d[2 * k], d[2 * k + 1], (int)fl[k]);
+    }
+    std::fclose(fm);
+    // the implied rotation as a rotation vector
+    const double* R = fit.R_ba;
+    const double vx = 0.5 * (R[7] - R[5]), vy = 0.5 * (R[2] - R[6]), vz = 0.5 * (R[3] - R[1]), sn = std::sqrt(vx * vx + vy * vy + vz * vz);
+    const double ang = std::atan2(sn, 0.5 * (R[0] + R[4] + R[8] - 1.0)), k = sn > 0.0 ? ang / sn * 180.0 / M_PI : 0.0;
+    std::fprintf(fs, "%zu,%s,%s,%.17g,%.17g,%.17g,%d,%d,%d,%lld,%lld,%.17g,%.17g,%lld,%.17g,%.17g\n", c, ModelName(A[c].model), ModelName(B[c].model), k * vx, k * vy, k * vz,
+                 fit.status, fit.iterations, fit.n_fit, s.count, s.invalid, s.count > 0 ? std::sqrt(s.sum_sq / s.count) : 0.0, s.max_err, sp.count,
+                 sp.count > 0 ? std::sqrt(sp.sum_sq / sp.count) : 0.0, sp.max_err);
+    std::fprintf(stderr, "I camera %zu (%s against %s): implied rotation %.4g deg, %.4g px rms (%.4g px max) over %lld samples; %.4g px rms without it\n", c,
+                 ModelName(A[c].model), ModelName(B[c].model), ang * 180.0 / M_PI, s.count > 0 ? std::sqrt(s.sum_sq / s.count) : 0.0, s.max_err, s.count,
+                 sp.count > 0 ? std::sqrt(sp.sum_sq / sp.count) : 0.0);
+  }
+  if (rc == 0) {                                         // the second table of the summary: one row per camera and ring, at the implied rotation
+    std::fprintf(fs, "camera,ring,rho_from,rho_to,count,invalid,rms_px,max_px\n");
+    for (size_t c = 0; c < A.size(); ++c)
+      for (int k = 0; k < o.rings; ++k)
+        std::fprintf(fs, "%zu,%d,%.17g,%.17g,%lld,%lld,%.17g,%.17g\n", c, k, (double)k / o.rings, (double)(k + 1) / o.rings, rings[c].count[k], rings[c].invalid[k],
+                     rings[c].count[k] > 0 ? std::sqrt(rings[c].sum_sq[k] / rings[c].count[k]) : 0.0, rings[c].max_err[k]);
+  }
+  std::fclose(fs);
+  if (rc == 0 && A.size() > 1) {
+    FILE* fe = std::fopen((o.dir + "/compare_extrinsics.csv").c_str(), "w");
+    if (!fe) { *err = "cannot write into " + o.dir; return 1; }
+    std::fprintf(fe, "camera,angle_deg,distance_m,angle_plain_deg,distance_plain_m,a_qx,a_qy,a_qz,a_qw,a_tx,a_ty,a_tz,b_qx,b_qy,b_qz,b_qw,b_tx,b_ty,b_tz\n");
+    for (size_t c = 0; c < A.size(); ++c) {              // (camera 0 against itself: a row of zeros that carries its two poses)
+      double out[4];
+      if (vc_compare_extrinsics(A[0].T_ck.data(), A[c].T_ck.data(), B[0].T_ck.data(), B[c].T_ck.data(), implied[0].data(), implied[c].data(), out) != VC_OK) {
+        *err = "camera " + std::to_string(c) + ": the poses cannot be compared"; std::fclose(fe); return 1;
+      }
+      std::fprintf(fe, "%zu,%.17g,%.17g,%.17g,%.17g", c, out[0] * 180.0 / M_PI, out[1], out[2] * 180.0 / M_PI, out[3]);
+      for (const vic::CameraAndPose* cam : {&A[c], &B[c]}) for (int k = 0; k < 7; ++k) std::fprintf(fe, ",%.17g", cam->T_ck.v[k]);
+      std::fprintf(fe, "\n");
+    }
+    std::fclose(fe);
+  }
+  return rc;
+}
+
 int main(int argc, char** argv) {
   DefineFlags();
   std::string err;
@@ -629,6 +819,26 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "ERROR: illegal value '%s' specified for flag 'holdout_every': expected 0 (off) or N >= 2 (N = 1 would leave no frame to calibrate from)\n", FlagString("holdout_every").c_str());
     return 1;
   }
+  // ---- -compare_models a.xml,b.xml: file against file, nothing is calibrated; -compare_to b.xml: read now, compared behind the results
+  CompareOptions compare;
+  std::vector<vic::CameraAndPose> compare_b;
+  if (!FlagString("compare_models").empty() || !FlagString("compare_to").empty()) {
+    if (!FlagString("compare_models").empty() && !FlagString("compare_to").empty()) { std::fprintf(stderr, "ERROR: -compare_models and -compare_to exclude each other\n"); return 1; }
+    if (!CompareFlags(&compare, &err)) { std::fprintf(stderr, "ERROR: %s\n", err.c_str()); return 1; }
+  }
+  if (!FlagString("compare_models").empty()) {
+    const std::string& both = FlagString("compare_models");
+    const size_t comma = both.find(',');
+    if (comma == std::string::npos || comma == 0 || comma + 1 >= both.size() || both.find(',', comma + 1) != std::string::npos) {
+      std::fprintf(stderr, "ERROR: illegal value '%s' specified for flag 'compare_models': expected a.xml,b.xml\n", both.c_str()); return 1;
+    }
+    std::vector<vic::CameraAndPose> a;
+    if (!ReadRigFile(both.substr(0, comma), &a, &err) || !ReadRigFile(both.substr(comma + 1), &compare_b, &err)) { std::fprintf(stderr, "F %s\n", err.c_str()); return 1; }
+    const int rc = CompareRigs(a, compare_b, compare, (int)FlagInt("device"), &err);
+    if (rc != 0) std::fprintf(stderr, "%s %s\n", rc == 3 ? "F" : "E comparison failed:", err.c_str());
+    return rc;
+  }
+  if (!FlagString("compare_to").empty() && !ReadRigFile(FlagString("compare_to"), &compare_b, &err)) { std::fprintf(stderr, "F %s\n", err.c_str()); return 1; }
   if (FlagString("cam").empty()) { std::fprintf(stderr, "F No camera URI given\n"); return 1; }      // vicalib-engine.cc:445
   // ---- grid (vicalib-engine.cc:449-464): the detections already carry X,Y,Z; the preset only bounds the dot ids ----
   int grid_w = (int)FlagInt("grid_width"), grid_h = (int)FlagInt("grid_height");
@@ -722,6 +932,7 @@ int main(int argc, char** argv) {
   }
   if (input_cameras.size() < n_cam) { std::fprintf(stderr, "F %zu camera models for %zu channels\n", input_cameras.size(), n_cam); return 1; }
   input_cameras.resize(n_cam);
+  if (!compare_b.empty() && !ComparableRigs(input_cameras, compare_b, compare, &err)) { std::fprintf(stderr, "F -compare_to: %s\n", err.c_str()); return 1; }      // before any solve
 
   // ---- frames: union of the frame ids, -frame_skip, -num_vicalib_frames (vicalib-engine.cc:540-590) ---------------------
   std::set<long> ids;
@@ -1065,6 +1276,16 @@ int main(int argc, char** argv) {
         { std::fprintf(stderr, "E rectification failed: %s\n", err.c_str()); rectify_failed = true; }
     } catch (const std::exception& e) { std::fprintf(stderr, "E rectification failed: %s\n", e.what()); rectify_failed = true; }
   }
+  bool compare_failed = false;
+  if (!compare_b.empty()) {                              // -compare_to: the result (A) against the file (B)
+    std::vector<vic::CameraAndPose> a;
+    for (size_t c = 0; c < n_cam; ++c) {
+      vic::CameraAndPose now = cal.GetCamera(c);
+      now.model = input_cameras[c].model; now.width = input_cameras[c].width; now.height = input_cameras[c].height;
+      a.push_back(now);
+    }
+    if (CompareRigs(a, compare_b, compare, (int)FlagInt("device"), &err) != 0) { std::fprintf(stderr, "E comparison failed: %s\n", err.c_str()); compare_failed = true; }
+  }
   if (FlagBool("print_poses")) {
     if (FILE* f = std::fopen("poses.txt", "w")) {
       for (size_t i = 0; i < all_frames.size(); ++i) { double c[6]; T2Cart(all_frames[i].t_wp_.data(), c); std::fprintf(f, "%f\t%f\t%f\t%f\t%f\t%f\n", c[0], c[1], c[2], c[3], c[4], c[5]); }
@@ -1101,5 +1322,6 @@ int main(int argc, char** argv) {
   std::printf("calibration %s -> %s\n", success ? "succeeded" : "FAILED", FlagString("output").c_str());
   if (undistort_failed) std::fprintf(stderr, "E -undistort_dir: the undistorted images are incomplete (exit status %d)\n", success ? 1 : 2);
   if (rectify_failed) std::fprintf(stderr, "E -rectify_dir: the rectification's files are incomplete (exit status %d)\n", success ? 1 : 2);
-  return success ? ((undistort_failed || rectify_failed) ? 1 : 0) : 2;
+  if (compare_failed) std::fprintf(stderr, "E -compare_to: the comparison's files are incomplete (exit status %d)\n", success ? 1 : 2);
+  return success ? ((undistort_failed || rectify_failed || compare_failed) ? 1 : 0) : 2;
 }

@@ -479,6 +479,53 @@ int vc_rectify_check(vc_rectifier* r, int n_frames, const long long* frame_off /
  * device-resident data (VC_ERR_BAD_ARG before a check). */
 int vc_time_rectify_check(vc_rectifier* r, int reps, double* out_ms);
 
+/* ---- comparing two calibrations of one camera in pixel space ----------------------------------------------------------------------
+ * Did a recalibration change the camera, by how much, and where in the image?  Cameras A and B (any two of the six models) of the SAME
+ * image size w x h, and a lattice of grid_x x grid_y samples: sample s = j grid_x + i sits at q = (i (w - 1) / (grid_x - 1),
+ * j (h - 1) / (grid_y - 1)), at the normalised radius rho = |q - c| / |c| from the image centre c = ((w - 1) / 2, (h - 1) / 2).
+ * Limits: 2 <= grid_x <= w, 2 <= grid_y <= h, grid_x grid_y <= 2^22.  The ray a of a sample is q through A's Newton inversion (the one of
+ * the undistorter's points), scaled to unit length; b likewise through B.  The projection difference at a rotation R (row-major, A-camera
+ * rays -> B-camera rays) is d = project(B, R a) - q.  flags: bit 0 A's inversion failed, bit 1 B's did, bit 2 the sample is INVALID -- an
+ * inversion failed, (R a)_z <= 0 (unless B is kb4) or d is not finite --: its d is a NaN pair and it enters no sum.
+ * The IMPLIED rotation is the one the extrinsics would absorb: over the fit set F (both inversions valid, rho <= fit_radius) it minimises
+ * E(R) = sum |d(R)|^2.  Start: Horn's rotation of H = sum_F a b^T.  Then Gauss-Newton with R <- exp(w) R, rows J = -A [R a]x (A = the
+ * 2 x 3 Jacobian of B's projection), w = -(sum J^T J)^-1 sum J^T d; a step that does not lower E is halved, up to 8 times; a sample of F
+ * that is invalid at the current R is left out of that sweep and counted.  status 0: converged -- a Gauss-Newton step of |w| <= 1e-9 rad
+ * (below 3.5e-7 px wherever f (1 + r_u^2) <= 3500), which is taken if it lowers E and is not halved; 1: max_iters reached (<= 0 means 20,
+ * above 100 means 100); 2: no step lowered E, R is the last accepted one.  VC_ERR_NUMERIC: fewer than 3 samples in F, or a 3 x 3 system
+ * without a positive pivot.
+ * A comparer is single-threaded with a stream of its own; nothing is launched before the first run; no CPU fallback.  Argument errors are
+ * VC_ERR_BAD_ARG and come before the device is looked for (VC_ERR_NO_DEVICE).  Every sum is formed in a fixed order that depends on the
+ * lattice alone: two runs, and two handles, give the same bits.  Any output pointer may be NULL. */
+typedef struct vc_comparer vc_comparer;
+int vc_comparer_create(int device, int model_a, const double* params_a, int nparams_a, int model_b, const double* params_b, int nparams_b, int width,
+                       int height, int grid_x, int grid_y, vc_comparer** out);
+/* A = camera `camera` of a calibrator as vc_get_camera returns it (model, intrinsics and size), on the calibrator's device */
+int vc_comparer_create_for_camera(vc_calibrator* h, int camera, int model_b, const double* params_b, int nparams_b, int grid_x, int grid_y, vc_comparer** out);
+void vc_comparer_destroy(vc_comparer* c);
+/* fit_radius > 0: the implied rotation is fitted, then the difference is taken at it.  fit_radius <= 0: no fit; R is R_ba (NULL = identity;
+ * VC_ERR_BAD_ARG unless it is a rotation to 1e-9).  R_ba is not read when there is a fit.  One synchronisation per Gauss-Newton evaluation
+ * and one for the difference sweep. */
+int vc_compare_run(vc_comparer* c, double fit_radius, int max_iters, const double R_ba[9]);
+/* The readers below return VC_ERR_BAD_ARG before a successful run.  cost0 = E(Horn's start), cost = E(R_ba); without a fit status,
+ * iterations, the counts and the costs are zero. */
+int vc_compare_get_fit(vc_comparer* c, double R_ba[9], int* status, int* iterations, int* n_fit, int* n_left_out, double* cost0, double* cost);
+int vc_compare_get_map(vc_comparer* c, double* diff /* grid_y x grid_x x 2 */, unsigned char* flags /* grid_y x grid_x */);
+/* over the valid samples: sum du, sum dv, sum |d|^2, and the largest |d| with its sample -- the lowest sample among those of the largest
+ * |d|^2 = du du + dv dv (both products rounded), -1 without a valid sample */
+int vc_compare_summary(vc_comparer* c, long long* count, long long* invalid, double* sum_du, double* sum_dv, double* sum_sq, double* max_err, long long* worst);
+/* n_rings in [1, 64] arrays: ring k = min(int(rho n_rings), n_rings - 1).  The run bins 8 rings; another count is a rings-only sweep over the
+ * stored d on the device (no inversion, no projection), kept until the next run or another count. */
+int vc_compare_rings(vc_comparer* c, int n_rings, long long* count, long long* invalid, double* sum_sq, double* max_err);
+/* Host code, no device: camera c >= 1 against camera 0 of rigs A and B, p_c = R_rel p_0 + t_rel from each rig's T_ck, centre of c in camera
+ * 0's frame c_X = -R_rel_X^T t_rel_X.  R_0 and R_c (NULL = identity) are the implied rotations of cameras 0 and c.  out4 = the rotation
+ * angle (rad) of R_rel_B^T R_c R_rel_A R_0^T and the distance |c_B - R_0 c_A|, then the same two with R_0 = R_c = I. */
+int vc_compare_extrinsics(const double T_ck_a0[7], const double T_ck_ac[7], const double T_ck_b0[7], const double T_ck_bc[7], const double R_0[9],
+                          const double R_c[9], double out4[4]);
+/* HIP events on the comparer's stream like vc_time_undistort, after a run: average ms of `reps` launches of [0] the rays, [1] one fit sweep,
+ * [2] the difference sweep, each with its reduction. */
+int vc_time_compare(vc_comparer* c, int reps, double out_ms[3]);
+
 #ifdef __cplusplus
 }
 #endif

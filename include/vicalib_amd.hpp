@@ -329,4 +329,61 @@ class Rectifier {
   vc_rectifier* r_ = nullptr;
 };
 
+// Two calibrations of one camera compared in pixel space (vc_compar*): d = project(B, R unproject(A, q)) - q on a lattice over the image, at
+// the implied rotation (fitted over the samples within fit_radius of the centre) or at a given one.
+struct CompareFit { double R_ba[9]; int status = 0, iterations = 0, n_fit = 0, n_left_out = 0; double cost0 = 0, cost = 0; };
+struct CompareSummary { long long count = 0, invalid = 0, worst = -1; double sum_du = 0, sum_dv = 0, sum_sq = 0, max_err = 0; };
+struct CompareRings { std::vector<long long> count, invalid; std::vector<double> sum_sq, max_err; };
+class Comparer {
+ public:
+  // a and b: model, params and size are read (the sizes must agree); the poses are not
+  Comparer(const CameraAndPose& a, const CameraAndPose& b, int grid_x, int grid_y, int device = 0) : gx_(grid_x), gy_(grid_y) {
+    if (a.width != b.width || a.height != b.height) throw std::runtime_error("vicalib_amd: Comparer: the two cameras' image sizes differ");
+    vc_checked(vc_comparer_create(device, a.model, a.params.data(), (int)a.params.size(), b.model, b.params.data(), (int)b.params.size(), a.width, a.height, grid_x,
+                                  grid_y, &c_), "Comparer");
+  }
+  Comparer(ViCalibrator& cal, int camera, const CameraAndPose& b, int grid_x, int grid_y) : gx_(grid_x), gy_(grid_y) {
+    vc_checked(vc_comparer_create_for_camera(cal.handle(), camera, b.model, b.params.data(), (int)b.params.size(), grid_x, grid_y, &c_), "Comparer");
+  }
+  ~Comparer() { vc_comparer_destroy(c_); }
+  Comparer(const Comparer&) = delete;
+  Comparer& operator=(const Comparer&) = delete;
+  // fit_radius <= 0: no fit, the difference at R_ba (nullptr = identity)
+  CompareFit Run(double fit_radius = 0.5, int max_iters = 0, const double* R_ba = nullptr) {
+    vc_checked(vc_compare_run(c_, fit_radius, max_iters, R_ba), "Run");
+    CompareFit f;
+    vc_checked(vc_compare_get_fit(c_, f.R_ba, &f.status, &f.iterations, &f.n_fit, &f.n_left_out, &f.cost0, &f.cost), "Run");
+    return f;
+  }
+  // diff: gy x gx x 2 (a NaN pair at an invalid sample), flags: gy x gx
+  void Map(std::vector<double>* diff, std::vector<unsigned char>* flags) {
+    diff->resize(2 * (size_t)gx_ * gy_); flags->resize((size_t)gx_ * gy_);
+    vc_checked(vc_compare_get_map(c_, diff->data(), flags->data()), "Map");
+  }
+  CompareSummary Summary() {
+    CompareSummary s;
+    vc_checked(vc_compare_summary(c_, &s.count, &s.invalid, &s.sum_du, &s.sum_dv, &s.sum_sq, &s.max_err, &s.worst), "Summary");
+    return s;
+  }
+  CompareRings Rings(int n_rings = 8) {
+    CompareRings r;
+    const size_t n = n_rings > 0 ? (size_t)n_rings : 1;
+    r.count.resize(n); r.invalid.resize(n); r.sum_sq.resize(n); r.max_err.resize(n);
+    vc_checked(vc_compare_rings(c_, n_rings, r.count.data(), r.invalid.data(), r.sum_sq.data(), r.max_err.data()), "Rings");
+    return r;
+  }
+  // host code, no device: [angle, distance] compensated by the implied rotations of cameras 0 and c, then [angle, distance] plain
+  static std::array<double, 4> Extrinsics(const Se3& T_ck_a0, const Se3& T_ck_ac, const Se3& T_ck_b0, const Se3& T_ck_bc, const double* R_0, const double* R_c) {
+    std::array<double, 4> out{{0, 0, 0, 0}};
+    vc_checked(vc_compare_extrinsics(T_ck_a0.data(), T_ck_ac.data(), T_ck_b0.data(), T_ck_bc.data(), R_0, R_c, out.data()), "Extrinsics");
+    return out;
+  }
+  std::array<double, 3> Time(int reps = 20) { std::array<double, 3> ms{{0, 0, 0}}; vc_checked(vc_time_compare(c_, reps, ms.data()), "Time"); return ms; }
+  vc_comparer* handle() { return c_; }
+
+ private:
+  vc_comparer* c_ = nullptr;
+  int gx_ = 0, gy_ = 0;
+};
+
 }  // namespace visual_inertial_calibration

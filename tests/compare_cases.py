@@ -1,0 +1,363 @@
+"""TEST INFRASTRUCTURE shared by test_compare_cpu.py and test_compare_gpu.py: the pairs of calibrations, the numpy side of every comparison
+(oracle_lib.project inverted by bisection on the oracle's radial profile; computed once per camera and kept) and the checks themselves --
+written against plain arrays, so that the same check holds the host build of the comparison's arithmetic
+(tests/host_harness/compare_harness.cpp) and the GPU kernels.
+
+A run is handed to the checks as a dict: R [3, 3], status, iterations, n_fit, n_left_out, cost0, cost; diff [n, 2] and flags [n] in sample
+order; summary (count, invalid, sum_du, sum_dv, sum_sq, max_err, worst); rings {n_rings: dict(count, invalid, sum_sq, max_err)}."""
+import functools
+import os
+import sys
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, HERE)
+import oracle_lib as ol          # noqa: E402
+import undistort_cases as uc     # noqa: E402
+from vicalib_amd import synth    # noqa: E402
+
+SIZE = (640, 480)
+GRID = (53, 41)                                   # 2173 samples: no multiple of 64 or 256, nine workgroups of 256
+R_MAX = 400.0 * 0.745356 * (1 - 0.6 * 0.745356 ** 2)      # 198.76 px: where undistort_cases.BEYOND_K's image ends
+RING_COUNTS = (8, 5, 64)
+FLAG_A, FLAG_B, FLAG_INVALID = 1, 2, 4
+
+
+# ------------------------------------------------------------------------------------------------------------ the oracle's projection
+def project(model, K, rays):
+    """oracle_lib.project of every ray [n, 3] -> [n, 2]: the same function of the oracle, called with buffers that are made once (a reference
+    here takes a quarter of a million projections, and undistort_cases.project spends 30 us of numpy and ctypes set-up on each)"""
+    import ctypes as C
+    L = ol.lib()
+    m = synth.MODEL_IDS[model]
+    rays = np.ascontiguousarray(rays, dtype=np.float64).reshape(-1, 3)
+    K = np.ascontiguousarray(K, dtype=np.float64)
+    out = np.zeros((len(rays), 2)); dray = np.zeros(6); dk = np.zeros(2 * L.vco_model_num_params(m))
+    pK, pr, pk = (C.c_void_p(a.ctypes.data) for a in (K, dray, dk))
+    r0, o0, fn = rays.ctypes.data, out.ctypes.data, L.vco_project
+    for i in range(len(rays)):
+        fn(m, C.c_void_p(r0 + 24 * i), pK, C.c_void_p(o0 + 16 * i), pr, pk)
+    return out
+
+
+def profile(model, K, t):
+    """the oracle's radial profile r_d(t) at unit focal length (fu = fv in every case here), as undistort_cases.profile"""
+    t = np.asarray(t, dtype=np.float64)
+    return (project(model, K, uc.ray_at(model, t, np.zeros_like(t)))[:, 0] - K[2]) / K[0]
+
+
+# ------------------------------------------------------------------------------------------------------------ lattice
+def lattice(size=SIZE, grid=GRID):
+    """(q [n, 2], rho [n]) in sample order s = j gx + i, in the arithmetic of the header: one rounding per product"""
+    (w, h), (gx, gy) = size, grid
+    s = np.arange(gx * gy)
+    i, j = s % gx, s // gx
+    q = np.stack([(i * (w - 1)).astype(np.float64) / (gx - 1), (j * (h - 1)).astype(np.float64) / (gy - 1)], 1)
+    cx, cy = 0.5 * (w - 1), 0.5 * (h - 1)
+    dx, dy = q[:, 0] - cx, q[:, 1] - cy
+    return q, np.sqrt(dx * dx + dy * dy) / np.sqrt(cx * cx + cy * cy)
+
+
+def ring_of(rho, n_rings):
+    return np.minimum((rho * n_rings).astype(int), n_rings - 1)
+
+
+def assert_thresholds_decided(rho, fit_radius, ring_counts=RING_COUNTS):
+    """CPU precondition: no sample within 1e-9 of the fit radius or of a ring boundary (where one rounding of rho could decide) unless it sits
+    ON it: the four samples half-way to the corners have rho = 0.5 with every step of the arithmetic exact (their |q - c|^2 is |c|^2 / 4 without
+    rounding, and sqrt(x / 4) = sqrt(x) / 2).  rho = 1, the image's corners, falls into the last ring whichever way it rounds."""
+    if fit_radius > 0:
+        off = np.abs(rho - fit_radius)
+        assert np.all((off > 1e-9) | (off == 0.0))
+    for n in ring_counts:
+        x = rho * n
+        off = np.abs(x - np.rint(x))[x < n - 0.5]
+        assert np.all((off > 1e-9) | (off == 0.0)), n
+
+
+# ------------------------------------------------------------------------------------------------------------ cameras and cases
+@functools.lru_cache(maxsize=None)
+def t_limit(model, K):
+    """the end of the bracket the bisection starts from: where the oracle's profile stops increasing, at most 3 rad (kb4) or tan = 4"""
+    K = np.array(K)
+    t = np.arange(0.0, 3.0 if model == "kb4" else 4.0, 0.005)
+    r = profile(model, K, t)
+    up = np.nonzero(np.diff(r) <= 0)[0]
+    return float(t[up[0]] if len(up) else t[-1])
+
+
+def assert_increasing(model, K, radius_px, max_inverse_slope=10.0):
+    """CPU precondition for a camera that is inverted: up to `radius_px` about its principal point the oracle's profile is increasing and no
+    flatter than 1 / max_inverse_slope"""
+    K = np.asarray(K)
+    t = np.linspace(0.0, t_limit(model, tuple(K)), 1024)
+    r = profile(model, K, t) * K[0]
+    assert r[-1] >= radius_px, (model, r[-1], radius_px)
+    upto = np.nonzero(r >= radius_px)[0][0] + 1
+    slope = np.diff(r[:upto] / K[0]) / np.diff(t[:upto])
+    assert np.all(slope > 0.0) and np.all(1.0 / slope < max_inverse_slope), (model, slope.min())
+
+
+@functools.lru_cache(maxsize=None)
+def kb4_of_poly3():
+    """a kb4 camera fitted to the lens of the poly3 ground truth: f, k1 .. k4 by scipy on the oracle's radial profile of the poly3 camera, up
+    to 98 % of that profile's maximum; same principal point"""
+    from scipy.optimize import least_squares
+    K3 = uc.gt("poly3")
+    tl = t_limit("poly3", tuple(K3))
+    t = np.linspace(0.0, tl, 2001)
+    r = profile("poly3", K3, t) * K3[0]
+    t = t[: np.nonzero(r >= 0.98 * r.max())[0][0] + 1][1:]
+    r = r[1: len(t) + 1]
+    th = np.arctan(t)
+
+    def res(x):
+        return x[0] * th * (1 + th ** 2 * (x[1] + th ** 2 * (x[2] + th ** 2 * (x[3] + th ** 2 * x[4])))) - r
+
+    x = least_squares(res, np.array([K3[0], 0.0, 0.0, 0.0, 0.0]), xtol=1e-15, ftol=1e-15, gtol=1e-15).x
+    return np.array([x[0], x[0], K3[2], K3[3], x[1], x[2], x[3], x[4]])
+
+
+class Case:
+    """name, cams = ((model, K) of A, (model, K) of B), fit_radius, beyond = which side is BEYOND_K (None, 0 or 1)"""
+
+    def __init__(self, name, a, b, fit_radius, beyond=None):
+        self.name, self.cams, self.fit_radius, self.beyond = name, (a, b), fit_radius, beyond
+
+
+def case_names():
+    return ["same-" + m for m in uc.MODELS] + ["shift", "cross", "beyond", "beyond-mirrored"]
+
+
+@functools.lru_cache(maxsize=None)
+def case(name):
+    p3 = ("poly3", uc.gt("poly3"))
+    if name.startswith("same-"):
+        m = name[5:]
+        return Case(name, (m, uc.gt(m)), (m, uc.gt(m)), 0.5)
+    if name == "shift":
+        return Case(name, p3, ("poly3", uc.gt("poly3") + np.array([0, 0, 3.0, -2.0, 0, 0, 0])), 0.5)
+    if name == "cross":
+        return Case(name, p3, ("kb4", kb4_of_poly3()), 0.5)
+    if name == "beyond":
+        return Case(name, p3, ("poly3", uc.BEYOND_K.copy()), 0.4, beyond=1)
+    if name == "beyond-mirrored":
+        return Case(name, ("poly3", uc.BEYOND_K.copy()), p3, 0.4, beyond=0)
+    raise KeyError(name)
+
+
+# ------------------------------------------------------------------------------------------------------------ numpy reference
+@functools.lru_cache(maxsize=None)
+def _inverted(model, K, size, grid):
+    """oracle-side inverse of every lattice pixel by bisection on the oracle's profile, all pixels at once: unit rays [n, 3] and whether the
+    pixel's radius is inside the profile's range"""
+    K = np.array(K)
+    q, _ = lattice(size, grid)
+    d = (q - K[2:4]) / K[:2]
+    rd = np.hypot(d[:, 0], d[:, 1])
+    hi0 = t_limit(model, tuple(K))
+    inside = rd < profile(model, K, np.array([hi0]))[0]
+    lo, hi = np.zeros(len(rd)), np.full(len(rd), hi0)
+    for _ in range(58):
+        mid = 0.5 * (lo + hi)
+        below = profile(model, K, mid) < rd
+        lo, hi = np.where(below, mid, lo), np.where(below, hi, mid)
+    rays = uc.ray_at(model, 0.5 * (lo + hi), np.arctan2(d[:, 1], d[:, 0]))
+    return rays / np.linalg.norm(rays, axis=1)[:, None], inside
+
+
+class Reference:
+    """of one case on one lattice: q, rho, the unit rays of A, ok_a / ok_b (the inversions), fit (the fit set), undecided (samples whose flags
+    the precondition leaves open)"""
+
+    def __init__(self, c, size, grid):
+        self.c = c
+        self.q, self.rho = lattice(size, grid)
+        (ma, Ka), (mb, Kb) = c.cams
+        self.rays, self.ok_a = _inverted(ma, tuple(Ka), size, grid)
+        _, self.ok_b = _inverted(mb, tuple(Kb), size, grid)
+        self.undecided = np.zeros(len(self.q), dtype=bool)
+        for side, (m, K) in enumerate(c.cams):
+            if c.beyond == side:
+                r = np.hypot(*(self.q - K[2:4]).T)
+                self.undecided |= (r > 0.9 * R_MAX) & (r < 1.01 * R_MAX)
+                assert_increasing(m, K, 0.9 * R_MAX)
+            else:
+                assert_increasing(m, K, np.hypot(*(self.q - K[2:4]).T).max())
+                assert (self.ok_a if side == 0 else self.ok_b).all()
+        assert self.undecided.mean() <= 0.10, self.undecided.mean()
+        self.fit = self.ok_a & self.ok_b & (self.rho <= c.fit_radius)
+        assert self.fit.sum() >= 3 and not (self.fit & self.undecided).any()
+        assert_thresholds_decided(self.rho, c.fit_radius)
+
+    def diff(self, R, mask=None):
+        """(d [n, 2], valid [n]) at R over the samples of `mask` (default: all); d is NaN where not valid"""
+        mb, Kb = self.c.cams[1]
+        both = self.ok_a & self.ok_b if mask is None else mask
+        ra = self.rays @ np.asarray(R).T
+        valid = both & ((ra[:, 2] > 0) | (mb == "kb4"))
+        d = np.full((len(self.q), 2), np.nan)
+        d[valid] = project(mb, Kb, ra[valid]) - self.q[valid]
+        valid &= np.isfinite(d).all(axis=1)
+        d[~valid] = np.nan
+        return d, valid
+
+    def cost(self, R):
+        d, valid = self.diff(R, self.fit)
+        assert valid[self.fit].all()                      # no case here leaves a fit sample out
+        return float(np.sum(d[self.fit] ** 2))
+
+
+@functools.lru_cache(maxsize=None)
+def reference(name, size=SIZE, grid=GRID):
+    return Reference(case(name), size, grid)
+
+
+def angle(R):
+    R = np.asarray(R)
+    v = np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])
+    return float(np.arctan2(0.5 * np.linalg.norm(v), 0.5 * (np.trace(R) - 1.0)))
+
+
+def rot(w):
+    return synth.so3_exp_matrix(np.asarray(w, dtype=np.float64))
+
+
+# ------------------------------------------------------------------------------------------------------------ checks
+def check_map(ref, out):
+    """1. d at the run's own R against the reference at 1e-8 px -- the round-trip bound of the point undistortion: Newton's 1e-14 stop x focal
+    lengths below 500 x inverse slopes below 10, the last two asserted here and in Reference --; flags equal wherever decided; NaN exactly
+    where flagged.  Returns the largest difference."""
+    for m, K in ref.c.cams:
+        assert max(K[0], K[1]) < 500
+    flags, d = np.asarray(out["flags"]), np.asarray(out["diff"])
+    dec = ~ref.undecided
+    assert np.array_equal(((flags & FLAG_A) != 0)[dec], ~ref.ok_a[dec]) and np.array_equal(((flags & FLAG_B) != 0)[dec], ~ref.ok_b[dec])
+    d_ref, valid_ref = ref.diff(out["R"])
+    bad = (flags & FLAG_INVALID) != 0
+    assert np.array_equal(bad[dec], ~valid_ref[dec])
+    assert np.all(bad[(flags & 3) != 0])
+    assert np.isnan(d[bad]).all() and np.isfinite(d[~bad]).all()
+    both = dec & ~bad & valid_ref
+    err = np.abs(d[both] - d_ref[both]).max()
+    print("%s: map differs from the reference by at most %.3g px over %d samples (%d undecided)" % (ref.c.name, err, both.sum(), ref.undecided.sum()))
+    assert err <= 1e-8
+    return err
+
+
+def check_cost(ref, out):
+    """2. the fit's cost against the reference's at the same R"""
+    d, _ = ref.diff(out["R"], ref.fit)
+    e_ref = float(np.sum(d[ref.fit] ** 2))
+    tol = 2e-8 * np.abs(d[ref.fit]).sum() + 1e-12 * e_ref
+    print("%s: cost %.17g, reference %.17g, tolerance %.3g" % (ref.c.name, out["cost"], e_ref, tol))
+    assert out["n_fit"] == ref.fit.sum() and out["n_left_out"] == 0
+    assert abs(out["cost"] - e_ref) <= tol
+
+
+def check_optimal(ref, out):
+    """3. independent of the run's optimiser: the reference's cost rises in all six directions about the run's R, and the run did not end
+    above its start.  The distance to a scipy optimum of the reference's cost is printed."""
+    from scipy.optimize import least_squares
+    e0 = ref.cost(out["R"])
+    for k in range(3):
+        for sgn in (1.0, -1.0):
+            e = ref.cost(rot(sgn * 1e-4 * np.eye(3)[k]) @ out["R"])
+            assert e > e0, (ref.c.name, k, sgn, e, e0)
+    assert out["cost"] <= out["cost0"]
+    sol = least_squares(lambda w: ref.diff(rot(w) @ out["R"], ref.fit)[0][ref.fit].ravel(), np.zeros(3), xtol=1e-14, ftol=1e-15, gtol=1e-14, x_scale=1e-3)
+    print("%s: status %d after %d steps, %.3g rad from the scipy optimum, cost %.6g (start %.6g)" %
+          (ref.c.name, out["status"], out["iterations"], np.linalg.norm(sol.x), out["cost"], out["cost0"]))
+
+
+def check_same(ref, out):
+    """4. a calibration against itself"""
+    assert out["status"] == 0 and angle(out["R"]) <= 1e-10, (out["status"], angle(out["R"]))
+    d = np.asarray(out["diff"])
+    assert np.isfinite(d).all() and np.abs(d).max() <= 1e-8 and np.hypot(d[:, 0], d[:, 1]).max() <= 1e-8
+
+
+def check_shift_plain(ref, out):
+    """5a. no fit: a principal point moved by (3, -2) moves every pixel by (3, -2)"""
+    d = np.asarray(out["diff"])
+    ok = (np.asarray(out["flags"]) & FLAG_INVALID) == 0
+    assert ok.all() and np.abs(d - [3.0, -2.0]).max() <= 1e-8
+    assert out["status"] == 0 and out["iterations"] == 0 and np.array_equal(out["R"], np.eye(3))
+
+
+def check_shift_fitted(ref, out):
+    """5b. with the fit: inside the fit set less than a tenth of sqrt(13) px is left"""
+    d = np.asarray(out["diff"])[ref.fit]
+    rms = np.sqrt(np.mean(np.sum(d ** 2, axis=1)))
+    print("shift: rms %.4f px inside the fit set, implied rotation %.4f deg" % (rms, np.degrees(angle(out["R"]))))
+    assert rms < 0.1 * np.sqrt(13.0)
+
+
+def check_sums(rho, out):
+    """6. summary and rings against numpy over the SAME run's map: sums to 1e-12 relative -- the cancelling ones relative to sum |du| --, the
+    maximum and the counts exactly, `worst` the first of equal maxima (of |d|^2 = du du + dv dv, both products rounded), ring counts adding up"""
+    d, flags = np.asarray(out["diff"]), np.asarray(out["flags"])
+    ok = (flags & FLAG_INVALID) == 0
+    assert np.array_equal(ok, np.isfinite(d).all(axis=1))
+    du, dv = d[ok, 0], d[ok, 1]
+    sq = du * du + dv * dv
+    s = out["summary"]
+    assert s["count"] == ok.sum() and s["invalid"] == (~ok).sum()
+    if not ok.any():
+        assert s["worst"] == -1 and s["max_err"] == 0 and s["sum_sq"] == 0
+    else:
+        assert abs(s["sum_du"] - du.sum()) <= 1e-12 * np.abs(du).sum() and abs(s["sum_dv"] - dv.sum()) <= 1e-12 * np.abs(dv).sum()
+        assert abs(s["sum_sq"] - sq.sum()) <= 1e-12 * sq.sum()
+        assert s["max_err"] == np.sqrt(sq.max())
+        assert s["worst"] == np.nonzero(ok)[0][np.argmax(sq)]
+    for n, r in out["rings"].items():
+        k = ring_of(rho, n)
+        assert r["count"].sum() == s["count"] and r["invalid"].sum() == s["invalid"]
+        for ring in range(n):
+            m = k[ok] == ring
+            assert r["count"][ring] == m.sum() and r["invalid"][ring] == (k[~ok] == ring).sum(), (n, ring)
+            assert abs(r["sum_sq"][ring] - sq[m].sum()) <= 1e-12 * sq[m].sum(), (n, ring)
+            assert r["max_err"][ring] == (np.sqrt(sq[m].max()) if m.any() else 0.0), (n, ring)
+
+
+def check_case(name, run):
+    """Checks 1 - 6 of one case.  run(case, fit_radius, R_ba) -> the dict above, rings at RING_COUNTS."""
+    ref = reference(name)
+    out = run(ref.c, ref.c.fit_radius, None)
+    check_map(ref, out)
+    check_cost(ref, out)
+    check_optimal(ref, out)
+    check_sums(ref.rho, out)
+    if name.startswith("same-"):
+        check_same(ref, out)
+    if name == "shift":
+        check_shift_fitted(ref, out)
+        plain = run(ref.c, 0.0, None)
+        check_shift_plain(ref, plain)
+        check_sums(ref.rho, plain)
+    if ref.c.beyond is not None:
+        assert out["summary"]["invalid"] > 0.5 * len(ref.q)            # most of the lattice has no image in BEYOND_K
+    return out
+
+
+# ------------------------------------------------------------------------------------------------------------ rig files
+XML_TYPES = {"fov": "calibu_fu_fv_u0_v0_w", "poly2": "calibu_fu_fv_u0_v0_k1_k2", "poly3": "calibu_fu_fv_u0_v0_k1_k2_k3", "kb4": "calibu_fu_fv_u0_v0_kb4",
+             "linear": "calibu_fu_fv_u0_v0", "rational6": "calibu_fu_fv_u0_v0_rational6"}
+
+
+def rig_xml(cams, size=SIZE, robotics=False):
+    """a rig file in the layout of vc_write_camera_models, written here so that the CPU tests have one without a calibrator:
+    cams = [(model, K, T_ck)]; T_wc = [R_ck^T RDF^T | -R_ck^T t_ck]"""
+    rdf = np.array([[0, 1, 0], [0, 0, 1], [1, 0, 0]], dtype=np.float64) if robotics else np.eye(3)
+    out = ["<rig>"]
+    for i, (m, K, T) in enumerate(cams):
+        R = synth.quat_to_matrix(np.asarray(T[:4])); t = np.asarray(T[4:], dtype=np.float64)
+        M, tw = R.T @ rdf.T, -R.T @ t
+        vec = lambda v: "[ " + "; ".join("%.17g" % x for x in v) + " ]"      # noqa: E731
+        out += ["  <camera>", '    <camera_model name="" index="%d" serialno="-1" type="%s" version="8">' % (i, XML_TYPES[m]),
+                "      <width> %d </width>" % size[0], "      <height> %d </height>" % size[1],
+                "      <right> %s </right>" % vec(rdf[0]), "      <down> %s </down>" % vec(rdf[1]), "      <forward> %s </forward>" % vec(rdf[2]),
+                "      <params> %s </params>" % vec(K), "    </camera_model>", "    <pose>",
+                "      <T_wc> [ " + "; ".join(", ".join("%.17g" % x for x in list(M[r]) + [tw[r]]) for r in range(3)) + " ] </T_wc>", "    </pose>", "  </camera>"]
+    return "\n".join(out + ["</rig>"]) + "\n"

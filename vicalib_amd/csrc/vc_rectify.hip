@@ -144,16 +144,7 @@ void quat_from_R(const double* R, double* q) {
   const double n = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
   for (int k = 0; k < 4; ++k) q[k] /= n;
 }
-// a finite pose whose quaternion has unit length to 1e-6, normalised
-bool pose_ok(const double* T, double* out) {
-  if (!T) return false;
-  for (int k = 0; k < 7; ++k) if (!std::isfinite(T[k])) return false;
-  const double n = std::sqrt(T[0] * T[0] + T[1] * T[1] + T[2] * T[2] + T[3] * T[3]);
-  if (!(std::fabs(n - 1.0) <= 1e-6)) return false;
-  for (int k = 0; k < 4; ++k) out[k] = T[k] / n;
-  for (int k = 4; k < 7; ++k) out[k] = T[k];
-  return true;
-}
+using vc::pose_ok;
 int rotation_status(int rc) { return rc == vc::kRectOk ? VC_OK : rc == vc::kRectCoincident ? VC_ERR_NUMERIC : VC_ERR_UNSUPPORTED; }
 size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 

@@ -22,6 +22,17 @@ struct RectPlan {
   double baseline;          // signed: e1 . c
 };
 
+// a finite pose whose quaternion has unit length to 1e-6, normalised (host: what the entry points hold a caller's T_ck to)
+inline bool pose_ok(const double* T, double* out) {
+  if (!T) return false;
+  for (int k = 0; k < 7; ++k) if (!std::isfinite(T[k])) return false;
+  const double n = std::sqrt(T[0] * T[0] + T[1] * T[1] + T[2] * T[2] + T[3] * T[3]);
+  if (!(std::fabs(n - 1.0) <= 1e-6)) return false;
+  for (int k = 0; k < 4; ++k) out[k] = T[k] / n;
+  for (int k = 4; k < 7; ++k) out[k] = T[k];
+  return true;
+}
+
 // Rotations of the two cameras into the common rectified frame (rows e1 e2 e3 of R_ds_a; R_ds_b = R_ds_a R^T):
 //   e1 = c / |c|, negated if it points against the summed x axes xm = x + R^T x (b to the left of a: images stay upright),
 //   e2 = normalize(zm x e1) with zm = z + R^T z the summed optical axes, e3 = e1 x e2.

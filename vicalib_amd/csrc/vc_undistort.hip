@@ -93,15 +93,6 @@ __global__ __launch_bounds__(256) void k_undist_points(UndistPlan p, int n, cons
   valid[k] = ok ? 1 : 0;
 }
 
-bool is_rotation(const double* R) {
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) {
-      const double d = R[3 * i] * R[3 * j] + R[3 * i + 1] * R[3 * j + 1] + R[3 * i + 2] * R[3 * j + 2] - (i == j ? 1.0 : 0.0);
-      if (!(std::fabs(d) <= 1e-9)) return false;
-    }
-  const double det = R[0] * (R[4] * R[8] - R[5] * R[7]) - R[1] * (R[3] * R[8] - R[5] * R[6]) + R[2] * (R[3] * R[7] - R[4] * R[6]);
-  return det > 0.0;
-}
 bool model_args_ok(int model, const double* params, int nparams, int w, int h) {
   if (model < 0 || model > 5 || !params || nparams != vc::model_nk(model)) return false;
   if (w < 2 || h < 2 || w > kMaxSize || h > kMaxSize) return false;
@@ -175,7 +166,7 @@ int vc_undistorter_create(int device, int model, const double* params, int npara
                           const double R_ds[9], int fill, vc_undistorter** out) {
   if (!out || !model_args_ok(model, params, nparams, src_w, src_h) || !linear_ok(dst_linear)) return VC_ERR_BAD_ARG;
   if (dst_w < 2 || dst_h < 2 || dst_w > kMaxSize || dst_h > kMaxSize || fill < 0 || fill > 255) return VC_ERR_BAD_ARG;
-  if (R_ds && !is_rotation(R_ds)) return VC_ERR_BAD_ARG;
+  if (R_ds && !vc::is_rotation(R_ds)) return VC_ERR_BAD_ARG;
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess || device < 0 || device >= n) return VC_ERR_NO_DEVICE;      // no CPU fallback
   if (hipSetDevice(device) != hipSuccess) return VC_ERR_NO_DEVICE;

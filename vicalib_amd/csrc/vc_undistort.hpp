@@ -94,6 +94,17 @@ VC_HD bool undist_point(const UndistPlan& p, double u, double v, double* ou, dou
   return true;
 }
 
+// orthonormal to 1e-9 with a positive determinant: what a caller's rotation matrix (row-major) is held to
+inline bool is_rotation(const double* R) {
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) {
+      const double d = R[3 * i] * R[3 * j] + R[3 * i + 1] * R[3 * j + 1] + R[3 * i + 2] * R[3 * j + 2] - (i == j ? 1.0 : 0.0);
+      if (!(std::fabs(d) <= 1e-9)) return false;
+    }
+  const double det = R[0] * (R[4] * R[8] - R[5] * R[7]) - R[1] * (R[3] * R[8] - R[5] * R[6]) + R[2] * (R[3] * R[7] - R[4] * R[6]);
+  return det > 0.0;
+}
+
 }  // namespace vc
 
 // ---- host side of vc_undistort.hip that the rectifier (vc_rectify.hip) builds on; defined there

@@ -40,6 +40,8 @@ SYMBOLS = [
     "vc_undistort_images_device", "vc_undistort_stream", "vc_undistort_points", "vc_undistort_get_map", "vc_undistort_get_linear", "vc_time_undistort",
     "vc_stereo_rectify_rotations", "vc_stereo_fit_linear", "vc_match_tiles", "vc_rectifier_create", "vc_rectifier_create_for_cameras", "vc_rectifier_destroy",
     "vc_rectifier_side", "vc_rectifier_get", "vc_rectify_pairs", "vc_rectify_check", "vc_time_rectify_check",
+    "vc_comparer_create", "vc_comparer_create_for_camera", "vc_comparer_destroy", "vc_compare_run", "vc_compare_get_fit", "vc_compare_get_map",
+    "vc_compare_summary", "vc_compare_rings", "vc_compare_extrinsics", "vc_time_compare",
 ]
 
 
@@ -107,7 +109,7 @@ def load():
         L.vc_holdout_num_corners.restype = C.c_longlong
         L.vc_allreduce_calls.restype = C.c_longlong
         L.vc_last_error.restype = C.c_char_p
-        for name in ("vc_destroy", "vc_detector_destroy", "vc_shard_comm_destroy", "vc_undistorter_destroy", "vc_rectifier_destroy"):
+        for name in ("vc_destroy", "vc_detector_destroy", "vc_shard_comm_destroy", "vc_undistorter_destroy", "vc_rectifier_destroy", "vc_comparer_destroy"):
             getattr(L, name).restype = None
         _lib = L
     return _lib
@@ -880,3 +882,83 @@ class Rectifier:
         ms = C.c_double(0)
         _check(self.L.vc_time_rectify_check(self.h, int(reps), C.byref(ms)), "time_rectify_check")
         return ms.value
+
+
+class Comparer:
+    """Two calibrations of one camera compared in pixel space (include/vicalib_amd.h: vc_compar*): cameras a and b -- (model, params) each -- of
+    the same image `size` = (w, h), sampled on a lattice `grid` = (gx, gy).  run(fit_radius) fits the implied rotation over the samples within
+    that normalised radius (fit_radius <= 0: none, the difference is taken at R_ba) and sweeps the difference d = project(b, R unproject(a, q)) - q;
+    fit(), map(), summary() and rings(n) read the last run; time(reps) -> ms per launch of the rays, one fit sweep and the difference sweep."""
+
+    def __init__(self, cam_a, cam_b, size, grid=(64, 48), device=0, _camera_of=None):
+        self.L = load()
+        self.h = C.c_void_p()
+        mb, Kb = cam_b
+        Kb = np.ascontiguousarray(Kb, dtype=np.float64)
+        if _camera_of is not None:
+            cal, cam = _camera_of
+            _check(self.L.vc_comparer_create_for_camera(cal.h, int(cam), _model_id(mb), _d(Kb), len(Kb), int(grid[0]), int(grid[1]), C.byref(self.h)),
+                   "comparer_create_for_camera")
+        else:
+            ma, Ka = cam_a
+            Ka = np.ascontiguousarray(Ka, dtype=np.float64)
+            _check(self.L.vc_comparer_create(int(device), _model_id(ma), _d(Ka), len(Ka), _model_id(mb), _d(Kb), len(Kb), int(size[0]), int(size[1]),
+                                             int(grid[0]), int(grid[1]), C.byref(self.h)), "comparer_create")
+        self.grid = (int(grid[0]), int(grid[1]))
+
+    @classmethod
+    def for_camera(cls, cal, camera, cam_b, grid=(64, 48)):
+        """Camera a is camera `camera` of a ViCalibrator as GetCamera returns it, with the size it was added with."""
+        return cls(None, cam_b, None, grid, _camera_of=(cal, camera))
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.vc_comparer_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+    def run(self, fit_radius=0.5, max_iters=0, R_ba=None):
+        Rp = None if R_ba is None else _d(np.ascontiguousarray(R_ba, dtype=np.float64).reshape(3, 3))
+        _check(self.L.vc_compare_run(self.h, C.c_double(fit_radius), int(max_iters), Rp), "compare_run")
+        return self.fit()
+
+    def fit(self):
+        R = np.zeros((3, 3)); st, it, nf, nl = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0); c0, c1 = C.c_double(0), C.c_double(0)
+        _check(self.L.vc_compare_get_fit(self.h, _d(R), C.byref(st), C.byref(it), C.byref(nf), C.byref(nl), C.byref(c0), C.byref(c1)), "compare_get_fit")
+        return dict(R=R, status=st.value, iterations=it.value, n_fit=nf.value, n_left_out=nl.value, cost0=c0.value, cost=c1.value)
+
+    def map(self):
+        """-> (d [gy, gx, 2], a NaN pair at an invalid sample; flags [gy, gx] uint8)"""
+        gx, gy = self.grid
+        d = np.zeros((gy, gx, 2)); f = np.zeros((gy, gx), dtype=np.uint8)
+        _check(self.L.vc_compare_get_map(self.h, d.ctypes.data_as(C.c_void_p), f.ctypes.data_as(C.c_void_p)), "compare_get_map")
+        return d, f
+
+    def summary(self):
+        n, bad, w = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
+        su, sv, sq, mx = C.c_double(0), C.c_double(0), C.c_double(0), C.c_double(0)
+        _check(self.L.vc_compare_summary(self.h, C.byref(n), C.byref(bad), C.byref(su), C.byref(sv), C.byref(sq), C.byref(mx), C.byref(w)), "compare_summary")
+        return dict(count=n.value, invalid=bad.value, sum_du=su.value, sum_dv=sv.value, sum_sq=sq.value, max_err=mx.value, worst=w.value)
+
+    def rings(self, n_rings=8):
+        n, bad = np.zeros(n_rings, dtype=np.int64), np.zeros(n_rings, dtype=np.int64)
+        sq, mx = np.zeros(n_rings), np.zeros(n_rings)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)      # noqa: E731
+        _check(self.L.vc_compare_rings(self.h, int(n_rings), p(n), p(bad), p(sq), p(mx)), "compare_rings")
+        return dict(count=n, invalid=bad, sum_sq=sq, max_err=mx)
+
+    @staticmethod
+    def extrinsics(T_ck_a0, T_ck_ac, T_ck_b0, T_ck_bc, R_0=None, R_c=None):
+        """Camera c against camera 0 of rigs a and b (vc_compare_extrinsics; host code, needs no GPU) -> [angle, distance] compensated by the two
+        implied rotations, then [angle, distance] plain."""
+        out = np.zeros(4)
+        Rp = [None if R is None else _d(np.ascontiguousarray(R, dtype=np.float64).reshape(3, 3)) for R in (R_0, R_c)]
+        _check(load().vc_compare_extrinsics(_d(T_ck_a0), _d(T_ck_ac), _d(T_ck_b0), _d(T_ck_bc), Rp[0], Rp[1], _d(out)), "compare_extrinsics")
+        return out
+
+    def time(self, reps=20):
+        out = np.zeros(3)
+        _check(self.L.vc_time_compare(self.h, int(reps), _d(out)), "time_compare")
+        return out
