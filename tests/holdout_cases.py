@@ -88,6 +88,16 @@ def ragged_case():
     return _case(p, tiles, held, seeds)
 
 
+def three_equal_corners(ids, pix, n=130, shift=(3.0, 4.0)):
+    """The first n corners of a view (copies), with corners 0, 65 and n - 1 the same target point seen at the same pixel, `shift` (5 px)
+    off its detection: three bit-equal residuals, the largest of the view, in two lanes and three sweeps of a wavefront."""
+    ids = np.array(ids[:n]); pix = np.array(pix[:n], dtype=np.float64)
+    assert len(ids) == n
+    pix[0] += shift
+    ids[[65, n - 1]] = ids[0]; pix[[65, n - 1]] = pix[0]
+    return ids, pix
+
+
 def all_cases():
     out = [("model-" + m, models_case(m)) for m in ALL_MODELS]
     out += [("rig2", rig_case(("fov", "kb4"))), ("rig3", rig_case(("poly3", "rational6", "linear"))), ("ragged", ragged_case())]

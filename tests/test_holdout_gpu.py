@@ -156,6 +156,29 @@ def test_ragged_frames_in_one_launch_equal_their_one_frame_runs_bit_for_bit():
         np.testing.assert_array_equal(again["views"][k], res["views"][k])
 
 
+def test_the_worst_corner_of_a_held_out_view_is_the_lowest_index_among_equal_ones():
+    """One held-out view of 130 corners (two full sweeps of the wavefront and a tail) of which the first, the 66th and the last are one
+    target point at one pixel 5 px off, against 0.1 px of detection noise: after the refit the three residuals are still bit-equal and
+    the largest (asserted from the returned residuals), and the view's worst corner is the first of them."""
+    base = hc.models_case("poly3")
+    f, c, ids, px = base["tiles"][0]
+    case = dict(base, tiles=[(f, c) + hc.three_equal_corners(ids, px)], n_frames=1, seeds=base["seeds"][:1])
+    cal = _calibrator(case)
+    _add(cal, case)
+    res = cal.HoldoutCompute(case["seeds"], max_iters=100)
+    assert res["frames"]["status"].tolist() == [CONVERGED]
+    r, v = res["r"], res["views"]
+    mag = np.sqrt(r[:, 0] * r[:, 0] + r[:, 1] * r[:, 1])
+    trio = [0, 65, 129]
+    print("planted |r| = %.6f px (x3), largest other %.6f px" % (mag[0], np.delete(mag, trio).max()))
+    assert len(r) == 130 and v["count"].tolist() == [130]
+    np.testing.assert_array_equal(r[trio], np.tile(r[0], (3, 1)))
+    assert np.all(np.delete(mag, trio) < mag[0])
+    assert v["worst_corner"][0] == 0
+    assert abs(v["max_err"][0] - mag[0]) <= 1e-15 * mag[0]            # (the device's square root is specified to 1 ulp)
+    _check_views(res)
+
+
 # ------------------------------------------------------------------------------------------------ 4. flagged frames
 def test_frames_that_cannot_be_fitted_are_flagged_not_fitted():
     base = hc.ragged_case()

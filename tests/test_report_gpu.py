@@ -9,6 +9,7 @@ import sys
 import numpy as np
 import pytest
 
+import holdout_cases as hc
 import oracle_lib as ol
 from vicalib_amd import synth
 from vicalib_amd.lib import ViCalibrator
@@ -169,6 +170,28 @@ def test_corners_views_and_maps_against_the_oracle_at_the_start_and_after_a_solv
         live = rep["camera"] == cam
         s = rep["r"][live].sum(axis=0); sa = np.abs(rep["r"][live]).sum(axis=0)
         assert np.all(np.abs(one["maps"][cam, 0, 0, 1:3] - s) <= live.sum() * EPS * sa)
+
+
+def test_the_worst_corner_of_a_view_is_the_lowest_index_among_equal_ones():
+    """vc_report.hpp's promise for view_worst: one camera, two frames, the first view cut to 130 corners (two full sweeps of the wavefront
+    and a tail) of which the first, the 66th and the last are one target point at one pixel 5 px off -- three bit-equal residuals, the
+    largest of the view at the ground-truth start state (detection noise 0.1 px)."""
+    p = synth.generate(synth.Config(models=("poly3",), n_frames=2, seed=13))
+    f, c, ids, pix = p.tiles[0]
+    p.tiles[0] = (f, c) + hc.three_equal_corners(ids, pix)
+    p.flat = None
+    cal = ViCalibrator(0).load_problem(p, init=False); cal.SetCalibrateImu(False)
+    rep = cal.report()
+    r, v = rep["r"], rep["views"]
+    mag = np.sqrt(r[:, 0] * r[:, 0] + r[:, 1] * r[:, 1])
+    trio = [0, 65, 129]
+    assert (rep["frame"][129], rep["camera"][129]) == (f, c) == (v["frame"][0], v["camera"][0]) and v["count"][0] == 130
+    print("planted |r| = %.6f px (x3), largest other of the view %.6f px" % (mag[0], np.delete(mag[:130], trio).max()))
+    np.testing.assert_array_equal(r[trio], np.tile(r[0], (3, 1)))
+    assert np.all(np.delete(mag[:130], trio) < mag[0])
+    assert v["worst_corner"][0] == 0
+    assert abs(v["max_err"][0] - mag[0]) <= 1e-15 * mag[0]            # (the device's square root: see _check_views)
+    _check_views(rep)
 
 
 def test_reading_needs_a_current_report_and_bins_in_range():

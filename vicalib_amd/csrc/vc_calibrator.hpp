@@ -314,7 +314,7 @@ struct vc_calibrator {
   }
   void init_ctrl(Ctrl* c) {
     std::memset(c, 0, sizeof(Ctrl));
-    c->radius = 1e4; c->decrease_factor = 2.0;
+    c->radius = LmRules::kInitialRadius; c->decrease_factor = LmRules::kInitialDecrease;
     c->ftol = function_tolerance; c->gtol = gradient_tolerance; c->ptol = parameter_tolerance; c->mult = (double)vis_mult;
     c->imu_mult = (double)imu_mult;
     c->cur = cur; c->reuse_diag = 0; c->need_lin = 1; c->init_scale = 1; c->max_iters = max_iters;

@@ -23,6 +23,7 @@
 #include <vector>
 #include "../../include/vicalib_amd.h"
 #include "vc_kutil.hpp"
+#include "vc_hostutil.hpp"
 #include "vc_compare.hpp"
 
 namespace {
@@ -138,12 +139,7 @@ __global__ __launch_bounds__(256) void k_cmp_diff(CmpView v, CmpRot rot, int n_r
   const double s_du = vc::wave_allsum(du), s_dv = vc::wave_allsum(dv), s_q = vc::wave_allsum(sq);
   double best = valid ? sq : -1.0;
   int best_i = valid ? s : -1;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const double ob = __shfl_xor(best, o, 64);
-    const int oi = __shfl_xor(best_i, o, 64);
-    if (ob > best || (ob == best && oi >= 0 && (best_i < 0 || oi < best_i))) { best = ob; best_i = oi; }
-  }
+  vc::wave_argmax_low(&best, &best_i);
   block_stage(s_w, 0, cnt); block_stage(s_w, 1, inv); block_stage(s_w, 2, s_du); block_stage(s_w, 3, s_dv); block_stage(s_w, 4, s_q);
   block_stage(s_w, 5, best); block_stage(s_w, 6, (double)best_i);
   __syncthreads();
@@ -193,8 +189,6 @@ __global__ __launch_bounds__(64) void k_cmp_reduce(const double* __restrict__ pa
     }
   }
 }
-
-size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 }  // namespace
 
@@ -252,9 +246,7 @@ int vc_comparer_create(int device, int model_a, const double* params_a, int npar
                        int grid_x, int grid_y, vc_comparer** out) {
   if (!out || !vc::undist_source_args_ok(model_a, params_a, nparams_a, width, height) || !vc::undist_source_args_ok(model_b, params_b, nparams_b, width, height) ||
       !grid_ok(width, height, grid_x, grid_y)) return VC_ERR_BAD_ARG;
-  int nd = 0;
-  if (hipGetDeviceCount(&nd) != hipSuccess || device < 0 || device >= nd) return VC_ERR_NO_DEVICE;      // no CPU fallback
-  if (hipSetDevice(device) != hipSuccess) return VC_ERR_NO_DEVICE;
+  if (vch::open_device(device) != VC_OK) return VC_ERR_NO_DEVICE;
   vc_comparer* c = new vc_comparer;
   c->device = device;
   std::memset(&c->v, 0, sizeof(c->v)); std::memset(&c->fit, 0, sizeof(c->fit));
@@ -263,17 +255,19 @@ int vc_comparer_create(int device, int model_a, const double* params_a, int npar
   for (int k = 0; k < nparams_a; ++k) p.Ka[k] = params_a[k];
   for (int k = 0; k < nparams_b; ++k) p.Kb[k] = params_b[k];
   vc::model_precompute(model_a, p.Ka, &p.pre_a); vc::model_precompute(model_b, p.Kb, &p.pre_b);
-  const size_t n = (size_t)p.n;
-  const size_t b_rays = up256(n * 24), b_diff = up256(n * 16), b_flags = up256(n), b_part = up256((size_t)c->n_wg() * kDiffDoubles * 8), b_out = up256(kDiffDoubles * 8);
-  if (hipStreamCreate(&c->stream) != hipSuccess || hipMalloc((void**)&c->d_buf, b_rays + b_diff + 2 * b_flags + b_part + b_out) != hipSuccess ||
+  auto carve = [&](vch::Carver q) {
+    const size_t n = (size_t)p.n;
+    c->v.rays = q.take<double>(n * 3);
+    c->v.diff = q.take<double2>(n);
+    c->v.flags0 = q.take<unsigned char>(n);
+    c->v.flags = q.take<unsigned char>(n);
+    c->v.part = q.take<double>((size_t)c->n_wg() * kDiffDoubles);
+    c->v.out = q.take<double>(kDiffDoubles);
+    return q.bytes();
+  };
+  if (hipStreamCreate(&c->stream) != hipSuccess || hipMalloc((void**)&c->d_buf, carve(vch::Carver())) != hipSuccess ||
       hipHostMalloc((void**)&c->h_res, kDiffDoubles * 8, hipHostMallocDefault) != hipSuccess) { vc_comparer_destroy(c); return VC_ERR_NO_DEVICE; }
-  unsigned char* q = c->d_buf;
-  c->v.rays = reinterpret_cast<double*>(q); q += b_rays;
-  c->v.diff = reinterpret_cast<double2*>(q); q += b_diff;
-  c->v.flags0 = q; q += b_flags;
-  c->v.flags = q; q += b_flags;
-  c->v.part = reinterpret_cast<double*>(q); q += b_part;
-  c->v.out = reinterpret_cast<double*>(q);
+  carve(vch::Carver(c->d_buf));
   *out = c;
   return VC_OK;
 }
@@ -407,26 +401,16 @@ int vc_time_compare(vc_comparer* c, int reps, double out_ms[3]) {
   if (!c || reps < 1 || !out_ms || !c->have_run) return VC_ERR_BAD_ARG;
   if (hipSetDevice(c->device) != hipSuccess) return VC_ERR_NO_DEVICE;
   if (c->in_flight) { (void)hipStreamSynchronize(c->stream); c->in_flight = false; }
-  hipEvent_t e0, e1;
-  if (hipEventCreate(&e0) != hipSuccess) return VC_ERR_NO_DEVICE;
-  if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); return VC_ERR_NO_DEVICE; }
-  bool ok = true;
-  for (int what = 0; what < 3 && ok; ++what) {
+  for (int what = 0; what < 3; ++what) {
     auto launch = [&]() {                                          // (each rewrites what the last run left: the same rays, the same map)
       if (what == 0) launch_rays(c, c->rays_radius);
       else if (what == 1) launch_fit(c, c->fit.R, c->fit_radius > 0.0 ? c->fit_radius : 1e300);
       else launch_diff(c, c->fit.R, vc::kCmpDefaultRings, 0);
     };
-    launch();
-    ok = hipEventRecord(e0, c->stream) == hipSuccess;
-    for (int r = 0; r < reps; ++r) launch();
-    float ms = 0.f;
-    ok = ok && hipEventRecord(e1, c->stream) == hipSuccess && hipEventSynchronize(e1) == hipSuccess && hipEventElapsedTime(&ms, e0, e1) == hipSuccess &&
-         hipGetLastError() == hipSuccess;
-    out_ms[what] = (double)ms / reps;
+    const int rc = vch::time_back_to_back(c->stream, reps, launch, &out_ms[what]);
+    if (rc != VC_OK) return rc;
   }
-  (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-  return ok ? VC_OK : VC_ERR_NO_DEVICE;
+  return VC_OK;
 }
 
 }  // extern "C"

@@ -32,6 +32,8 @@
 #include <cstring>
 #include <vector>
 #include "../../include/vicalib_amd.h"
+#include "vc_kutil.hpp"
+#include "vc_hostutil.hpp"
 
 namespace {
 
@@ -234,11 +236,6 @@ __global__ __launch_bounds__(256) void k_det_order(DetView v) {
   for (int j = 0; j < n; ++j) rank += (sc[j] < mine) ? 1 : 0;
   v.cand_sorted[rank] = mine;
 }
-__device__ __forceinline__ double det_wave_sum(double x) {       // all lanes, fixed order
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-  return x;
-}
 // dual conic through the box of candidate c (Ouellet & Hebert): sum over pixels of |g|^2 K K^T theta = -|g|^2 K c^2 with
 // l = (g_x, g_y, c), c = -g . (x - box centre), K = (a^2, a b, b^2, a c, b c); centre = box centre + (theta_3, theta_4) / 2
 __global__ __launch_bounds__(64) void k_det_fit(DetView v) {
@@ -270,7 +267,7 @@ __global__ __launch_bounds__(64) void k_det_fit(DetView v) {
     for (int i = 0; i < 5; ++i) acc[15 + i] += w2 * K[i] * (-(c * c));
   }
 #pragma unroll
-  for (int k = 0; k < 20; ++k) acc[k] = det_wave_sum(acc[k]);
+  for (int k = 0; k < 20; ++k) acc[k] = vc::wave_allsum(acc[k]);      // (all lanes, fixed order)
   if (lane == 0) {
     double M[5][6];
     int e = 0;
@@ -333,9 +330,7 @@ extern "C" {
 
 int vc_detector_create(int device, int width, int height, vc_detector** out) {
   if (!out || width < 8 || height < 8 || (long long)width * height > (1 << 26)) return VC_ERR_BAD_ARG;
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || device < 0 || device >= n) return VC_ERR_NO_DEVICE;      // no CPU fallback
-  if (hipSetDevice(device) != hipSuccess) return VC_ERR_NO_DEVICE;
+  if (vch::open_device(device) != VC_OK) return VC_ERR_NO_DEVICE;
   vc_detector* d = new vc_detector;
   d->device = device; d->w = width; d->h = height;
   const size_t np = (size_t)width * height, out_bytes = kHeadBytes + (size_t)d->max_cand * sizeof(DetRec);
@@ -352,7 +347,7 @@ int vc_detector_create(int device, int width, int height, vc_detector** out) {
 void vc_detector_destroy(vc_detector* d) {
   if (!d) return;
   (void)hipSetDevice(d->device);
-  if (d->stream) (void)hipStreamDestroy(d->stream);
+  if (d->stream) { (void)hipStreamSynchronize(d->stream); (void)hipStreamDestroy(d->stream); }      // (a call that left through an error path may still read the buffers)
   (void)hipFree(d->d_img); (void)hipFree(d->d_S); (void)hipFree(d->d_lab); (void)hipFree(d->d_stats); (void)hipFree(d->d_cand);
   (void)hipFree(d->d_cand_sorted); (void)hipFree(d->d_out);
   if (d->h_out) (void)hipHostFree(d->h_out);

@@ -1,6 +1,6 @@
 #pragma once
 // vc_host.hpp -- what the host driver's translation units share: includes, the HIP_OK macro, device buffers, the packed upload, the
-// target-point table, the run-time bindings of RCCL and roctx.  (The driver itself: vc_calibrator.hpp.)
+// target-point table, the handles' host helpers (vc_hostutil.hpp), the run-time bindings of RCCL and roctx.  (The driver itself: vc_calibrator.hpp.)
 //
 //
 // Mirrors visual_inertial_calibration::ViCalibrator (include/vicalib/vicalibrator.h): the problem
@@ -32,6 +32,7 @@
 #include "vc_pnp.hpp"
 #include "vc_grid.hpp"
 #include "vc_imu.hpp"
+#include "vc_hostutil.hpp"
 
 using namespace vc;
 
@@ -123,13 +124,6 @@ struct Packer {
     launch_unpack((const UnpackSeg*)(dev.p + tab), (int)segs.size(), dev.p, img, s);
     return hipGetLastError();
   }
-};
-
-// a fixed set of timing events, destroyed on every exit path
-template <int N> struct EventSet {
-  hipEvent_t e[N] = {};
-  bool create() { for (int i = 0; i < N; ++i) if (hipEventCreate(&e[i]) != hipSuccess) return false; return true; }
-  ~EventSet() { for (int i = 0; i < N; ++i) if (e[i]) (void)hipEventDestroy(e[i]); }
 };
 
 struct HostCam { int model, nk, width, height; double K[10]; double T_ck[7]; };

@@ -463,14 +463,7 @@ __device__ __forceinline__ void res_tile_sweep(const DevView& v, const TileXf& x
 }
 __device__ __forceinline__ void res_tile_dispatch(const DevView& v, int model, const TileXf& x, const double* K, int off, int cnt,
                                                   int lane, double mult, double* cost, double* sq) {
-  switch (model) {
-    case kFov: res_tile_sweep<kFov>(v, x, K, off, cnt, lane, mult, cost, sq); break;
-    case kPoly2: res_tile_sweep<kPoly2>(v, x, K, off, cnt, lane, mult, cost, sq); break;
-    case kPoly3: res_tile_sweep<kPoly3>(v, x, K, off, cnt, lane, mult, cost, sq); break;
-    case kKb4: res_tile_sweep<kKb4>(v, x, K, off, cnt, lane, mult, cost, sq); break;
-    case kRational6: res_tile_sweep<kRational6>(v, x, K, off, cnt, lane, mult, cost, sq); break;
-    default: res_tile_sweep<kLinear>(v, x, K, off, cnt, lane, mult, cost, sq); break;
-  }
+  with_model(model, [&](auto m) { res_tile_sweep<decltype(m)::value>(v, x, K, off, cnt, lane, mult, cost, sq); });
 }
 // plain sweep of one state buffer (RMSE, vc_evaluate): tile_trial[t] = {mult * sum rho, sum |r|^2}
 __global__ __launch_bounds__(256) void k_reproj_res(DevView v, int state, double mult) {
@@ -484,12 +477,9 @@ __global__ __launch_bounds__(256) void k_reproj_res(DevView v, int state, double
     mult = ct->mult;
   }
   const int f = v.tile_frame[tile], c = v.tile_cam[tile];
-  const double* cam = v.cams[state] + (size_t)c * kCamStride;
   TileXf x;
-  make_tile_xf(v.poses[state] + (size_t)f * kPoseStride, cam, &x);
   double K[10];
-#pragma unroll
-  for (int i = 0; i < 10; ++i) K[i] = cam[kCamK + i];
+  view_setup(v.poses[state] + (size_t)f * kPoseStride, v.cams[state] + (size_t)c * kCamStride, &x, K);
   double cost, sq;
   res_tile_dispatch(v, v.cd[c].model, x, K, v.tile_off[tile], v.tile_off[tile + 1] - v.tile_off[tile], lane, mult, &cost, &sq);
   if (lane == 0) { v.tile_trial[2 * tile] = cost; v.tile_trial[2 * tile + 1] = sq; }
@@ -514,21 +504,11 @@ __global__ __launch_bounds__(256) void k_outlier_mask(DevView v, int state, cons
   if (tile >= v.n_tiles) return;
   const int f = v.tile_frame[tile], c = v.tile_cam[tile];
   const int off = v.tile_off[tile], cnt = v.tile_off[tile + 1] - off;
-  const double* cam = v.cams[state] + (size_t)c * kCamStride;
   TileXf x;
-  make_tile_xf(v.poses[state] + (size_t)f * kPoseStride, cam, &x);
   double K[10];
-#pragma unroll
-  for (int i = 0; i < 10; ++i) K[i] = cam[kCamK + i];
+  view_setup(v.poses[state] + (size_t)f * kPoseStride, v.cams[state] + (size_t)c * kCamStride, &x, K);
   const double th = thresh[c];
-  switch (v.cd[c].model) {
-    case kFov: mask_tile_body<kFov>(v, x, K, off, cnt, lane, th, mask); break;
-    case kPoly2: mask_tile_body<kPoly2>(v, x, K, off, cnt, lane, th, mask); break;
-    case kPoly3: mask_tile_body<kPoly3>(v, x, K, off, cnt, lane, th, mask); break;
-    case kKb4: mask_tile_body<kKb4>(v, x, K, off, cnt, lane, th, mask); break;
-    case kRational6: mask_tile_body<kRational6>(v, x, K, off, cnt, lane, th, mask); break;
-    default: mask_tile_body<kLinear>(v, x, K, off, cnt, lane, th, mask); break;
-  }
+  with_model(v.cd[c].model, [&](auto m) { mask_tile_body<decltype(m)::value>(v, x, K, off, cnt, lane, th, mask); });
 }
 
 // ------------------------------------------------------------------------------------------ frame elimination
@@ -1712,17 +1692,17 @@ __device__ void lm_decide_local(const DevView& v, Ctrl* c, const double* s, bool
     if (R_gmax <= c->gtol) { c->done = kDoneConvergence; return; }
   }
   c->init_scale = 0;
-  // iteration callback (vicalibrator.h:690-721): ++num_iterations_, stop if 0 < |g| < 1e-9
+  // iteration callback (vicalibrator.h:690-721): ++num_iterations_, stop if 0 < |g| < LmRules::kCallbackGnorm
   c->num_callbacks += 1;
-  if (c->last_gnorm > 0.0 && c->last_gnorm < 1e-9) { c->done = kDoneUserSuccess; return; }
+  if (c->last_gnorm > 0.0 && c->last_gnorm < LmRules::kCallbackGnorm) { c->done = kDoneUserSuccess; return; }
   if (c->iter >= c->max_iters) { c->done = kDoneNoConvergence; return; }
   c->iter += 1;
   double rec[kTraceCols] = {(double)c->iter, c->cost, 0.0, c->gmax, c->gnorm, 0.0, 0.0, c->radius, 0.0, (double)c->stage};
   const double model_change = -0.5 * R_gd + 0.5 * R_dld;
   if (fail || !(model_change > 0.0)) {
     c->invalid += 1;
-    if (c->invalid >= 5) { trace_push(v, c, rec, writer); c->done = kDoneFailure; return; }
-    c->radius *= 0.5; rec[7] = c->radius;
+    if (c->invalid >= LmRules::kMaxInvalid) { trace_push(v, c, rec, writer); c->done = kDoneFailure; return; }
+    c->radius *= LmRules::kInvalidShrink; rec[7] = c->radius;
     trace_push(v, c, rec, writer);
     c->need_lin = 0; c->reuse_diag = 1;
     return;
@@ -1734,7 +1714,7 @@ __device__ void lm_decide_local(const DevView& v, Ctrl* c, const double* s, bool
   rec[2] = c->cost - R_new_cost;
   if (fabs(rec[2]) < c->ftol * c->cost) { trace_push(v, c, rec, writer); c->done = kDoneConvergence; return; }
   rec[6] = rec[2] / model_change;
-  if (rec[6] > 1e-3) {
+  if (rec[6] > LmRules::kMinRelativeDecrease) {
     {
       // convergence predictor for the feeding host (vc_solve.cpp: solve_once): quadratic-looking approach to the function tolerance
       const double rel = fabs(rec[2]) / c->cost;
@@ -1743,8 +1723,8 @@ __device__ void lm_decide_local(const DevView& v, Ctrl* c, const double* s, bool
     }
     c->cur = 1 - c->cur;
     const double q = 2.0 * rec[6] - 1.0;
-    c->radius = fmin(1e16, c->radius / fmax(1.0 / 3.0, 1.0 - q * q * q));
-    c->decrease_factor = 2.0;
+    c->radius = fmin(LmRules::kMaxRadius, c->radius / fmax(1.0 / 3.0, 1.0 - q * q * q));
+    c->decrease_factor = LmRules::kInitialDecrease;
     rec[7] = c->radius; rec[8] = 1.0;
     for (int i = 0; i < kTraceCols; ++i) c->pend[i] = rec[i];
     c->pending = 1; c->need_lin = v.fused ? 0 : 1; c->reuse_diag = 0;
@@ -1752,7 +1732,7 @@ __device__ void lm_decide_local(const DevView& v, Ctrl* c, const double* s, bool
     c->radius = c->radius / c->decrease_factor; c->decrease_factor *= 2.0;
     rec[7] = c->radius;
     trace_push(v, c, rec, writer);
-    if (c->radius < 1e-32) { c->done = kDoneConvergence; return; }
+    if (c->radius < LmRules::kMinRadius) { c->done = kDoneConvergence; return; }
     c->need_lin = 0; c->reuse_diag = 1;
   }
 }

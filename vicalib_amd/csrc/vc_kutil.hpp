@@ -63,10 +63,26 @@ __device__ __forceinline__ void wave_sum6(const double* a, double* out, int lane
   out[0] = readlane_f64(d, 0); out[1] = readlane_f64(d, 4); out[2] = readlane_f64(d, 2);
   out[3] = readlane_f64(d, 1); out[4] = readlane_f64(d, 5); out[5] = readlane_f64(d, 3);
 }
-__device__ __forceinline__ double wave_allsum(double x) {   // result in every lane, fixed order
+template <class T>
+__device__ __forceinline__ T wave_allsum(T x) {   // double or int; result in every lane, fixed order (a + b and b + a are the same bits)
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
   return x;
+}
+// The largest `best` of the wavefront and, among equal values, the lowest non-negative `index` (int or long long), in every lane.
+//  - Lane 0 ends with what a __shfl_down tree ending in lane 0 gives: at every step the lanes lane 0's value descends from pair up
+//    with the same partners in the same operand order -- for the sums beside it, (x0 + x32) + (x16 + x48) ..., as for the maximum,
+//    which does not depend on the order at all.
+//  - "the lower index wins a tie" without the test for a negative one is the same rule wherever an index >= 0 goes with a value
+//    >= 0 and the index -1 (a lane without an entry) with the value -1.0: the only state the callers produce.
+template <class I>
+__device__ __forceinline__ void wave_argmax_low(double* best, I* index) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const double ob = __shfl_xor(*best, o, 64);
+    const I oi = __shfl_xor(*index, o, 64);
+    if (ob > *best || (ob == *best && oi >= 0 && (*index < 0 || oi < *index))) { *best = ob; *index = oi; }
+  }
 }
 
 

@@ -12,6 +12,7 @@
 // constant-per-tile rotations are applied after the tile reduction.
 #pragma once
 #include <cmath>
+#include <type_traits>
 
 #if defined(__HIPCC__)
 #define VC_HD __host__ __device__ __forceinline__
@@ -24,6 +25,20 @@ namespace vc {
 // model ids = order of the -models strings (vicalib-engine.cc:203-253)
 enum Model { kFov = 0, kPoly2 = 1, kPoly3 = 2, kKb4 = 3, kLinear = 4, kRational6 = 5 };
 VC_HD int model_nk(int m) { return m == kFov ? 5 : m == kPoly2 ? 6 : m == kPoly3 ? 7 : m == kKb4 ? 8 : m == kLinear ? 4 : m == kRational6 ? 10 : -1; }
+
+// f(std::integral_constant<int, MODEL>) with the run-time model as a compile-time constant: the one place that lists the six models for
+// the sweeps whose body is the same template for all of them (the Jacobian sweep keeps its own switch: jac_tile_dispatch, vc_kernels.hip)
+template <class F>
+VC_HD void with_model(int model, F&& f) {
+  switch (model) {   // wave-uniform on the device
+    case kFov: f(std::integral_constant<int, kFov>()); break;
+    case kPoly2: f(std::integral_constant<int, kPoly2>()); break;
+    case kPoly3: f(std::integral_constant<int, kPoly3>()); break;
+    case kKb4: f(std::integral_constant<int, kKb4>()); break;
+    case kRational6: f(std::integral_constant<int, kRational6>()); break;
+    default: f(std::integral_constant<int, kLinear>()); break;
+  }
+}
 
 constexpr int kPoseStride = 8;    // [qx qy qz qw tx ty tz pad] = 64 B per frame
 constexpr int kCamStride = 24;    // [T_ck(7) pad | K(<=10) pad..]
@@ -341,6 +356,14 @@ VC_HD void make_tile_xf(const double* T_wk, const double* T_ck, TileXf* x) {
     x->tck[i] = T_ck[4 + i];
     x->tcw[i] = T_ck[4 + i] - (x->Rcw[3 * i] * T_wk[4] + x->Rcw[3 * i + 1] * T_wk[5] + x->Rcw[3 * i + 2] * T_wk[6]);
   }
+}
+// a view's prologue: the tile transform of (rig pose, camera record) and the camera's intrinsics
+VC_HD void view_setup(const double* T_wk, const double* cam, TileXf* x, double* K /*10*/) {
+  make_tile_xf(T_wk, cam, x);
+#if defined(__clang__)
+#pragma unroll
+#endif
+  for (int i = 0; i < 10; ++i) K[i] = cam[kCamK + i];
 }
 VC_HD void tile_point(const TileXf& x, const double* pw, double* pc) {
   pc[0] = x.Rcw[0] * pw[0] + x.Rcw[1] * pw[1] + x.Rcw[2] * pw[2] + x.tcw[0];

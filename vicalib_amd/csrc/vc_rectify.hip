@@ -25,6 +25,7 @@
 #include <vector>
 #include "../../include/vicalib_amd.h"
 #include "vc_kutil.hpp"
+#include "vc_hostutil.hpp"
 #include "vc_rectify.hpp"
 
 namespace {
@@ -44,12 +45,6 @@ struct RectView {
   unsigned char* flags;              // n: 1 = invalid pair
   double* stats;                     // n_frames x kStatDoubles
 };
-
-__device__ __forceinline__ int wave_allsum_int(int x) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-  return x;
-}
 
 __global__ __launch_bounds__(256) void k_rectify_check(RectView v) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -80,14 +75,9 @@ __global__ __launch_bounds__(256) void k_rectify_check(RectView v) {
       if (e > best) { best = e; best_i = i; }
     }
   }
-  nv = wave_allsum_int(nv);
+  nv = vc::wave_allsum(nv);
   s_dv = vc::wave_allsum(s_dv); s_dv2 = vc::wave_allsum(s_dv2); s_z = vc::wave_allsum(s_z);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {                           // the same pair in every lane: larger |dv|, then the lower index
-    const double ob = __shfl_xor(best, o, 64);
-    const long long oi = __shfl_xor(best_i, o, 64);
-    if (ob > best || (ob == best && oi >= 0 && (best_i < 0 || oi < best_i))) { best = ob; best_i = oi; }
-  }
+  vc::wave_argmax_low(&best, &best_i);                         // the same pair in every lane: larger |dv|, then the lower index
   // ---- passes 2 - 4: the rigid fit of the triangulated corners onto the target (rotation + translation, NO scale) ------------------
   double rms = nan;
   if (v.target && nv >= 3) {                                   // (wave-uniform: nv is the same in every lane)
@@ -146,7 +136,6 @@ void quat_from_R(const double* R, double* q) {
 }
 using vc::pose_ok;
 int rotation_status(int rc) { return rc == vc::kRectOk ? VC_OK : rc == vc::kRectCoincident ? VC_ERR_NUMERIC : VC_ERR_UNSUPPORTED; }
-size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 }  // namespace
 
@@ -166,24 +155,26 @@ struct vc_rectifier {
 
 namespace {
 
+void carve_check(vch::Carver* c, size_t cp, size_t cf, RectView* v) {
+  v->frame_off = c->take<long long>(cf + 1);
+  v->px_a = c->take<double2>(cp); v->px_b = c->take<double2>(cp);
+  v->target = c->take<double>(cp * 3);
+  v->pairs = c->take<double>(cp * vc::kRectPairDoubles);
+  v->flags = c->take<unsigned char>(cp);
+  v->stats = c->take<double>(cf * kStatDoubles);
+}
 bool reserve_check(vc_rectifier* r, size_t n, size_t nf, RectView* v) {
   if (n > r->cap_pairs || nf > r->cap_frames) {
     const size_t cp = std::max(n, r->cap_pairs), cf = std::max(nf, r->cap_frames);
     (void)hipStreamSynchronize(r->stream);
     (void)hipFree(r->d_buf); r->d_buf = nullptr; r->cap_pairs = r->cap_frames = 0; r->have_last = false;
-    const size_t bytes = up256((cf + 1) * 8) + 2 * up256(cp * 16) + up256(cp * 24) + up256(cp * 48) + up256(cp) + up256(cf * kStatDoubles * 8);
-    if (hipMalloc((void**)&r->d_buf, bytes) != hipSuccess) return false;
+    vch::Carver size;
+    carve_check(&size, cp, cf, v);
+    if (hipMalloc((void**)&r->d_buf, size.bytes()) != hipSuccess) return false;
     r->cap_pairs = cp; r->cap_frames = cf;
   }
-  const size_t cp = r->cap_pairs, cf = r->cap_frames;
-  unsigned char* p = r->d_buf;
-  v->frame_off = reinterpret_cast<const long long*>(p); p += up256((cf + 1) * 8);
-  v->px_a = reinterpret_cast<const double2*>(p); p += up256(cp * 16);
-  v->px_b = reinterpret_cast<const double2*>(p); p += up256(cp * 16);
-  v->target = reinterpret_cast<const double*>(p); p += up256(cp * 24);
-  v->pairs = reinterpret_cast<double*>(p); p += up256(cp * 48);
-  v->flags = p; p += up256(cp);
-  v->stats = reinterpret_cast<double*>(p);
+  vch::Carver at(r->d_buf);
+  carve_check(&at, r->cap_pairs, r->cap_frames, v);
   return true;
 }
 void launch_check(vc_rectifier* r, const RectView& v) {
@@ -384,18 +375,7 @@ int vc_rectify_check(vc_rectifier* r, int n_frames, const long long* frame_off, 
 int vc_time_rectify_check(vc_rectifier* r, int reps, double* out_ms) {
   if (!r || reps < 1 || !out_ms || !r->have_last) return VC_ERR_BAD_ARG;
   if (hipSetDevice(r->device) != hipSuccess) return VC_ERR_NO_DEVICE;
-  hipEvent_t e0, e1;
-  if (hipEventCreate(&e0) != hipSuccess) return VC_ERR_NO_DEVICE;
-  if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); return VC_ERR_NO_DEVICE; }
-  launch_check(r, r->last);                              // warm-up (it rewrites the same results)
-  bool ok = hipEventRecord(e0, r->stream) == hipSuccess;
-  for (int k = 0; k < reps; ++k) launch_check(r, r->last);
-  float ms = 0.f;
-  ok = ok && hipEventRecord(e1, r->stream) == hipSuccess && hipEventSynchronize(e1) == hipSuccess && hipEventElapsedTime(&ms, e0, e1) == hipSuccess &&
-       hipGetLastError() == hipSuccess;
-  *out_ms = (double)ms / reps;
-  (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-  return ok ? VC_OK : VC_ERR_NO_DEVICE;
+  return vch::time_back_to_back(r->stream, reps, [&]() { launch_check(r, r->last); }, out_ms);      // (a launch rewrites the same results)
 }
 
 }  // extern "C"

@@ -17,95 +17,48 @@
 #include "vc_imu.hpp"
 #include "vc_device.h"
 #include "vc_kutil.hpp"
+#include "vc_view.hpp"
 #include "vc_report.hpp"
 
 namespace vc {
 
-// |r|^2 as two rounded products and one rounded sum (no contraction): the number a host restatement of the report forms from (ru, rv)
-__device__ __forceinline__ double report_sq(double ru, double rv) { return __dadd_rn(__dmul_rn(ru, ru), __dmul_rn(rv, rv)); }
-
-template <int MODEL>
-__device__ __forceinline__ void report_tile_body(const DevView& v, const ReportView& rp, const TileXf& x, const double* K, int off, int cnt,
-                                                 int lane, int tile) {
-  ModelPre pre;
-  model_precompute(MODEL, K, &pre);
-  double sq = 0.0, best = -1.0;
-  long long best_i = -1;
-  int marked = 0;
-  for (int d = lane; d < cnt; d += 64) {                     // (ascending d = ascending caller index inside a view: ties keep the lowest)
-    const double2 uv = v.obs_uv[off + d];
-    const int id = v.obs_pt[off + d];
-    const int ci = rp.obs_index[off + d];
-    double r[2];
-    corner_residual<MODEL>(x, K, pre, v.points + 3 * (size_t)(id & kObsPointMask), uv.x, uv.y, r);
-    rp.res[ci] = make_double2(r[0], r[1]);
-    const double s2 = report_sq(r[0], r[1]);
-    sq += s2;
-    const double e = sqrt(s2);
-    if (e > best) { best = e; best_i = ci; }
-    marked += (id & kObsOneLess) ? 1 : 0;
+// a corner of the problem's tile-sorted arrays: u16 point ids that carry the one-copy-fewer mark
+struct ReportCorners {
+  const DevView& v; const int* obs_index;
+  __device__ __forceinline__ ViewCorner operator()(int i) const {
+    const int id = v.obs_pt[i];
+    return {v.obs_uv[i], v.points + 3 * (size_t)(id & kObsPointMask), obs_index[i], (id & kObsOneLess) != 0};
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    sq += __shfl_down(sq, o, 64);
-    marked += __shfl_down(marked, o, 64);
-    const double ob = __shfl_down(best, o, 64);
-    const long long oi = __shfl_down(best_i, o, 64);
-    if (ob > best || (ob == best && oi < best_i)) { best = ob; best_i = oi; }
-  }
-  if (lane == 0) {
-    rp.view_sq[tile] = sq; rp.view_max[tile] = best_i >= 0 ? best : 0.0; rp.view_worst[tile] = best_i; rp.view_marked[tile] = marked;
-  }
-}
+};
 __global__ __launch_bounds__(256) void k_report_vision(DevView v, ReportView rp) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int tile = blockIdx.x * 4 + wave;
   if (tile >= v.n_tiles) return;
   const int f = v.tile_frame[tile], c = v.tile_cam[tile];
   const int off = v.tile_off[tile], cnt = v.tile_off[tile + 1] - off;
-  const double* cam = v.cams[rp.cur] + (size_t)c * kCamStride;
   TileXf x;
-  make_tile_xf(v.poses[rp.cur] + (size_t)f * kPoseStride, cam, &x);
   double K[10];
-#pragma unroll
-  for (int i = 0; i < 10; ++i) K[i] = cam[kCamK + i];
-  switch (v.cd[c].model) {
-    case kFov: report_tile_body<kFov>(v, rp, x, K, off, cnt, lane, tile); break;
-    case kPoly2: report_tile_body<kPoly2>(v, rp, x, K, off, cnt, lane, tile); break;
-    case kPoly3: report_tile_body<kPoly3>(v, rp, x, K, off, cnt, lane, tile); break;
-    case kKb4: report_tile_body<kKb4>(v, rp, x, K, off, cnt, lane, tile); break;
-    case kRational6: report_tile_body<kRational6>(v, rp, x, K, off, cnt, lane, tile); break;
-    default: report_tile_body<kLinear>(v, rp, x, K, off, cnt, lane, tile); break;
-  }
+  view_setup(v.poses[rp.cur] + (size_t)f * kPoseStride, v.cams[rp.cur] + (size_t)c * kCamStride, &x, K);
+  with_model(v.cd[c].model, [&](auto m) {
+    const ViewStats s = view_residuals<decltype(m)::value>(x, K, ReportCorners{v, rp.obs_index}, off, cnt, lane, rp.res);
+    if (lane == 0) { rp.view_sq[tile] = s.sq; rp.view_max[tile] = s.max; rp.view_worst[tile] = s.worst; rp.view_marked[tile] = s.marked; }
+  });
 }
 
-template <int MODEL>
-__device__ __forceinline__ void report_one_corner(const TileXf& x, const double* K, const double* pw, double2 uv, double* r) {
-  ModelPre pre;
-  model_precompute(MODEL, K, &pre);
-  corner_residual<MODEL>(x, K, pre, pw, uv.x, uv.y, r);
-}
 __global__ __launch_bounds__(64) void k_report_dropped(DevView v, ReportView rp) {
   const int i = blockIdx.x * 64 + threadIdx.x;
   if (i >= rp.n_dropped) return;
   const ReportDropped m = rp.dropped[i];
   const double2 uv = rp.dropped_uv[i];
-  const double* cam = v.cams[rp.cur] + (size_t)m.cam * kCamStride;
   TileXf x;
-  make_tile_xf(v.poses[rp.cur] + (size_t)m.frame * kPoseStride, cam, &x);
   double K[10];
-#pragma unroll
-  for (int k = 0; k < 10; ++k) K[k] = cam[kCamK + k];
-  const double* pw = v.points + 3 * (size_t)m.pid;
+  view_setup(v.poses[rp.cur] + (size_t)m.frame * kPoseStride, v.cams[rp.cur] + (size_t)m.cam * kCamStride, &x, K);
   double r[2];
-  switch (v.cd[m.cam].model) {
-    case kFov: report_one_corner<kFov>(x, K, pw, uv, r); break;
-    case kPoly2: report_one_corner<kPoly2>(x, K, pw, uv, r); break;
-    case kPoly3: report_one_corner<kPoly3>(x, K, pw, uv, r); break;
-    case kKb4: report_one_corner<kKb4>(x, K, pw, uv, r); break;
-    case kRational6: report_one_corner<kRational6>(x, K, pw, uv, r); break;
-    default: report_one_corner<kLinear>(x, K, pw, uv, r); break;
-  }
+  with_model(v.cd[m.cam].model, [&](auto mc) {
+    ModelPre pre;
+    model_precompute(decltype(mc)::value, K, &pre);
+    corner_residual<decltype(mc)::value>(x, K, pre, v.points + 3 * (size_t)m.pid, uv.x, uv.y, r);
+  });
   rp.res[m.index] = make_double2(r[0], r[1]);
 }
 
@@ -138,7 +91,7 @@ __global__ __launch_bounds__(64) void k_report_map_part(DevView v, ReportView rp
         const int ce = s_cell[i];
         if ((ce & 63) == lane) {
           const double a = s_r[2 * i], b = s_r[2 * i + 1];
-          slab[4 * ce] += 1.0; slab[4 * ce + 1] += a; slab[4 * ce + 2] += b; slab[4 * ce + 3] += report_sq(a, b);
+          slab[4 * ce] += 1.0; slab[4 * ce + 1] += a; slab[4 * ce + 2] += b; slab[4 * ce + 3] += view_sq(a, b);
         }
       }
       wave_lds_sync();

@@ -19,6 +19,7 @@
 #include <cstring>
 #include <vector>
 #include "../../include/vicalib_amd.h"
+#include "vc_hostutil.hpp"
 #include "vc_undistort.hpp"
 
 namespace {
@@ -146,6 +147,13 @@ bool reserve_images(vc_undistorter* u, int n) {
   return true;
 }
 size_t points_bytes(int n) { return (size_t)n * 33; }
+// a batch of n images at src / dst (host or device), rows and images at the given pitches and strides
+bool images_args_ok(const vc_undistorter* u, int n, const unsigned char* src, int src_pitch, long long src_stride, const unsigned char* dst, int dst_pitch,
+                    long long dst_stride) {
+  if (!u || n < 0 || (n > 0 && (!src || !dst)) || src_pitch < u->p.src_w || dst_pitch < u->p.dst_w) return false;
+  if (n > 1 && (src_stride < (long long)src_pitch * u->p.src_h || dst_stride < (long long)dst_pitch * u->p.dst_h)) return false;
+  return n <= 65535;                                         // (the image index is the grid's y)
+}
 bool reserve_points(vc_undistorter* u, int n) {
   if (n <= u->cap_points) return true;
   (void)hipStreamSynchronize(u->stream);
@@ -164,21 +172,15 @@ extern "C" {
 
 int vc_undistorter_create(int device, int model, const double* params, int nparams, int src_w, int src_h, const double dst_linear[4], int dst_w, int dst_h,
                           const double R_ds[9], int fill, vc_undistorter** out) {
-  if (!out || !model_args_ok(model, params, nparams, src_w, src_h) || !linear_ok(dst_linear)) return VC_ERR_BAD_ARG;
-  if (dst_w < 2 || dst_h < 2 || dst_w > kMaxSize || dst_h > kMaxSize || fill < 0 || fill > 255) return VC_ERR_BAD_ARG;
+  if (!out || !model_args_ok(model, params, nparams, src_w, src_h) || !dst_linear || !vc::undist_dest_args_ok(dst_linear, dst_w, dst_h, fill)) return VC_ERR_BAD_ARG;
   if (R_ds && !vc::is_rotation(R_ds)) return VC_ERR_BAD_ARG;
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || device < 0 || device >= n) return VC_ERR_NO_DEVICE;      // no CPU fallback
-  if (hipSetDevice(device) != hipSuccess) return VC_ERR_NO_DEVICE;
+  if (vch::open_device(device) != VC_OK) return VC_ERR_NO_DEVICE;
   vc_undistorter* u = new vc_undistorter;
   u->device = device;
   UndistPlan& p = u->p;
-  std::memset(&p, 0, sizeof(p));
-  p.model = model; p.src_w = src_w; p.src_h = src_h; p.dst_w = dst_w; p.dst_h = dst_h; p.map_pitch = (dst_w + 3) & ~3; p.fill = fill;
-  for (int k = 0; k < nparams; ++k) p.K[k] = params[k];
-  vc::model_precompute(model, p.K, &p.pre);
+  vc::undist_source_plan(&p, model, params, nparams, src_w, src_h, R_ds);
+  p.dst_w = dst_w; p.dst_h = dst_h; p.map_pitch = (dst_w + 3) & ~3; p.fill = fill;
   for (int k = 0; k < 4; ++k) p.dl[k] = dst_linear[k];
-  for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) p.R_sd[3 * i + j] = R_ds ? R_ds[3 * j + i] : (i == j ? 1.0 : 0.0);
   if (hipStreamCreate(&u->stream) != hipSuccess || hipMalloc((void**)&u->d_map, (size_t)p.map_pitch * dst_h * sizeof(float2)) != hipSuccess) { vc_undistorter_destroy(u); return VC_ERR_NO_DEVICE; }
   launch_map(u);                                     // the map is built once
   if (hipGetLastError() != hipSuccess || hipStreamSynchronize(u->stream) != hipSuccess) { vc_undistorter_destroy(u); return VC_ERR_NO_DEVICE; }
@@ -305,7 +307,7 @@ const vc::UndistPlan& vc::undist_plan_of(const vc_undistorter* u) { return u->p;
 extern "C" {
 
 int vc_undistort_fit_linear(int model, const double* params, int nparams, int src_w, int src_h, int dst_w, int dst_h, double alpha, double dst_linear[4]) {
-  if (!model_args_ok(model, params, nparams, src_w, src_h) || !dst_linear || dst_w < 2 || dst_h < 2 || dst_w > kMaxSize || dst_h > kMaxSize) return VC_ERR_BAD_ARG;
+  if (!model_args_ok(model, params, nparams, src_w, src_h) || !dst_linear || !vc::undist_dest_args_ok(nullptr, dst_w, dst_h, 0)) return VC_ERR_BAD_ARG;
   if (!(alpha >= 0.0 && alpha <= 1.0)) return VC_ERR_BAD_ARG;
   UndistPlan p;
   vc::undist_source_plan(&p, model, params, nparams, src_w, src_h, nullptr);
@@ -314,9 +316,7 @@ int vc_undistort_fit_linear(int model, const double* params, int nparams, int sr
 
 int vc_undistort_images_device(vc_undistorter* u, int n, const unsigned char* d_src, int src_pitch, long long src_stride, unsigned char* d_dst, int dst_pitch,
                                long long dst_stride) {
-  if (!u || n < 0 || (n > 0 && (!d_src || !d_dst)) || src_pitch < u->p.src_w || dst_pitch < u->p.dst_w) return VC_ERR_BAD_ARG;
-  if (n > 1 && (src_stride < (long long)src_pitch * u->p.src_h || dst_stride < (long long)dst_pitch * u->p.dst_h)) return VC_ERR_BAD_ARG;
-  if (n > 65535) return VC_ERR_BAD_ARG;                       // (the image index is the grid's y)
+  if (!images_args_ok(u, n, d_src, src_pitch, src_stride, d_dst, dst_pitch, dst_stride)) return VC_ERR_BAD_ARG;
   if (n == 0) return VC_OK;
   if (hipSetDevice(u->device) != hipSuccess) return VC_ERR_NO_DEVICE;
   launch_remap(u, n, d_src, src_pitch, (size_t)src_stride, d_dst, dst_pitch, (size_t)dst_stride);
@@ -327,9 +327,7 @@ int vc_undistort_images_device(vc_undistorter* u, int n, const unsigned char* d_
 // vc_undistort_images in two halves, so that a rectifier (vc_rectify.hip) has both sides' batches in flight before it waits for either:
 // begin stages and enqueues upload, remap and download on the handle's stream; end waits for the stream and hands the pixels out.
 int vc::undist_images_begin(vc_undistorter* u, int n, const unsigned char* src, int src_pitch, long long src_stride, unsigned char* dst, int dst_pitch, long long dst_stride) {
-  if (!u || n < 0 || (n > 0 && (!src || !dst)) || src_pitch < u->p.src_w || dst_pitch < u->p.dst_w) return VC_ERR_BAD_ARG;
-  if (n > 1 && (src_stride < (long long)src_pitch * u->p.src_h || dst_stride < (long long)dst_pitch * u->p.dst_h)) return VC_ERR_BAD_ARG;
-  if (n > 65535) return VC_ERR_BAD_ARG;
+  if (!images_args_ok(u, n, src, src_pitch, src_stride, dst, dst_pitch, dst_stride)) return VC_ERR_BAD_ARG;
   if (n == 0) return VC_OK;
   if (hipSetDevice(u->device) != hipSuccess) return VC_ERR_NO_DEVICE;
   // one call in flight per handle (the staging buffers and the stream belong to it), as for a detector
@@ -418,26 +416,16 @@ int vc_time_undistort(vc_undistorter* u, int n_images, int reps, double out_ms[3
   }
   if (hipMemcpyAsync(u->d_src, u->h_src, u->src_bytes() * n_images, hipMemcpyHostToDevice, u->stream) != hipSuccess ||
       hipMemcpyAsync(u->d_pts, u->h_pts, (size_t)kTimePoints * 16, hipMemcpyHostToDevice, u->stream) != hipSuccess) return VC_ERR_NO_DEVICE;
-  hipEvent_t e0, e1;
-  if (hipEventCreate(&e0) != hipSuccess) return VC_ERR_NO_DEVICE;
-  if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); return VC_ERR_NO_DEVICE; }
-  bool ok = true;
-  for (int what = 0; what < 3 && ok; ++what) {
-    auto launch = [&]() {
+  for (int what = 0; what < 3; ++what) {
+    auto launch = [&]() {                              // (the map a launch rewrites is the same map)
       if (what == 0) launch_map(u);
       else if (what == 1) launch_remap(u, n_images, u->d_src, u->p.src_w, u->src_bytes(), u->d_dst, u->p.map_pitch, u->dst_bytes());
       else launch_points(u, kTimePoints);
     };
-    launch();                                          // warm-up (the map it rewrites is the same map)
-    ok = hipEventRecord(e0, u->stream) == hipSuccess;
-    for (int r = 0; r < reps; ++r) launch();
-    float ms = 0.f;
-    ok = ok && hipEventRecord(e1, u->stream) == hipSuccess && hipEventSynchronize(e1) == hipSuccess && hipEventElapsedTime(&ms, e0, e1) == hipSuccess &&
-         hipGetLastError() == hipSuccess;
-    out_ms[what] = (double)ms / reps;
+    const int rc = vch::time_back_to_back(u->stream, reps, launch, &out_ms[what]);
+    if (rc != VC_OK) return rc;
   }
-  (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-  return ok ? VC_OK : VC_ERR_NO_DEVICE;
+  return VC_OK;
 }
 
 }  // extern "C"

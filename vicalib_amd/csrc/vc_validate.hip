@@ -14,8 +14,9 @@
 //                        floating-point atomic -- two runs, and a frame alone or among others, give the same bits.
 //                        Step: (H + D / radius) delta = -g with D = clamp(diag H) (lm_clamped_diag, no Jacobi scaling: six
 //                        parameters of one pose), 6 x 6 Cholesky in registers, trial pose by se3_plus, trial cost by a second sweep
-//                        (project_any<false>).  Accept / reject / radius: the rules of lm_decide_local (vc_kernels.hip), restated in
-//                        HoldoutLm below.  A corner at depth <= 0 at the iterate enters no sum of that sweep and is counted.
+//                        (project_any<false>).  Accept / reject / radius: the rules of lm_decide_local (vc_kernels.hip), with
+//                        the solver's own constants (LmRules, vc_device.h).  A corner at depth <= 0 at the iterate enters no sum of that
+//                        sweep and is counted.
 //  k_validate_residuals  one wavefront per held-out (frame, camera) tile at the refined poses, in the manner of k_report_vision:
 //                        (ru, rv) per corner at its place in the caller's order, per view sum |r|^2 (no contraction), max |r| and
 //                        the corner that has it.
@@ -23,34 +24,12 @@
 #include "vc_math.hpp"
 #include "vc_device.h"
 #include "vc_kutil.hpp"
+#include "vc_view.hpp"
 #include "vc_validate.hpp"
 
 namespace vc {
 
-// The trust-region constants of the solver's loop, as lm_decide_local (vc_kernels.hip) and init_ctrl (vc_calibrator.hpp) have them:
-// the Ceres Levenberg-Marquardt rules the project restates.
-struct HoldoutLm {
-  static constexpr double kInitialRadius = 1e4;            // init_ctrl: c->radius
-  static constexpr double kInitialDecrease = 2.0;          // init_ctrl / lm_decide_local: c->decrease_factor, doubled by every rejection
-  static constexpr double kMinRelativeDecrease = 1e-3;     // lm_decide_local: rec[6] > 1e-3 accepts
-  static constexpr double kMaxRadius = 1e16, kMinRadius = 1e-32;
-  static constexpr double kInvalidShrink = 0.5;            // a step without a factorisation or a model decrease: radius *= 0.5
-  static constexpr int kMaxInvalid = 5;                    // ... five in a row end the solve as a failure
-};
-
 constexpr int kHoAcc = 28;      // 21 (upper triangle of J^T W J, row by row) + 6 (J^T W r) + 1 (sum rho)
-
-// every lane ends with the sum over the wave, formed in the same order in every lane (a + b and b + a are the same bits)
-__device__ __forceinline__ double wave_sum_all(double x) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-  return x;
-}
-__device__ __forceinline__ int wave_sum_all(int x) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-  return x;
-}
 
 // One tile's corners into the lane's sums.  JAC: the linearisation (acc[0..27]); otherwise the cost alone (acc[27]).
 template <int MODEL, bool JAC>
@@ -106,28 +85,19 @@ __device__ __forceinline__ double validate_sweep(const HoldoutView& h, int t0, i
     const int off = h.tile_off[t], cnt = h.tile_off[t + 1] - off;
     const double* cam = h.cams + (size_t)c * kCamStride;
     TileXf x;
-    make_tile_xf(T, cam, &x);
     double Rck[9], K[10];
+    view_setup(T, cam, &x, K);
     quat_to_R(cam, Rck);
-#pragma unroll
-    for (int i = 0; i < 10; ++i) K[i] = cam[kCamK + i];
-    switch (h.model[c]) {
-      case kFov: validate_tile_body<kFov, JAC>(h, x, Rck, K, off, cnt, lane, acc, &behind); break;
-      case kPoly2: validate_tile_body<kPoly2, JAC>(h, x, Rck, K, off, cnt, lane, acc, &behind); break;
-      case kPoly3: validate_tile_body<kPoly3, JAC>(h, x, Rck, K, off, cnt, lane, acc, &behind); break;
-      case kKb4: validate_tile_body<kKb4, JAC>(h, x, Rck, K, off, cnt, lane, acc, &behind); break;
-      case kRational6: validate_tile_body<kRational6, JAC>(h, x, Rck, K, off, cnt, lane, acc, &behind); break;
-      default: validate_tile_body<kLinear, JAC>(h, x, Rck, K, off, cnt, lane, acc, &behind); break;
-    }
+    with_model(h.model[c], [&](auto m) { validate_tile_body<decltype(m)::value, JAC>(h, x, Rck, K, off, cnt, lane, acc, &behind); });
   }
   if (JAC) {
 #pragma unroll
-    for (int i = 0; i < 21; ++i) Hu[i] = wave_sum_all(acc[i]);
+    for (int i = 0; i < 21; ++i) Hu[i] = wave_allsum(acc[i]);
 #pragma unroll
-    for (int i = 0; i < 6; ++i) g[i] = wave_sum_all(acc[21 + i]);
+    for (int i = 0; i < 6; ++i) g[i] = wave_allsum(acc[21 + i]);
   }
-  *behind_out = wave_sum_all(behind);
-  return 0.5 * wave_sum_all(acc[27]);
+  *behind_out = wave_allsum(behind);
+  return 0.5 * wave_allsum(acc[27]);
 }
 
 __device__ __forceinline__ double max_abs6(const double* g) {
@@ -156,7 +126,7 @@ __global__ __launch_bounds__(256) void k_validate_pose(HoldoutView h) {
   } else {
     // every quantity below is the same in all 64 lanes (the sweeps end in all-lane sums): the control flow is wave-uniform
     double Hu[21], g[6];
-    double radius = HoldoutLm::kInitialRadius, decrease = HoldoutLm::kInitialDecrease;
+    double radius = LmRules::kInitialRadius, decrease = LmRules::kInitialDecrease;
     int invalid = 0;
     cost0 = cost = validate_sweep<true>(h, t0, t1, T, lane, Hu, g, &behind);
     status = kHoMaxIters;
@@ -186,8 +156,8 @@ __global__ __launch_bounds__(256) void k_validate_pose(HoldoutView h) {
         model_change = -0.5 * gd + 0.5 * dld;
       }
       if (!ok || !(model_change > 0.0)) {                        // (NaN fails the comparison too)
-        if (++invalid >= HoldoutLm::kMaxInvalid) { status = kHoFailed; break; }
-        radius *= HoldoutLm::kInvalidShrink;
+        if (++invalid >= LmRules::kMaxInvalid) { status = kHoFailed; break; }
+        radius *= LmRules::kInvalidShrink;
         continue;
       }
       invalid = 0;
@@ -204,17 +174,17 @@ __global__ __launch_bounds__(256) void k_validate_pose(HoldoutView h) {
       const double change = cost - cost_n;
       if (finite && fabs(change) < h.ftol * cost) { status = kHoConverged; break; }
       const double quality = change / model_change;
-      if (finite && quality > HoldoutLm::kMinRelativeDecrease) {
+      if (finite && quality > LmRules::kMinRelativeDecrease) {
 #pragma unroll
         for (int i = 0; i < 7; ++i) T[i] = Tn[i];
         const double q = 2.0 * quality - 1.0;
-        radius = fmin(HoldoutLm::kMaxRadius, radius / fmax(1.0 / 3.0, 1.0 - q * q * q));
-        decrease = HoldoutLm::kInitialDecrease;
+        radius = fmin(LmRules::kMaxRadius, radius / fmax(1.0 / 3.0, 1.0 - q * q * q));
+        decrease = LmRules::kInitialDecrease;
         cost = validate_sweep<true>(h, t0, t1, T, lane, Hu, g, &behind);      // (the cost of the linearisation point, as the solver keeps it)
         if (max_abs6(g) <= h.gtol) { status = kHoConverged; break; }
       } else {                                                   // rejected (a non-finite trial cost included): more damping
         radius = radius / decrease; decrease *= 2.0;
-        if (radius < HoldoutLm::kMinRadius) { status = kHoConverged; break; }
+        if (radius < LmRules::kMinRadius) { status = kHoConverged; break; }
       }
     }
   }
@@ -228,35 +198,11 @@ __global__ __launch_bounds__(256) void k_validate_pose(HoldoutView h) {
 }
 
 // ------------------------------------------------------------------------------------------ residual sweep
-// |r|^2 as two rounded products and one rounded sum (no contraction): the number a host restatement forms from (ru, rv)
-__device__ __forceinline__ double validate_sq(double ru, double rv) { return __dadd_rn(__dmul_rn(ru, ru), __dmul_rn(rv, rv)); }
-
-template <int MODEL>
-__device__ __forceinline__ void validate_res_body(const HoldoutView& h, const TileXf& x, const double* K, int off, int cnt, int lane, int tile) {
-  ModelPre pre;
-  model_precompute(MODEL, K, &pre);
-  double sq = 0.0, best = -1.0;
-  long long best_i = -1;
-  for (int d = lane; d < cnt; d += 64) {                     // (ascending d = ascending caller index inside a view: ties keep the lowest)
-    const double2 uv = h.obs_uv[off + d];
-    const int ci = h.obs_index[off + d];
-    double r[2];
-    corner_residual<MODEL>(x, K, pre, h.points + 3 * (size_t)h.obs_pt[off + d], uv.x, uv.y, r);
-    h.res[ci] = make_double2(r[0], r[1]);
-    const double s2 = validate_sq(r[0], r[1]);
-    sq += s2;
-    const double e = sqrt(s2);
-    if (e > best) { best = e; best_i = ci; }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    sq += __shfl_down(sq, o, 64);
-    const double ob = __shfl_down(best, o, 64);
-    const long long oi = __shfl_down(best_i, o, 64);
-    if (ob > best || (ob == best && oi < best_i)) { best = ob; best_i = oi; }
-  }
-  if (lane == 0) { h.view_sq[tile] = sq; h.view_max[tile] = best_i >= 0 ? best : 0.0; h.view_worst[tile] = best_i; }
-}
+// a corner of the hold-out set's tile-sorted arrays: plain point ids, never marked
+struct HoldoutCorners {
+  const HoldoutView& h;
+  __device__ __forceinline__ ViewCorner operator()(int i) const { return {h.obs_uv[i], h.points + 3 * (size_t)h.obs_pt[i], h.obs_index[i], false}; }
+};
 __global__ __launch_bounds__(256) void k_validate_residuals(HoldoutView h) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int tile = blockIdx.x * 4 + wave;
@@ -268,20 +214,13 @@ __global__ __launch_bounds__(256) void k_validate_residuals(HoldoutView h) {
     if (lane == 0) { h.view_sq[tile] = 0.0; h.view_max[tile] = 0.0; h.view_worst[tile] = -1; }
     return;
   }
-  const double* cam = h.cams + (size_t)c * kCamStride;
   TileXf x;
-  make_tile_xf(h.pose + (size_t)f * kPoseStride, cam, &x);
   double K[10];
-#pragma unroll
-  for (int i = 0; i < 10; ++i) K[i] = cam[kCamK + i];
-  switch (h.model[c]) {
-    case kFov: validate_res_body<kFov>(h, x, K, off, cnt, lane, tile); break;
-    case kPoly2: validate_res_body<kPoly2>(h, x, K, off, cnt, lane, tile); break;
-    case kPoly3: validate_res_body<kPoly3>(h, x, K, off, cnt, lane, tile); break;
-    case kKb4: validate_res_body<kKb4>(h, x, K, off, cnt, lane, tile); break;
-    case kRational6: validate_res_body<kRational6>(h, x, K, off, cnt, lane, tile); break;
-    default: validate_res_body<kLinear>(h, x, K, off, cnt, lane, tile); break;
-  }
+  view_setup(h.pose + (size_t)f * kPoseStride, h.cams + (size_t)c * kCamStride, &x, K);
+  with_model(h.model[c], [&](auto m) {
+    const ViewStats s = view_residuals<decltype(m)::value>(x, K, HoldoutCorners{h}, off, cnt, lane, h.res);
+    if (lane == 0) { h.view_sq[tile] = s.sq; h.view_max[tile] = s.max; h.view_worst[tile] = s.worst; }
+  });
 }
 
 // ------------------------------------------------------------------------------------------ launchers
