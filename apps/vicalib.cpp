@@ -144,6 +144,13 @@ static void DefineFlags() {
   Define("compare_grid", "string", "64x48", "Lattice of the comparison, GXxGY: 2 ... image width by 2 ... image height, at most 2^22 samples.");
   Define("compare_fit_radius", "double", "0.5", "The implied rotation is fitted over the samples within this fraction of the half-diagonal of the image centre (> 0).");
   Define("compare_rings", "int32", "8", "Rings of equal width in normalised radius in compare_summary.csv, 1 ... 64.");
+  // a calibrated camera converted to another camera model (vc_convert*): off unless asked for
+  Define("convert_models", "string", "", "in.xml: convert the cameras of this rig file to the models of -convert_to into -convert_output; needs no -cam, nothing is calibrated.");
+  Define("convert_to", "string", "", "m[,m...]: target model(s) of the conversion, one for all cameras or one per camera.  Without -convert_models the calibration just computed "
+         "is converted.  With -compare_dir the original is also compared with the converted cameras, at the identity rotation.");
+  Define("convert_output", "string", "converted.xml", "Rig file of the converted cameras: every camera keeps its pose and size.");
+  Define("convert_grid", "string", "64x48", "Lattice of the conversion, GXxGY: 2 ... image width by 2 ... image height, at most 2^22 samples.");
+  Define("convert_fit_radius", "double", "1", "The target model is fitted over the samples within this fraction of the half-diagonal of the image centre (> 0; 1 = the whole image).");
 }
 
 static int Usage(int code) {
@@ -692,7 +699,7 @@ static bool ParseCompareGrid(const std::string& s, int* gx, int* gy) {
   *gx = a; *gy = b;
   return true;
 }
-struct CompareOptions { std::string dir; int gx = 64, gy = 48, rings = 8; double fit_radius = 0.5; };
+struct CompareOptions { std::string dir; int gx = 64, gy = 48, rings = 8; double fit_radius = 0.5; bool identity = false; };      // identity: no implied rotation is fitted
 // the flags of a comparison, checked before anything else runs
 static bool CompareFlags(CompareOptions* o, std::string* err) {
   o->dir = FlagString("compare_dir");
@@ -739,7 +746,7 @@ static int CompareRigs(const std::vector<vic::CameraAndPose>& A, const std::vect
     std::vector<unsigned char> fl(n);
     vic::CompareFit fit;
     vic::CompareSummary s, sp;
-    int q = vc_compare_run(h, o.fit_radius, 0, nullptr);
+    int q = vc_compare_run(h, o.identity ? 0.0 : o.fit_radius, 0, nullptr);
     if (q == VC_OK) q = vc_compare_get_fit(h, fit.R_ba, &fit.status, &fit.iterations, &fit.n_fit, &fit.n_left_out, &fit.cost0, &fit.cost);
     if (q == VC_OK) q = vc_compare_get_map(h, d.data(), fl.data());
     if (q == VC_OK) q = vc_compare_summary(h, &s.count, &s.invalid, &s.sum_du, &s.sum_dv, &s.sum_sq, &s.max_err, &s.worst);
@@ -800,6 +807,104 @@ static int CompareRigs(const std::vector<vic::CameraAndPose>& A, const std::vect
   return rc;
 }
 
+// ---- -convert_models / -convert_to: calibrated cameras converted to other camera models (vc_convert*) ------------------------------------
+static const char* ModelXmlType(int id) {
+  static const char* n[] = {"calibu_fu_fv_u0_v0_w", "calibu_fu_fv_u0_v0_k1_k2", "calibu_fu_fv_u0_v0_k1_k2_k3", "calibu_fu_fv_u0_v0_kb4", "calibu_fu_fv_u0_v0", "calibu_fu_fv_u0_v0_rational6"};
+  return (id >= 0 && id < 6) ? n[id] : "?";
+}
+struct ConvertOptions { std::string output; std::vector<int> models; int gx = 64, gy = 48; double fit_radius = 1.0; };
+// the flags of a conversion, checked before anything else runs
+static bool ConvertFlags(ConvertOptions* o, std::string* err) {
+  const std::string to = FlagString("convert_to");
+  if (to.empty()) { *err = "-convert_models needs -convert_to"; return false; }
+  o->models.clear();
+  for (size_t from = 0; from <= to.size();) {
+    const size_t comma = std::min(to.find(',', from), to.size());
+    const std::string name = to.substr(from, comma - from);
+    const int id = ModelId(name);
+    if (id < 0) { *err = "illegal value '" + to + "' specified for flag 'convert_to': expected fov, poly2, poly3, kb4, linear or rational6, one for all cameras or one per camera"; return false; }
+    o->models.push_back(id);
+    from = comma + 1;
+  }
+  o->output = FlagString("convert_output");
+  if (o->output.empty()) { *err = "illegal value for flag 'convert_output': expected a file name"; return false; }
+  if (!ParseCompareGrid(FlagString("convert_grid"), &o->gx, &o->gy)) { *err = "illegal value '" + FlagString("convert_grid") + "' specified for flag 'convert_grid': expected GXxGY, both at least 2, at most 2^22 samples"; return false; }
+  o->fit_radius = FlagDouble("convert_fit_radius");
+  if (!(o->fit_radius > 0.0 && o->fit_radius <= 1e6)) { *err = "illegal value for flag 'convert_fit_radius': expected a radius above 0"; return false; }
+  return true;
+}
+// what can be said about the cameras before a device is looked for
+static bool ConvertibleRig(const std::vector<vic::CameraAndPose>& cams, const ConvertOptions& o, std::string* err) {
+  if (o.models.size() != 1 && o.models.size() != cams.size()) {
+    *err = "illegal value for flag 'convert_to': " + std::to_string(o.models.size()) + " models for " + std::to_string(cams.size()) + " cameras (expected one, or one per camera)"; return false;
+  }
+  for (size_t c = 0; c < cams.size(); ++c)
+    if (o.gx > cams[c].width || o.gy > cams[c].height) { *err = "camera " + std::to_string(c) + ": -convert_grid exceeds the image"; return false; }
+  return true;
+}
+// Converts the cameras of the rig file `path` (read into `cams`) and writes -convert_output: the file's own text with every camera's model type and
+// <params> replaced -- poses, sizes and axes stay as they are written.  Then, with `compare`, the comparison of the original against the
+// converted cameras.  Exit status: 0, 1 (an error said in *err, or a camera whose fit failed) or 3 (no device).
+static int ConvertRig(const std::string& path, const std::vector<vic::CameraAndPose>& cams, const ConvertOptions& o, const CompareOptions* compare, int device, std::string* err) {
+  if (!ConvertibleRig(cams, o, err)) return 1;
+  std::ifstream f(path);
+  if (!f) { *err = "cannot open rig file " + path; return 1; }
+  std::stringstream ss; ss << f.rdbuf();
+  std::string text = ss.str();
+  std::vector<vic::CameraAndPose> converted = cams;
+  std::vector<std::string> lines;
+  bool failed = false;
+  size_t from = 0;
+  for (size_t c = 0; c < cams.size(); ++c) {
+    const int model_b = o.models[o.models.size() == 1 ? 0 : c];
+    vc_converter* h = nullptr;
+    const int st_create = vc_converter_create(device, cams[c].model, cams[c].params.data(), (int)cams[c].params.size(), cams[c].width, cams[c].height, model_b, o.gx, o.gy, &h);
+    if (st_create == VC_ERR_NO_DEVICE) { *err = "no HIP device (there is no CPU fallback)"; return 3; }
+    if (st_create != VC_OK) { *err = "camera " + std::to_string(c) + ": the conversion refuses this camera (status " + std::to_string(st_create) + ")"; return 1; }
+    vic::ConvertResult r;
+    int nk = 0;
+    r.params.resize(10);
+    int q = vc_convert_run(h, o.fit_radius, 200, nullptr, 0);
+    if (q == VC_OK) q = vc_convert_get(h, r.params.data(), &nk, &r.status, &r.iterations, &r.n_fit, &r.n_left_out, &r.cost0, &r.cost, &r.max_err, &r.worst);
+    vc_converter_destroy(h);
+    if (q != VC_OK) {
+      *err = "camera " + std::to_string(c) + (q == VC_ERR_NUMERIC ? ": the target model cannot be fitted (too few samples within -convert_fit_radius that the camera has a ray for, or a start nothing can be evaluated at)"
+                                                                  : ": the conversion failed (status " + std::to_string(q) + ")");
+      return q == VC_ERR_NO_DEVICE ? 3 : 1;
+    }
+    r.params.resize((size_t)nk);
+    converted[c].model = model_b; converted[c].params = r.params;
+    if (r.status == 2) failed = true;
+    const int used = r.n_fit - r.n_left_out;
+    char line[256];
+    std::snprintf(line, sizeof(line), "camera %zu: %s converted to %s: status %d, %d iterations, %.6g px rms, %.6g px max over %d samples", c, ModelName(cams[c].model),
+                  ModelName(model_b), r.status, r.iterations, used > 0 ? std::sqrt(2.0 * r.cost / used) : 0.0, r.max_err, used);
+    lines.push_back(line);
+    // the c-th <camera> of the text: its type and its parameters
+    const size_t p = text.find("<camera>", from), e = p == std::string::npos ? p : text.find("</camera>", p);
+    const size_t t0 = p == std::string::npos ? p : text.find("type=\"", p), a0 = p == std::string::npos ? p : text.find("<params>", p);
+    const size_t t1 = t0 == std::string::npos ? t0 : text.find('"', t0 + 6), a1 = a0 == std::string::npos ? a0 : text.find("</params>", a0);
+    if (e == std::string::npos || t1 == std::string::npos || a1 == std::string::npos || t1 > e || a1 > e || t1 > a0) { *err = path + ": camera " + std::to_string(c) + " cannot be rewritten"; return 1; }
+    std::string params = "<params> [ ";
+    for (int k = 0; k < nk; ++k) { char num[40]; std::snprintf(num, sizeof(num), "%.17g", r.params[k]); params += num; params += k + 1 < nk ? "; " : " ] "; }
+    text.replace(a0, a1 - a0, params);                            // (the later position first: the earlier one stays valid)
+    text.replace(t0 + 6, t1 - t0 - 6, ModelXmlType(model_b));
+    from = text.find("</camera>", p) + 9;
+  }
+  std::ofstream out(o.output);
+  out << text;
+  out.close();
+  if (!out) { *err = "cannot write " + o.output; return 1; }
+  for (const std::string& l : lines) std::printf("%s\n", l.c_str());
+  std::printf("conversion %s -> %s\n", failed ? "FAILED" : "succeeded", o.output.c_str());
+  if (compare) {
+    const int rc = CompareRigs(cams, converted, *compare, device, err);
+    if (rc != 0) return rc;
+  }
+  if (failed) { *err = "a camera's fit failed (status 2): its parameters are the last accepted point"; return 1; }
+  return 0;
+}
+
 int main(int argc, char** argv) {
   DefineFlags();
   std::string err;
@@ -825,6 +930,25 @@ int main(int argc, char** argv) {
   if (!FlagString("compare_models").empty() || !FlagString("compare_to").empty()) {
     if (!FlagString("compare_models").empty() && !FlagString("compare_to").empty()) { std::fprintf(stderr, "ERROR: -compare_models and -compare_to exclude each other\n"); return 1; }
     if (!CompareFlags(&compare, &err)) { std::fprintf(stderr, "ERROR: %s\n", err.c_str()); return 1; }
+  }
+  // ---- -convert_models in.xml -convert_to m[,m...]: file to file, nothing is calibrated; -convert_to alone: the result is converted behind it
+  ConvertOptions convert;
+  const bool converting = !FlagString("convert_models").empty() || !FlagString("convert_to").empty();
+  if (converting) {
+    if (!FlagString("compare_models").empty() || !FlagString("compare_to").empty()) { std::fprintf(stderr, "ERROR: -convert_models / -convert_to and -compare_models / -compare_to exclude each other\n"); return 1; }
+    if (!ConvertFlags(&convert, &err)) { std::fprintf(stderr, "ERROR: %s\n", err.c_str()); return 1; }
+    if (!FlagString("compare_dir").empty()) {
+      if (!CompareFlags(&compare, &err)) { std::fprintf(stderr, "ERROR: %s\n", err.c_str()); return 1; }
+      compare.identity = true; compare.gx = convert.gx; compare.gy = convert.gy;      // (the conversion's own lattice; -compare_grid is not read)
+    }
+  }
+  if (!FlagString("convert_models").empty()) {
+    std::vector<vic::CameraAndPose> a;
+    if (!ReadRigFile(FlagString("convert_models"), &a, &err)) { std::fprintf(stderr, "F %s\n", err.c_str()); return 1; }
+    if (!ConvertibleRig(a, convert, &err)) { std::fprintf(stderr, "ERROR: %s\n", err.c_str()); return 1; }
+    const int rc = ConvertRig(FlagString("convert_models"), a, convert, compare.identity ? &compare : nullptr, (int)FlagInt("device"), &err);
+    if (rc != 0) std::fprintf(stderr, "%s %s\n", rc == 3 ? "F" : "E conversion failed:", err.c_str());
+    return rc;
   }
   if (!FlagString("compare_models").empty()) {
     const std::string& both = FlagString("compare_models");
@@ -932,6 +1056,7 @@ int main(int argc, char** argv) {
   }
   if (input_cameras.size() < n_cam) { std::fprintf(stderr, "F %zu camera models for %zu channels\n", input_cameras.size(), n_cam); return 1; }
   input_cameras.resize(n_cam);
+  if (converting && !ConvertibleRig(input_cameras, convert, &err)) { std::fprintf(stderr, "ERROR: %s\n", err.c_str()); return 1; }      // before any solve
   if (!compare_b.empty() && !ComparableRigs(input_cameras, compare_b, compare, &err)) { std::fprintf(stderr, "F -compare_to: %s\n", err.c_str()); return 1; }      // before any solve
 
   // ---- frames: union of the frame ids, -frame_skip, -num_vicalib_frames (vicalib-engine.cc:540-590) ---------------------
@@ -1286,6 +1411,13 @@ int main(int argc, char** argv) {
     }
     if (CompareRigs(a, compare_b, compare, (int)FlagInt("device"), &err) != 0) { std::fprintf(stderr, "E comparison failed: %s\n", err.c_str()); compare_failed = true; }
   }
+  bool convert_failed = false;
+  if (converting) {                                      // -convert_to: the cameras just written, converted
+    std::vector<vic::CameraAndPose> a;
+    if (!ReadRigFile(FlagString("output"), &a, &err) || ConvertRig(FlagString("output"), a, convert, compare.identity ? &compare : nullptr, (int)FlagInt("device"), &err) != 0) {
+      std::fprintf(stderr, "E conversion failed: %s\n", err.c_str()); convert_failed = true;
+    }
+  }
   if (FlagBool("print_poses")) {
     if (FILE* f = std::fopen("poses.txt", "w")) {
       for (size_t i = 0; i < all_frames.size(); ++i) { double c[6]; T2Cart(all_frames[i].t_wp_.data(), c); std::fprintf(f, "%f\t%f\t%f\t%f\t%f\t%f\n", c[0], c[1], c[2], c[3], c[4], c[5]); }
@@ -1323,5 +1455,6 @@ int main(int argc, char** argv) {
   if (undistort_failed) std::fprintf(stderr, "E -undistort_dir: the undistorted images are incomplete (exit status %d)\n", success ? 1 : 2);
   if (rectify_failed) std::fprintf(stderr, "E -rectify_dir: the rectification's files are incomplete (exit status %d)\n", success ? 1 : 2);
   if (compare_failed) std::fprintf(stderr, "E -compare_to: the comparison's files are incomplete (exit status %d)\n", success ? 1 : 2);
-  return success ? ((undistort_failed || rectify_failed || compare_failed) ? 1 : 0) : 2;
+  if (convert_failed) std::fprintf(stderr, "E -convert_to: the converted rig is incomplete (exit status %d)\n", success ? 1 : 2);
+  return success ? ((undistort_failed || rectify_failed || compare_failed || convert_failed) ? 1 : 0) : 2;
 }

@@ -526,6 +526,45 @@ int vc_compare_extrinsics(const double T_ck_a0[7], const double T_ck_ac[7], cons
  * [2] the difference sweep, each with its reduction. */
 int vc_time_compare(vc_comparer* c, int reps, double out_ms[3]);
 
+/* ---- converting a calibrated camera to another camera model ---------------------------------------------------------------------------
+ * A rig calibrated with one model handed to a consumer that speaks another, without calibrating again: source camera A (any of the six
+ * models, image w x h), a target model m_b, and the comparer's lattice of grid_x x grid_y samples with its limits.  The ray a_s of sample s
+ * is its pixel q_s through A's Newton inversion, scaled to unit length.  The fit set F holds the samples whose inversion succeeded and whose
+ * rho <= fit_radius (>= 1: the whole image).  The result is the K_b of model m_b that minimises E(K_b) = sum over F of
+ * |project(m_b, K_b, a_s) - q_s|^2.  No rotation, no change of extrinsics: the converted camera sees the same rays, T_ck stays valid.  A sample
+ * of F with a_z <= 0 (unless m_b is kb4) or a d that is not finite is left out of a sweep and counted.
+ * Levenberg-Marquardt on the host over device sweeps, one synchronisation per evaluation, with the rules of the calibration's own loop:
+ * cost E / 2, initial radius 1e4, (H + D) delta = -g with D = clamp(diag H, 1e-6, 1e32) / radius; a step without a factorisation or a model
+ * decrease halves the radius, five in a row end the fit as failed; a trial is accepted above a step quality of 1e-3.  status 0: converged --
+ * |delta| <= 1e-10 (|x_free| + 1e-10) before a trial (the step is not taken), or |cost change| <= 1e-12 cost after an accepted step; 1:
+ * max_iters trials (<= 0 means 50, above 200 means 200); 2: failed (the radius fell below 1e-32, or five invalid steps): K_b is the last
+ * accepted point.  VC_ERR_NUMERIC: 2 n_fit is below the number of free parameters, or the first evaluation is not finite.
+ * A converter is single-threaded with a stream of its own; nothing is launched before the first run; no CPU fallback.  Argument errors are
+ * VC_ERR_BAD_ARG and come before the device is looked for (VC_ERR_NO_DEVICE).  Every sum is formed in a fixed order that depends on the
+ * lattice alone: two runs, and two handles, give the same bits. */
+typedef struct vc_converter vc_converter;
+int vc_converter_create(int device, int model_a, const double* params_a, int nparams_a, int width, int height, int model_b, int grid_x, int grid_y,
+                        vc_converter** out);
+/* A = camera `camera` of a calibrator as vc_get_camera returns it (model, intrinsics and size), on the calibrator's device */
+int vc_converter_create_for_camera(vc_calibrator* h, int camera, int model_b, int grid_x, int grid_y, vc_converter** out);
+void vc_converter_destroy(vc_converter* c);
+/* fit_radius > 0.  start: the nk_b start values, finite; NULL = [fu fv u0 v0] of A with the distortion parameters 0 (fov: w = 0.2, where the
+ * reference starts it -- at w = 0 the model's derivative with respect to w is zero).  free_mask: bit k set = K_b[k] is free, 0 = all free,
+ * no bit at or above nk_b; a fixed parameter stays at its start value. */
+int vc_convert_run(vc_converter* c, double fit_radius, int max_iters, const double* start, unsigned int free_mask);
+/* The last run: VC_ERR_BAD_ARG before a successful one; any pointer may be NULL.  params_b takes nk_b doubles.  iterations = trial points
+ * evaluated; cost0 and cost = E / 2 at the start and at K_b, each from a values-only sweep of its own (the sums a comparer of A against that
+ * camera gives); n_left_out, max_err and worst come from the sweep at K_b: the largest |d| over the fit set and its sample -- the lowest
+ * among those of the largest |d|^2 = du du + dv dv (both products rounded). */
+int vc_convert_get(vc_converter* c, double* params_b, int* nparams_b, int* status, int* iterations, int* n_fit, int* n_left_out, double* cost0, double* cost,
+                   double* max_err, long long* worst);
+/* A comparer of A against the result on the same lattice and device -- run at the identity rotation (fit_radius = 0, R_ba = NULL) it is the
+ * conversion's residual per sample.  The caller destroys it. */
+int vc_convert_comparer(vc_converter* c, vc_comparer** out);
+/* HIP events on the converter's stream like vc_time_compare, after a run: average ms of `reps` launches of [0] the rays, [1] one
+ * linearisation, [2] one cost sweep, each with its reduction. */
+int vc_time_convert(vc_converter* c, int reps, double out_ms[3]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -386,4 +386,46 @@ class Comparer {
   int gx_ = 0, gy_ = 0;
 };
 
+// A calibrated camera converted to another camera model (vc_convert*): the target's intrinsics fitted to the source's rays on a lattice over
+// the image.  No change of extrinsics: the converted camera keeps the source's pose and size.
+struct ConvertResult {
+  std::vector<double> params;             // K_b
+  int status = 0, iterations = 0, n_fit = 0, n_left_out = 0;
+  double cost0 = 0, cost = 0, max_err = 0;
+  long long worst = -1;
+};
+class Converter {
+ public:
+  // a: model, params and size are read; the pose is not
+  Converter(const CameraAndPose& a, int model_b, int grid_x, int grid_y, int device = 0) {
+    vc_checked(vc_converter_create(device, a.model, a.params.data(), (int)a.params.size(), a.width, a.height, model_b, grid_x, grid_y, &c_), "Converter");
+  }
+  Converter(ViCalibrator& cal, int camera, int model_b, int grid_x, int grid_y) {
+    vc_checked(vc_converter_create_for_camera(cal.handle(), camera, model_b, grid_x, grid_y, &c_), "Converter");
+  }
+  ~Converter() { vc_converter_destroy(c_); }
+  Converter(const Converter&) = delete;
+  Converter& operator=(const Converter&) = delete;
+  // start: nullptr = the source's [fu fv u0 v0] without distortion; free_mask: bit k set = K_b[k] is free, 0 = all
+  ConvertResult Run(double fit_radius = 1.0, int max_iters = 0, const double* start = nullptr, unsigned int free_mask = 0) {
+    vc_checked(vc_convert_run(c_, fit_radius, max_iters, start, free_mask), "Run");
+    return Get();
+  }
+  ConvertResult Get() {
+    ConvertResult r;
+    int nk = 0;
+    r.params.resize(10);
+    vc_checked(vc_convert_get(c_, r.params.data(), &nk, &r.status, &r.iterations, &r.n_fit, &r.n_left_out, &r.cost0, &r.cost, &r.max_err, &r.worst), "Get");
+    r.params.resize((size_t)nk);
+    return r;
+  }
+  // a comparer of the source against the result on the same lattice; the caller destroys it (vc_comparer_destroy)
+  vc_comparer* MakeComparer() { vc_comparer* cmp = nullptr; vc_checked(vc_convert_comparer(c_, &cmp), "MakeComparer"); return cmp; }
+  std::array<double, 3> Time(int reps = 20) { std::array<double, 3> ms{{0, 0, 0}}; vc_checked(vc_time_convert(c_, reps, ms.data()), "Time"); return ms; }
+  vc_converter* handle() { return c_; }
+
+ private:
+  vc_converter* c_ = nullptr;
+};
+
 }  // namespace visual_inertial_calibration

@@ -338,6 +338,13 @@ int vc_comparer_create_for_camera(vc_calibrator* h, int c, int model_b, const do
   { std::lock_guard<std::mutex> lk(h->result_mutex); cm = h->cams[c]; }
   return vc_comparer_create(h->device, cm.model, cm.K, cm.nk, model_b, params_b, nparams_b, cm.width, cm.height, grid_x, grid_y, out);
 }
+// a converter (vc_convert.hip) whose camera A is camera c as vc_get_camera returns it, on the calibrator's device
+int vc_converter_create_for_camera(vc_calibrator* h, int c, int model_b, int grid_x, int grid_y, vc_converter** out) {
+  if (!h || c < 0 || c >= (int)h->cams.size()) return VC_ERR_BAD_ARG;
+  HostCam cm;
+  { std::lock_guard<std::mutex> lk(h->result_mutex); cm = h->cams[c]; }
+  return vc_converter_create(h->device, cm.model, cm.K, cm.nk, cm.width, cm.height, model_b, grid_x, grid_y, out);
+}
 int vc_get_frame(vc_calibrator* h, int f, double T_wk[7], double v_w[3], double* time) {
   if (!h || f < 0 || f >= (int)h->frames.size()) return VC_ERR_BAD_ARG;
   std::lock_guard<std::mutex> lk(h->result_mutex);

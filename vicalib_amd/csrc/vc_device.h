@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include "vc_chain_plan.hpp"
+#include "vc_lm_rules.hpp"
 
 namespace vc {
 
@@ -57,17 +58,7 @@ constexpr void seg_entry(int e, int* a, int* b) {
   else { *a = 18 + (e - kSegGi); *b = 33; }
 }
 
-// The trust-region rules of the Levenberg-Marquardt loop (the Ceres rules the project restates), stated once: read by
-// init_ctrl (vc_calibrator.hpp), lm_decide_local (vc_kernels.hip) and the held-out pose refit (k_validate_pose, vc_validate.hip).
-struct LmRules {
-  static constexpr double kInitialRadius = 1e4;
-  static constexpr double kInitialDecrease = 2.0;          // radius /= decrease_factor on a rejection; the factor doubles with every one
-  static constexpr double kMinRelativeDecrease = 1e-3;     // step quality above this accepts
-  static constexpr double kMaxRadius = 1e16, kMinRadius = 1e-32;
-  static constexpr double kInvalidShrink = 0.5;            // a step without a factorisation or a model decrease: radius *= 0.5
-  static constexpr int kMaxInvalid = 5;                    // ... so many in a row end the solve as a failure
-  static constexpr double kCallbackGnorm = 1e-9;           // iteration callback (vicalibrator.h:690-721): stop if 0 < |g| < this
-};
+// (the trust-region rules of the Levenberg-Marquardt loop, LmRules: vc_lm_rules.hpp)
 
 struct Ctrl {
   double radius, decrease_factor, cost, gmax, gnorm, last_gnorm;

@@ -42,6 +42,7 @@ SYMBOLS = [
     "vc_rectifier_side", "vc_rectifier_get", "vc_rectify_pairs", "vc_rectify_check", "vc_time_rectify_check",
     "vc_comparer_create", "vc_comparer_create_for_camera", "vc_comparer_destroy", "vc_compare_run", "vc_compare_get_fit", "vc_compare_get_map",
     "vc_compare_summary", "vc_compare_rings", "vc_compare_extrinsics", "vc_time_compare",
+    "vc_converter_create", "vc_converter_create_for_camera", "vc_converter_destroy", "vc_convert_run", "vc_convert_get", "vc_convert_comparer", "vc_time_convert",
 ]
 
 
@@ -109,7 +110,7 @@ def load():
         L.vc_holdout_num_corners.restype = C.c_longlong
         L.vc_allreduce_calls.restype = C.c_longlong
         L.vc_last_error.restype = C.c_char_p
-        for name in ("vc_destroy", "vc_detector_destroy", "vc_shard_comm_destroy", "vc_undistorter_destroy", "vc_rectifier_destroy", "vc_comparer_destroy"):
+        for name in ("vc_destroy", "vc_detector_destroy", "vc_shard_comm_destroy", "vc_undistorter_destroy", "vc_rectifier_destroy", "vc_comparer_destroy", "vc_converter_destroy"):
             getattr(L, name).restype = None
         _lib = L
     return _lib
@@ -961,4 +962,61 @@ class Comparer:
     def time(self, reps=20):
         out = np.zeros(3)
         _check(self.L.vc_time_compare(self.h, int(reps), _d(out)), "time_compare")
+        return out
+
+
+class Converter:
+    """A calibrated camera converted to another camera model (include/vicalib_amd.h: vc_convert*): source camera a = (model, params) of image
+    `size` = (w, h), the target `model_b`, sampled on a lattice `grid` = (gx, gy).  run(fit_radius) fits the target's intrinsics to a's rays over
+    the samples within that normalised radius (>= 1: the whole image) and returns what get() reads; comparer() is a Comparer of a against the
+    result (run it with fit_radius = 0 for the residual per sample); time(reps) -> ms per launch of the rays, one linearisation and one cost sweep."""
+
+    def __init__(self, cam_a, model_b, size, grid=(64, 48), device=0, _camera_of=None):
+        self.L = load()
+        self.h = C.c_void_p()
+        if _camera_of is not None:
+            cal, cam = _camera_of
+            _check(self.L.vc_converter_create_for_camera(cal.h, int(cam), _model_id(model_b), int(grid[0]), int(grid[1]), C.byref(self.h)), "converter_create_for_camera")
+        else:
+            ma, Ka = cam_a
+            Ka = np.ascontiguousarray(Ka, dtype=np.float64)
+            _check(self.L.vc_converter_create(int(device), _model_id(ma), _d(Ka), len(Ka), int(size[0]), int(size[1]), _model_id(model_b), int(grid[0]), int(grid[1]),
+                                              C.byref(self.h)), "converter_create")
+        self.grid = (int(grid[0]), int(grid[1]))
+
+    @classmethod
+    def for_camera(cls, cal, camera, model_b, grid=(64, 48)):
+        """The source is camera `camera` of a ViCalibrator as GetCamera returns it, with the size it was added with."""
+        return cls(None, model_b, None, grid, _camera_of=(cal, camera))
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.vc_converter_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+    def run(self, fit_radius=1.0, max_iters=0, start=None, free_mask=0):
+        sp = None if start is None else _d(np.ascontiguousarray(start, dtype=np.float64))
+        _check(self.L.vc_convert_run(self.h, C.c_double(fit_radius), int(max_iters), sp, C.c_uint(int(free_mask))), "convert_run")
+        return self.get()
+
+    def get(self):
+        K = np.zeros(10); nk, st, it, nf, nl = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
+        c0, c1, mx, w = C.c_double(0), C.c_double(0), C.c_double(0), C.c_longlong(0)
+        _check(self.L.vc_convert_get(self.h, _d(K), C.byref(nk), C.byref(st), C.byref(it), C.byref(nf), C.byref(nl), C.byref(c0), C.byref(c1), C.byref(mx), C.byref(w)),
+               "convert_get")
+        return dict(K=K[:nk.value].copy(), status=st.value, iterations=it.value, n_fit=nf.value, n_left_out=nl.value, cost0=c0.value, cost=c1.value,
+                    max_err=mx.value, worst=w.value)
+
+    def comparer(self):
+        cmp = Comparer.__new__(Comparer)
+        cmp.L, cmp.h, cmp.grid = self.L, C.c_void_p(), self.grid
+        _check(self.L.vc_convert_comparer(self.h, C.byref(cmp.h)), "convert_comparer")
+        return cmp
+
+    def time(self, reps=20):
+        out = np.zeros(3)
+        _check(self.L.vc_time_convert(self.h, int(reps), _d(out)), "time_convert")
         return out
