@@ -149,6 +149,12 @@ static void DefineFlags() {
   Define("convert_to", "string", "", "m[,m...]: target model(s) of the conversion, one for all cameras or one per camera.  Without -convert_models the calibration just computed "
          "is converted.  With -compare_dir the original is also compared with the converted cameras, at the identity rotation.");
   Define("convert_output", "string", "converted.xml", "Rig file of the converted cameras: every camera keeps its pose and size.");
+  Define("uncertainty_dir", "string", "", "Directory for uncertainty_cam<i>.csv (x, y, s_uu, s_uv, s_vv, sigma_max, flags per lattice sample: the covariance in px^2 of the projection "
+         "shift that the covariance of the intrinsics leaves after the rotation the extrinsics would absorb) and uncertainty_summary.csv, written behind a calibration.");
+  Define("uncertainty_grid", "string", "64x48", "Lattice of the uncertainty map, GXxGY: 2 ... image width by 2 ... image height, at most 2^22 samples.");
+  Define("uncertainty_fit_radius", "double", "0.5", "The absorbed rotation is fitted over the samples within this fraction of the half-diagonal of the image centre (<= 0: no rotation is removed).");
+  Define("uncertainty_rings", "int32", "8", "Rings of equal width in normalised radius in uncertainty_summary.csv, 1 ... 64.");
+  Define("uncertainty_noise", "double", "0", "Detection noise in px per coordinate that scales the covariance; 0 = the camera's own reprojection RMSE.");
   Define("convert_grid", "string", "64x48", "Lattice of the conversion, GXxGY: 2 ... image width by 2 ... image height, at most 2^22 samples.");
   Define("convert_fit_radius", "double", "1", "The target model is fitted over the samples within this fraction of the half-diagonal of the image centre (> 0; 1 = the whole image).");
 }
@@ -905,6 +911,94 @@ static int ConvertRig(const std::string& path, const std::vector<vic::CameraAndP
   return 0;
 }
 
+// ---- -uncertainty_dir: the projection uncertainty of every camera just calibrated, mapped over its image (vc_uncertainty*) -----------------
+struct UncertaintyOptions { std::string dir; int gx = 64, gy = 48, rings = 8; double fit_radius = 0.5, noise = 0.0; };
+static bool UncertaintyFlags(UncertaintyOptions* o, std::string* err) {
+  o->dir = FlagString("uncertainty_dir");
+  if (!ParseCompareGrid(FlagString("uncertainty_grid"), &o->gx, &o->gy)) { *err = "illegal value '" + FlagString("uncertainty_grid") + "' specified for flag 'uncertainty_grid': expected GXxGY, both at least 2, at most 2^22 samples"; return false; }
+  o->fit_radius = FlagDouble("uncertainty_fit_radius");
+  if (!(std::fabs(o->fit_radius) <= 1e6)) { *err = "illegal value for flag 'uncertainty_fit_radius': expected a finite radius"; return false; }
+  o->rings = (int)FlagInt("uncertainty_rings");
+  if (o->rings < 1 || o->rings > 64) { *err = "illegal value for flag 'uncertainty_rings': expected 1 ... 64"; return false; }
+  o->noise = FlagDouble("uncertainty_noise");
+  if (!(o->noise >= 0.0 && o->noise <= 1e6)) { *err = "illegal value for flag 'uncertainty_noise': expected 0 (the camera's own RMSE) or a noise in px above 0"; return false; }
+  return true;
+}
+// cov: the solution covariance (dim x dim, blocks q_ck (4), p_ck (3), params (nk) per camera); cams: model, params and size of every camera;
+// rmse: the cameras' reprojection RMSE per coordinate.  Writes the files of -uncertainty_dir and prints one line per camera.
+static bool UncertaintyOutputs(const std::vector<vic::CameraAndPose>& cams, const std::vector<double>& cov, int dim, const std::vector<double>& rmse,
+                               const UncertaintyOptions& o, int device, std::string* err) {
+  struct stat st;
+  if (mkdir(o.dir.c_str(), 0777) != 0 && !(stat(o.dir.c_str(), &st) == 0 && S_ISDIR(st.st_mode))) { *err = "cannot create the directory " + o.dir; return false; }      // (one level)
+  FILE* fs = std::fopen((o.dir + "/uncertainty_summary.csv").c_str(), "w");
+  if (!fs) { *err = "cannot write into " + o.dir; return false; }
+  std::fprintf(fs, "camera,ring,rho_from,rho_to,count,invalid,rms_px,max_sigma_px,noise_px\n");
+  std::vector<std::vector<double>> blocks(cams.size());
+  bool ok = true;
+  int first = 0;
+  for (size_t c = 0; c < cams.size() && ok; ++c) {
+    const int nk = (int)cams[c].params.size();
+    first += 7;
+    if (first + nk > dim) { *err = "the solution covariance has no block for the intrinsics of camera " + std::to_string(c); ok = false; break; }
+    std::vector<double>& block = blocks[c];
+    block.resize((size_t)nk * nk);
+    for (int r = 0; r < nk; ++r) for (int q = 0; q < nk; ++q) block[(size_t)r * nk + q] = cov[(size_t)(first + r) * dim + first + q];
+    first += nk;
+    const double noise = o.noise > 0.0 ? o.noise : rmse[c];
+    vc_uncertainty* h = nullptr;
+    int q = vc_uncertainty_create(device, cams[c].model, cams[c].params.data(), nk, cams[c].width, cams[c].height, o.gx, o.gy, &h);
+    const size_t n = (size_t)o.gx * o.gy;
+    std::vector<double> sg(3 * n);
+    std::vector<unsigned char> fl(n);
+    vic::UncertaintySummary s;
+    vic::UncertaintyRings r;
+    r.count.resize(o.rings); r.invalid.resize(o.rings); r.sum_var.resize(o.rings); r.max_lam.resize(o.rings);
+    if (q == VC_OK) q = vc_uncertainty_run(h, block.data(), noise, o.fit_radius);
+    if (q == VC_OK) q = vc_uncertainty_get_map(h, sg.data(), fl.data());
+    if (q == VC_OK) q = vc_uncertainty_summary(h, &s.count, &s.invalid, &s.sum_var, &s.max_lam, &s.worst);
+    if (q == VC_OK) q = vc_uncertainty_rings(h, o.rings, r.count.data(), r.invalid.data(), r.sum_var.data(), r.max_lam.data());
+    vc_uncertainty_destroy(h);
+    if (q != VC_OK) {
+      *err = "camera " + std::to_string(c) + (q == VC_ERR_NUMERIC ? ": the absorbed rotation cannot be fitted (fewer than 3 samples within -uncertainty_fit_radius, or a degenerate system)"
+                                                                  : q == VC_ERR_BAD_ARG && !(noise > 0.0) ? ": the noise is 0 (a reprojection RMSE of 0: give -uncertainty_noise)"
+                                                                  : ": the uncertainty map failed (status " + std::to_string(q) + ")");
+      ok = false; break;
+    }
+    FILE* fm = std::fopen((o.dir + "/uncertainty_cam" + std::to_string(c) + ".csv").c_str(), "w");
+    if (!fm) { *err = "cannot write into " + o.dir; ok = false; break; }
+    std::fprintf(fm, "x,y,s_uu,s_uv,s_vv,sigma_max,flags\n");
+    for (size_t k = 0; k < n; ++k) {
+      const int i = (int)(k % o.gx), j = (int)(k / o.gx);
+      const double* t = &sg[3 * k];
+      const double df = t[0] - t[2], lam = 0.5 * ((t[0] + t[2]) + std::sqrt(df * df + 4.0 * (t[1] * t[1])));
+      std::fprintf(fm, "%.17g,%.17g,%.17g,%.17g,%.17g,%.17g,%d\n", (double)(i * (cams[c].width - 1)) / (o.gx - 1), (double)(j * (cams[c].height - 1)) / (o.gy - 1), t[0], t[1], t[2],
+                   std::sqrt(lam > 0.0 ? lam : lam == lam ? 0.0 : lam), (int)fl[k]);
+    }
+    std::fclose(fm);
+    for (int k = 0; k < o.rings; ++k)
+      std::fprintf(fs, "%zu,%d,%.17g,%.17g,%lld,%lld,%.17g,%.17g,%.17g\n", c, k, (double)k / o.rings, (double)(k + 1) / o.rings, r.count[k], r.invalid[k],
+                   r.count[k] > 0 ? std::sqrt(r.sum_var[k] / r.count[k]) : 0.0, std::sqrt(r.max_lam[k]), noise);
+    if (s.worst >= 0)
+      std::printf("camera %zu: projection uncertainty: worst sigma_max %.4g px at (%.1f, %.1f), %.4g px rms expected shift over %lld samples, noise %.4g px\n", c,
+                  std::sqrt(s.max_lam), (double)((s.worst % o.gx) * (cams[c].width - 1)) / (o.gx - 1), (double)((s.worst / o.gx) * (cams[c].height - 1)) / (o.gy - 1),
+                  std::sqrt(s.sum_var / s.count), s.count, noise);
+    else std::printf("camera %zu: projection uncertainty: no valid sample\n", c);
+  }
+  if (ok) {                                              // the second table: the covariance of the intrinsics that was mapped, row by row
+    std::fprintf(fs, "camera,parameter,covariance\n");
+    for (size_t c = 0; c < cams.size(); ++c) {
+      const int nk = (int)cams[c].params.size();
+      for (int r = 0; r < nk; ++r) {
+        std::fprintf(fs, "%zu,%d", c, r);
+        for (int q = 0; q < nk; ++q) std::fprintf(fs, ",%.17g", blocks[c][(size_t)r * nk + q]);
+        std::fprintf(fs, "\n");
+      }
+    }
+  }
+  std::fclose(fs);
+  return ok;
+}
+
 int main(int argc, char** argv) {
   DefineFlags();
   std::string err;
@@ -924,6 +1018,8 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "ERROR: illegal value '%s' specified for flag 'holdout_every': expected 0 (off) or N >= 2 (N = 1 would leave no frame to calibrate from)\n", FlagString("holdout_every").c_str());
     return 1;
   }
+  UncertaintyOptions uncertainty;
+  if (!UncertaintyFlags(&uncertainty, &err)) { std::fprintf(stderr, "ERROR: %s\n", err.c_str()); return 1; }
   // ---- -compare_models a.xml,b.xml: file against file, nothing is calibrated; -compare_to b.xml: read now, compared behind the results
   CompareOptions compare;
   std::vector<vic::CameraAndPose> compare_b;
@@ -1057,6 +1153,11 @@ int main(int argc, char** argv) {
   if (input_cameras.size() < n_cam) { std::fprintf(stderr, "F %zu camera models for %zu channels\n", input_cameras.size(), n_cam); return 1; }
   input_cameras.resize(n_cam);
   if (converting && !ConvertibleRig(input_cameras, convert, &err)) { std::fprintf(stderr, "ERROR: %s\n", err.c_str()); return 1; }      // before any solve
+  if (!uncertainty.dir.empty()) {
+    if (!FlagBool("calibrate_intrinsics")) { std::fprintf(stderr, "F -uncertainty_dir needs -calibrate_intrinsics: fixed intrinsics have no covariance\n"); return 1; }
+    for (size_t c = 0; c < input_cameras.size(); ++c)
+      if (uncertainty.gx > input_cameras[c].width || uncertainty.gy > input_cameras[c].height) { std::fprintf(stderr, "F camera %zu: -uncertainty_grid exceeds the image\n", c); return 1; }
+  }
   if (!compare_b.empty() && !ComparableRigs(input_cameras, compare_b, compare, &err)) { std::fprintf(stderr, "F -compare_to: %s\n", err.c_str()); return 1; }      // before any solve
 
   // ---- frames: union of the frame ids, -frame_skip, -num_vicalib_frames (vicalib-engine.cc:540-590) ---------------------
@@ -1411,6 +1512,22 @@ int main(int argc, char** argv) {
     }
     if (CompareRigs(a, compare_b, compare, (int)FlagInt("device"), &err) != 0) { std::fprintf(stderr, "E comparison failed: %s\n", err.c_str()); compare_failed = true; }
   }
+  bool uncertainty_failed = false;
+  if (!uncertainty.dir.empty()) {                        // -uncertainty_dir: the covariance at the result (collective when the frames are sharded), mapped per camera
+    std::vector<std::vector<double>> covs((size_t)n_gpus);
+    std::vector<int> dims((size_t)n_gpus, 0);
+    std::vector<std::thread> th;
+    for (int r = 0; r < n_gpus; ++r) th.emplace_back([&, r] { covs[r] = cals[r]->GetSolutionCovariance(&dims[r]); });
+    for (auto& t : th) t.join();
+    std::vector<vic::CameraAndPose> a;
+    for (size_t c = 0; c < n_cam; ++c) {
+      vic::CameraAndPose now = cal.GetCamera(c);
+      now.model = input_cameras[c].model; now.width = input_cameras[c].width; now.height = input_cameras[c].height;
+      a.push_back(now);
+    }
+    if (covs[0].empty()) { std::fprintf(stderr, "E uncertainty map failed: the solution covariance cannot be computed\n"); uncertainty_failed = true; }
+    else if (!UncertaintyOutputs(a, covs[0], dims[0], rmse, uncertainty, (int)FlagInt("device"), &err)) { std::fprintf(stderr, "E uncertainty map failed: %s\n", err.c_str()); uncertainty_failed = true; }
+  }
   bool convert_failed = false;
   if (converting) {                                      // -convert_to: the cameras just written, converted
     std::vector<vic::CameraAndPose> a;
@@ -1456,5 +1573,6 @@ int main(int argc, char** argv) {
   if (rectify_failed) std::fprintf(stderr, "E -rectify_dir: the rectification's files are incomplete (exit status %d)\n", success ? 1 : 2);
   if (compare_failed) std::fprintf(stderr, "E -compare_to: the comparison's files are incomplete (exit status %d)\n", success ? 1 : 2);
   if (convert_failed) std::fprintf(stderr, "E -convert_to: the converted rig is incomplete (exit status %d)\n", success ? 1 : 2);
-  return success ? ((undistort_failed || rectify_failed || compare_failed || convert_failed) ? 1 : 0) : 2;
+  if (uncertainty_failed) std::fprintf(stderr, "E -uncertainty_dir: the uncertainty map's files are incomplete (exit status %d)\n", success ? 1 : 2);
+  return success ? ((undistort_failed || rectify_failed || compare_failed || convert_failed || uncertainty_failed) ? 1 : 0) : 2;
 }

@@ -565,6 +565,49 @@ int vc_convert_comparer(vc_converter* c, vc_comparer** out);
  * linearisation, [2] one cost sweep, each with its reduction. */
 int vc_time_convert(vc_converter* c, int reps, double out_ms[3]);
 
+/* ---- mapping the projection uncertainty of a calibrated camera ------------------------------------------------------------------------
+ * How far can this calibration be trusted, and where in the image?  Camera A (any of the six models, intrinsics K -- nk of them --, image
+ * w x h), the comparer's lattice of grid_x x grid_y samples with its limits, a covariance Cov of K (nk x nk, row-major), a noise scale
+ * sigma_px > 0 and a fit_radius.  The ray a_s of sample s is its pixel q_s through A's Newton inversion, scaled to unit length.  B_s (2 x nk,
+ * with respect to K) and A_s (2 x 3, with respect to the ray) are the Jacobian blocks of A's projection at a_s; Jw_s = -A_s [a_s]x is the
+ * comparer's rotation row at R = I.  The fit set F: inversion valid, rho <= fit_radius, a_z > 0 unless the model is kb4.  Over F,
+ * G = sum Jw^T Jw (3 x 3), C = sum Jw^T B (3 x nk) and M = -G^-1 C, in rad per unit of each parameter: a change dK moves sample s by
+ * B_s dK, the rotation that best absorbs it over F -- the one the extrinsics, or the pose of whoever uses the camera, would take up -- is
+ * w = M dK, and what is left is J_s dK with J_s = B_s + Jw_s M.  fit_radius <= 0: no compensation, M = 0 and J_s = B_s.
+ * The map: Sigma_s = sigma_px^2 J_s Cov J_s^T, a symmetric 2 x 2 stored as (s_uu, s_uv, s_vv) in px^2.  var_s = s_uu + s_vv is the
+ * expected squared shift of the sample; lam_s = (var_s + sqrt((s_uu - s_vv)^2 + 4 s_uv^2)) / 2, clamped at 0, is the variance along the
+ * worst direction.  Every valid sample gets a value, in F or not.  flags: bit 0 A's inversion failed, bit 2 the sample is INVALID -- the
+ * inversion failed, a_z <= 0 (unless kb4) or Sigma is not finite --: its triple is NaN and it enters no sum.  Cov is multiplied by
+ * sigma_px^2 before it enters the sweep: doubling sigma_px quadruples every output bit for bit.
+ * What the map does NOT say: it is the intrinsics' share after a rotation, for one camera on its own -- the baseline and the relative pose
+ * of a stereo pair carry an uncertainty of their own that is not in it --, and like any covariance it assumes the noise model of the solve.
+ * VC_ERR_NUMERIC: fewer than 3 samples in F, or a G without a positive pivot.  A handle is single-threaded with a stream of its own;
+ * nothing is launched before the first run; no CPU fallback.  Argument errors are VC_ERR_BAD_ARG and come before the device is looked for
+ * (VC_ERR_NO_DEVICE).  Every sum is formed in a fixed order that depends on the lattice alone: two runs, and two handles, give the same
+ * bits.  Any output pointer may be NULL. */
+typedef struct vc_uncertainty vc_uncertainty;
+int vc_uncertainty_create(int device, int model, const double* params, int nparams, int width, int height, int grid_x, int grid_y, vc_uncertainty** out);
+/* A = camera `camera` of a calibrator as vc_get_camera returns it (model, intrinsics and size), on the calibrator's device, with the
+ * camera's params block of vc_get_solution_covariance at the current state kept as the handle's covariance: collective on a sharded
+ * calibrator like that call, whose status is handed on (VC_ERR_NUMERIC included).  VC_ERR_BAD_ARG with fixed intrinsics: no block then. */
+int vc_uncertainty_create_for_camera(vc_calibrator* h, int camera, int grid_x, int grid_y, vc_uncertainty** out);
+void vc_uncertainty_destroy(vc_uncertainty* u);
+/* cov: nk x nk, NULL = the calibrator's (VC_ERR_BAD_ARG on a handle without one).  VC_ERR_BAD_ARG: an entry of cov that is not finite,
+ * cov not symmetric to 1e-12 max |diag|, a negative diagonal entry, sigma_px not > 0 and finite, fit_radius not finite.  The rays are
+ * computed once per handle; another fit_radius redoes only the sweep of G and C.  A refused run leaves nothing to read. */
+int vc_uncertainty_run(vc_uncertainty* u, const double* cov, double sigma_px, double fit_radius);
+/* The readers below return VC_ERR_BAD_ARG before a successful run.  Without compensation M, G and n_fit are zero. */
+int vc_uncertainty_get_fit(vc_uncertainty* u, double* M /* 3 x nk */, double* G /* 3 x 3 */, int* n_fit);
+int vc_uncertainty_get_map(vc_uncertainty* u, double* sigma /* grid_y x grid_x x 3 */, unsigned char* flags /* grid_y x grid_x */);
+/* over the valid samples: sum var, and the largest lam with its sample -- the lowest among equal ones, -1 (and max_lam 0) without a valid sample */
+int vc_uncertainty_summary(vc_uncertainty* u, long long* count, long long* invalid, double* sum_var, double* max_lam, long long* worst);
+/* n_rings in [1, 64] arrays, the comparer's rings.  The run bins 8; another count is a rings-only sweep over the stored triples on the
+ * device, kept until the next run or another count.  max_lam of a ring without a valid sample is 0. */
+int vc_uncertainty_rings(vc_uncertainty* u, int n_rings, long long* count, long long* invalid, double* sum_var, double* max_lam);
+/* HIP events on the handle's stream like vc_time_compare, after a run: average ms of `reps` launches of [0] the rays, [1] the sweep of G
+ * and C, [2] the map sweep, each with its reduction. */
+int vc_time_uncertainty(vc_uncertainty* u, int reps, double out_ms[3]);
+
 #ifdef __cplusplus
 }
 #endif

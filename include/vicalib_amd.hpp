@@ -428,4 +428,57 @@ class Converter {
   vc_converter* c_ = nullptr;
 };
 
+// The projection uncertainty of one calibrated camera mapped over its image (vc_uncertainty*): per lattice sample the 2 x 2 covariance, in
+// px^2, of the shift that a covariance of the intrinsics leaves after the rotation the extrinsics would absorb.  One camera on its own: the
+// relative pose of a stereo pair is not in it.
+struct UncertaintyFit { std::vector<double> M; double G[9]; int n_fit = 0; };      // M: 3 x nk, rad per unit of each parameter
+struct UncertaintySummary { long long count = 0, invalid = 0, worst = -1; double sum_var = 0, max_lam = 0; };
+struct UncertaintyRings { std::vector<long long> count, invalid; std::vector<double> sum_var, max_lam; };
+class Uncertainty {
+ public:
+  // a: model, params and size are read; the pose is not.  Run needs a covariance.
+  Uncertainty(const CameraAndPose& a, int grid_x, int grid_y, int device = 0) : nk_((int)a.params.size()), gx_(grid_x), gy_(grid_y) {
+    vc_checked(vc_uncertainty_create(device, a.model, a.params.data(), (int)a.params.size(), a.width, a.height, grid_x, grid_y, &u_), "Uncertainty");
+  }
+  // the calibrator's camera with its block of the solution covariance at the current state
+  Uncertainty(ViCalibrator& cal, int camera, int grid_x, int grid_y) : gx_(grid_x), gy_(grid_y) {
+    vc_checked(vc_uncertainty_create_for_camera(cal.handle(), camera, grid_x, grid_y, &u_), "Uncertainty");
+    nk_ = (int)cal.GetCamera(camera).params.size();
+  }
+  ~Uncertainty() { vc_uncertainty_destroy(u_); }
+  Uncertainty(const Uncertainty&) = delete;
+  Uncertainty& operator=(const Uncertainty&) = delete;
+  // cov: nk x nk row-major, nullptr = the calibrator's; fit_radius <= 0: no compensation
+  UncertaintyFit Run(const double* cov, double sigma_px, double fit_radius = 0.5) {
+    vc_checked(vc_uncertainty_run(u_, cov, sigma_px, fit_radius), "Run");
+    UncertaintyFit f;
+    f.M.resize(3 * (size_t)nk_);
+    vc_checked(vc_uncertainty_get_fit(u_, f.M.data(), f.G, &f.n_fit), "Run");
+    return f;
+  }
+  // sigma: gy x gx x 3 = (s_uu, s_uv, s_vv), NaN at an invalid sample; flags: gy x gx
+  void Map(std::vector<double>* sigma, std::vector<unsigned char>* flags) {
+    sigma->resize(3 * (size_t)gx_ * gy_); flags->resize((size_t)gx_ * gy_);
+    vc_checked(vc_uncertainty_get_map(u_, sigma->data(), flags->data()), "Map");
+  }
+  UncertaintySummary Summary() {
+    UncertaintySummary s;
+    vc_checked(vc_uncertainty_summary(u_, &s.count, &s.invalid, &s.sum_var, &s.max_lam, &s.worst), "Summary");
+    return s;
+  }
+  UncertaintyRings Rings(int n_rings = 8) {
+    UncertaintyRings r;
+    const size_t n = n_rings > 0 ? (size_t)n_rings : 1;
+    r.count.resize(n); r.invalid.resize(n); r.sum_var.resize(n); r.max_lam.resize(n);
+    vc_checked(vc_uncertainty_rings(u_, n_rings, r.count.data(), r.invalid.data(), r.sum_var.data(), r.max_lam.data()), "Rings");
+    return r;
+  }
+  std::array<double, 3> Time(int reps = 20) { std::array<double, 3> ms{{0, 0, 0}}; vc_checked(vc_time_uncertainty(u_, reps, ms.data()), "Time"); return ms; }
+  vc_uncertainty* handle() { return u_; }
+
+ private:
+  vc_uncertainty* u_ = nullptr;
+  int nk_ = 0, gx_ = 0, gy_ = 0;
+};
+
 }  // namespace visual_inertial_calibration

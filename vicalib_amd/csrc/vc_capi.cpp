@@ -1,6 +1,7 @@
 // vc_capi.cpp -- the C entry points of include/vicalib_amd.h over struct vc_calibrator (vc_calibrator.hpp): argument checks, device binding,
 // status codes; RCCL communicators; parity / timing hooks; solution covariance; results as text and cameras.xml.
 #include "vc_calibrator.hpp"
+#include "vc_uncertainty.hpp"
 
 static int env_bit(const char* name) { const char* e = std::getenv(name); return (e && (e[0] == '0' || e[0] == '1')) ? e[0] - '0' : -1; }
 Switches Switches::read() {
@@ -344,6 +345,34 @@ int vc_converter_create_for_camera(vc_calibrator* h, int c, int model_b, int gri
   HostCam cm;
   { std::lock_guard<std::mutex> lk(h->result_mutex); cm = h->cams[c]; }
   return vc_converter_create(h->device, cm.model, cm.K, cm.nk, cm.width, cm.height, model_b, grid_x, grid_y, out);
+}
+// an uncertainty map (vc_uncertainty.hip) of camera c as vc_get_camera returns it, on the calibrator's device, with the camera's params block of
+// vc_get_solution_covariance at the current state (the layout of covariance_layout: q_ck (4), p_ck (3), params (nk) per camera)
+int vc_uncertainty_create_for_camera(vc_calibrator* h, int c, int grid_x, int grid_y, vc_uncertainty** out) {
+  if (!h || !out || c < 0 || c >= (int)h->cams.size() || h->fix_intrinsics) return VC_ERR_BAD_ARG;
+  HostCam cm;
+  int first = 0;
+  {
+    std::lock_guard<std::mutex> lk(h->result_mutex);
+    cm = h->cams[c];
+    for (int k = 0; k < c; ++k) first += 7 + h->cams[k].nk;
+  }
+  first += 7;
+  if (!vc::undist_source_args_ok(cm.model, cm.K, cm.nk, cm.width, cm.height) || !vc::cvt_grid_ok(cm.width, cm.height, grid_x, grid_y)) return VC_ERR_BAD_ARG;
+  const int n = vc_solution_covariance_dim(h);
+  if (n < first + cm.nk) return VC_ERR_BAD_ARG;
+  std::vector<double> cov((size_t)n * n), block((size_t)cm.nk * cm.nk);
+  int m = 0;
+  const int rc = vc_get_solution_covariance(h, cov.data(), n, &m);
+  if (rc != VC_OK) return rc;
+  for (int r = 0; r < cm.nk; ++r)
+    for (int s = 0; s < cm.nk; ++s) block[(size_t)r * cm.nk + s] = cov[(size_t)(first + r) * n + first + s];
+  vc_uncertainty* u = nullptr;
+  const int st = vc_uncertainty_create(h->device, cm.model, cm.K, cm.nk, cm.width, cm.height, grid_x, grid_y, &u);
+  if (st != VC_OK) return st;
+  vc::unc_attach_cov(u, block.data());
+  *out = u;
+  return VC_OK;
 }
 int vc_get_frame(vc_calibrator* h, int f, double T_wk[7], double v_w[3], double* time) {
   if (!h || f < 0 || f >= (int)h->frames.size()) return VC_ERR_BAD_ARG;

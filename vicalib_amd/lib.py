@@ -43,6 +43,8 @@ SYMBOLS = [
     "vc_comparer_create", "vc_comparer_create_for_camera", "vc_comparer_destroy", "vc_compare_run", "vc_compare_get_fit", "vc_compare_get_map",
     "vc_compare_summary", "vc_compare_rings", "vc_compare_extrinsics", "vc_time_compare",
     "vc_converter_create", "vc_converter_create_for_camera", "vc_converter_destroy", "vc_convert_run", "vc_convert_get", "vc_convert_comparer", "vc_time_convert",
+    "vc_uncertainty_create", "vc_uncertainty_create_for_camera", "vc_uncertainty_destroy", "vc_uncertainty_run", "vc_uncertainty_get_fit", "vc_uncertainty_get_map",
+    "vc_uncertainty_summary", "vc_uncertainty_rings", "vc_time_uncertainty",
 ]
 
 
@@ -110,7 +112,8 @@ def load():
         L.vc_holdout_num_corners.restype = C.c_longlong
         L.vc_allreduce_calls.restype = C.c_longlong
         L.vc_last_error.restype = C.c_char_p
-        for name in ("vc_destroy", "vc_detector_destroy", "vc_shard_comm_destroy", "vc_undistorter_destroy", "vc_rectifier_destroy", "vc_comparer_destroy", "vc_converter_destroy"):
+        for name in ("vc_destroy", "vc_detector_destroy", "vc_shard_comm_destroy", "vc_undistorter_destroy", "vc_rectifier_destroy", "vc_comparer_destroy", "vc_converter_destroy",
+                     "vc_uncertainty_destroy"):
             getattr(L, name).restype = None
         _lib = L
     return _lib
@@ -1019,4 +1022,81 @@ class Converter:
     def time(self, reps=20):
         out = np.zeros(3)
         _check(self.L.vc_time_convert(self.h, int(reps), _d(out)), "time_convert")
+        return out
+
+
+class Uncertainty:
+    """The projection uncertainty of one calibrated camera mapped over its image (include/vicalib_amd.h: vc_uncertainty*): camera = (model,
+    params) of image `size` = (w, h), sampled on a lattice `grid` = (gx, gy).  run(cov, sigma_px, fit_radius) takes a covariance of the
+    intrinsics (None: the calibrator's, on a handle made by for_camera), removes the rotation the extrinsics would absorb -- fitted over the
+    samples within fit_radius; <= 0: none -- and maps Sigma = sigma_px^2 J cov J^T per sample; fit(), map(), summary() and rings(n) read the
+    last run; time(reps) -> ms per launch of the rays, the sweep of G and C and the map sweep."""
+
+    def __init__(self, camera, size, grid=(64, 48), device=0, _camera_of=None):
+        self.L = load()
+        self.h = C.c_void_p()
+        if _camera_of is not None:
+            cal, cam = _camera_of
+            _check(self.L.vc_uncertainty_create_for_camera(cal.h, int(cam), int(grid[0]), int(grid[1]), C.byref(self.h)), "uncertainty_create_for_camera")
+            self.nk = len(cal.GetCamera(cam)[0])
+        else:
+            m, K = camera
+            K = np.ascontiguousarray(K, dtype=np.float64)
+            _check(self.L.vc_uncertainty_create(int(device), _model_id(m), _d(K), len(K), int(size[0]), int(size[1]), int(grid[0]), int(grid[1]), C.byref(self.h)),
+                   "uncertainty_create")
+            self.nk = len(K)
+        self.grid = (int(grid[0]), int(grid[1]))
+
+    @classmethod
+    def for_camera(cls, cal, camera, grid=(64, 48)):
+        """Camera `camera` of a ViCalibrator as GetCamera returns it, with the size it was added with and its params block of
+        GetSolutionCovariance() at the current state as the handle's covariance."""
+        return cls(None, None, grid, _camera_of=(cal, camera))
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.vc_uncertainty_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+    def run(self, cov=None, sigma_px=1.0, fit_radius=0.5):
+        cp = None
+        if cov is not None:
+            cov = np.ascontiguousarray(cov, dtype=np.float64)
+            if cov.shape != (self.nk, self.nk):
+                raise VicalibError("uncertainty_run failed: VC_ERR_BAD_ARG (cov is not nk x nk)")
+            cp = _d(cov)
+        _check(self.L.vc_uncertainty_run(self.h, cp, C.c_double(sigma_px), C.c_double(fit_radius)), "uncertainty_run")
+        return self.fit()
+
+    def fit(self):
+        M = np.zeros((3, self.nk)); G = np.zeros((3, 3)); nf = C.c_int(0)
+        _check(self.L.vc_uncertainty_get_fit(self.h, _d(M), _d(G), C.byref(nf)), "uncertainty_get_fit")
+        return dict(M=M, G=G, n_fit=nf.value)
+
+    def map(self):
+        """-> (sigma [gy, gx, 3] = (s_uu, s_uv, s_vv), a NaN triple at an invalid sample; flags [gy, gx] uint8)"""
+        gx, gy = self.grid
+        s = np.zeros((gy, gx, 3)); f = np.zeros((gy, gx), dtype=np.uint8)
+        _check(self.L.vc_uncertainty_get_map(self.h, s.ctypes.data_as(C.c_void_p), f.ctypes.data_as(C.c_void_p)), "uncertainty_get_map")
+        return s, f
+
+    def summary(self):
+        n, bad, w = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
+        sv, mx = C.c_double(0), C.c_double(0)
+        _check(self.L.vc_uncertainty_summary(self.h, C.byref(n), C.byref(bad), C.byref(sv), C.byref(mx), C.byref(w)), "uncertainty_summary")
+        return dict(count=n.value, invalid=bad.value, sum_var=sv.value, max_lam=mx.value, worst=w.value)
+
+    def rings(self, n_rings=8):
+        n, bad = np.zeros(n_rings, dtype=np.int64), np.zeros(n_rings, dtype=np.int64)
+        sv, mx = np.zeros(n_rings), np.zeros(n_rings)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)      # noqa: E731
+        _check(self.L.vc_uncertainty_rings(self.h, int(n_rings), p(n), p(bad), p(sv), p(mx)), "uncertainty_rings")
+        return dict(count=n, invalid=bad, sum_var=sv, max_lam=mx)
+
+    def time(self, reps=20):
+        out = np.zeros(3)
+        _check(self.L.vc_time_uncertainty(self.h, int(reps), _d(out)), "time_uncertainty")
         return out
