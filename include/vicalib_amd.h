@@ -189,6 +189,10 @@ int vc_shard_info(vc_calibrator* h, int* rank, int* world_size, int* rccl_ranks,
  * one launch (k_chain_back_path), Gram sums in the top level's launch, top-level frames as a partial record of their own, the reduced
  * solve's tail in the back-substitution's launch, the shared parameters' blocks formed ahead of the reduced solve }. */
 int vc_pass_paths(vc_calibrator* h, int* out6);
+/* Which levels of the chain elimination the uploaded problem eliminates by odd-even reduction inside a workgroup (same standing as
+ * vc_pass_paths): *n_levels = levels below the top one, oe_levels[l] (l < cap; the caller provides cap ints) = 1 where level l does,
+ * *oe_top likewise for the top level. */
+int vc_chain_order(vc_calibrator* h, int* n_levels, int* oe_levels, int cap, int* oe_top);
 /* Text behind the last failing status of vc_set_shard_rccl on this thread (which library call failed, RCCL's error string and
  * last-error text): what a launcher prints before it falls back to another transport.  Empty if nothing failed. */
 const char* vc_last_error(void);

@@ -21,7 +21,7 @@ struct Switches {
   long long sync_bound = 800000;        // VICALIB_AMD_SYNC_BOUND: polls before a flag wait gives up (~0.2 s; a tiny bound forces the time-out path)
   int sync_bound_from_pass = 0;         // VICALIB_AMD_SYNC_BOUND_FROM_PASS: that bound only from this pass of the calibrator on
   int pre_backsub = -1;                 // VICALIB_AMD_PRE_BACKSUB=0 / 1: k_backsub off / on whatever the tile count (-1: unset)
-  ChainSwitches chain;                  // VICALIB_AMD_FOLD_L0, _BACK_PATH, _HADD_EARLY, _DEFER_TAIL (vc_chain_plan.hpp)
+  ChainSwitches chain;                  // VICALIB_AMD_FOLD_L0, _BACK_PATH, _HADD_EARLY, _DEFER_TAIL, _CHAIN_ODD_EVEN (vc_chain_plan.hpp)
   static Switches read();
 };
 

@@ -18,6 +18,7 @@ Switches Switches::read() {
   w.pre_backsub = env_bit("VICALIB_AMD_PRE_BACKSUB");
   w.chain.fold_l0 = env_bit("VICALIB_AMD_FOLD_L0") != 0; w.chain.back_path = env_bit("VICALIB_AMD_BACK_PATH") != 0;
   w.chain.hadd_early = env_bit("VICALIB_AMD_HADD_EARLY") != 0; w.chain.defer_tail = env_bit("VICALIB_AMD_DEFER_TAIL") != 0;
+  w.chain.odd_even = env_bit("VICALIB_AMD_CHAIN_ODD_EVEN") != 0;
   return w;
 }
 
@@ -622,6 +623,13 @@ int vc_pass_paths(vc_calibrator* h, int* out6) {
   const ChainPlan& p = h->plan;      // (the forms of the uploaded problem: every pass runs them)
   out6[0] = p.fold_l0; out6[1] = p.back_path; out6[2] = p.gram_top_stride > 0 ? 1 : 0; out6[3] = p.top_gram_launch;
   out6[4] = p.tail_deferred; out6[5] = p.hadd_early;
+  return VC_OK;
+}
+int vc_chain_order(vc_calibrator* h, int* n_levels, int* oe_levels, int cap, int* oe_top) {
+  if (!h || !n_levels || !oe_levels || !oe_top || cap < 0) return VC_ERR_BAD_ARG;
+  const ChainPlan& p = h->plan;
+  *n_levels = p.n_levels; *oe_top = p.oe_top;
+  for (int l = 0; l < cap; ++l) oe_levels[l] = l < p.n_levels ? p.oe[l] : 0;
   return VC_OK;
 }
 void* vc_get_stream(vc_calibrator* h) { return h ? (void*)h->stream : nullptr; }

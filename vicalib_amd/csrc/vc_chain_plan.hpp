@@ -10,8 +10,8 @@ constexpr int kChainM = 8;               // group size: 7 eliminations per wavef
 constexpr int kChainMaxLevels = 16;      // levels below the top one (a level multiplies the stride by kChainM)
 constexpr int kChainEarlyTopD = 31;      // = kEarlyTopD (vc_device.h): k_reduced adds the top level's frames itself up to this width
 
-// the tested switches that select forms of the pass (VICALIB_AMD_FOLD_L0, _BACK_PATH, _HADD_EARLY, _DEFER_TAIL; =0 turns one off)
-struct ChainSwitches { bool fold_l0 = true, back_path = true, hadd_early = true, defer_tail = true; };
+// the tested switches that select forms of the pass (VICALIB_AMD_FOLD_L0, _BACK_PATH, _HADD_EARLY, _DEFER_TAIL, _CHAIN_ODD_EVEN; =0 turns one off)
+struct ChainSwitches { bool fold_l0 = true, back_path = true, hadd_early = true, defer_tail = true, odd_even = true; };
 
 struct ChainPlan {
   // strides 1, m, m^2, ... while more than m - 1 frames are active, then the top level (one wavefront eliminates the rest, stride top_stride)
@@ -22,6 +22,12 @@ struct ChainPlan {
   // A function of the frame count and the level only: forward, backward and every hand-over mode agree on it.  (Measured 26.3 -> 21.7 us
   // per level at cfg3; the bottom level too, since the weight update on the other stream starts behind it -- vc_pass.cpp)
   int two[kChainMaxLevels] = {};
+  // oe[l]: level l's groups are eliminated by odd-even reduction inside a workgroup of four wavefronts (k_chain_oe, vc_chain_order.hpp):
+  // 3 dependent eliminations per level instead of the two sweeps' 4.  One-column borders, single-process passes, levels above the bottom one (whose builders occupy
+  // the other two wavefronts); two[l] keeps its value -- it says what the level runs with the switch off.  oe_top: the top level likewise
+  // (ceil(log2(t + 1)) eliminations for its t frames instead of t).
+  int oe[kChainMaxLevels] = {};
+  int oe_top = 0;
   int top_stride = 1;
   int forward_launches = 0;              // launches of the forward elimination (levels + the top level); 0: no frames
   int bottom_groups = 1;                 // groups of the bottom level (DevView::n_chain_groups)
@@ -49,6 +55,9 @@ inline ChainPlan plan_chain(int N, int D, int n_cams, bool imu_on, bool sharded,
   if (p.n_levels > 0) p.bottom_groups = p.groups[0];
   const int cpl = (D + 1 + 27 + 63) / 64;      // 64-column images of a frame's row (border + 27 chain columns) per lane
   for (int l = 0; l < p.n_levels; ++l) p.two[l] = (cpl <= 1 || (cpl <= 2 && p.groups[l] <= 256)) ? 1 : 0;
+  // (never a sharded pass: those keep the two sweeps and the one-wavefront top level)
+  for (int l = 1; l < p.n_levels; ++l) p.oe[l] = (sw.odd_even && !sharded && p.two[l] && cpl <= 1) ? 1 : 0;
+  p.oe_top = (sw.odd_even && !sharded && cpl <= 1) ? 1 : 0;
   if (!imu_on) return p;
   // k_chain_l0 serves narrow borders, at most two cameras, at least one level below the top one; never a sharded pass.  A function of the
   // problem only, never of the hand-over mode; its chunk of the partial sums is the group of 8 frames

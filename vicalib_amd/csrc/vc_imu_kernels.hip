@@ -17,6 +17,8 @@
 //                  camera Gram blocks and of the IMU shared-parameter block
 //  k_chain_fwd     one level of the partitioned chain elimination: a wavefront eliminates the interior frames of a group
 //                  of 8 (L, X_s = L^-1 C, X_n = L^-1 B, Y = L^-1 [W | g]); the group's first frame survives to the next level
+//  k_chain_oe      one level of the elimination by odd-even reduction inside a workgroup of four wavefronts (one-column borders, the levels
+//                  above the bottom one, the top level: vc_chain_order.hpp) -- 3 dependent eliminations per level instead of 4
 //  k_chain_gram    sum over all frames of [Y | z]^T [Y | z] on the matrix pipe (v_mfma_f64_16x16x4_f64)
 //  k_chain_l0      (round 5) k_chain_init's work and the bottom level of the elimination in one launch: the frames' images stay in LDS
 //                  (narrow borders, at most two cameras, single process)
@@ -32,6 +34,7 @@
 #include "vc_imu.hpp"
 #include "vc_imu_weights.hpp"
 #include "vc_device.h"
+#include "vc_chain_order.hpp"
 #include "vc_kutil.hpp"
 #include "vc_reduced_tail.hpp"
 #include "vc_shared_blocks.hpp"
@@ -1853,6 +1856,228 @@ __global__ __launch_bounds__(128 * NW, VC_FWD2_WAVES) void k_chain_fwd2(DevView 
   F2STAMP(14);
 }
 
+// ---- odd-even elimination of a group (narrow borders: one column per lane; vc_chain_order.hpp) -------------------------------------------
+// The two sweeps above still leave (m - 2) / 2 + 1 = 4 DEPENDENT eliminations per level, each ~1000 instructions of a wavefront that is alone
+// on its SIMD.  Here a workgroup of four wavefronts eliminates the interior frames e_1 .. e_q of a group in ceil(log2(q + 1)) rounds:
+// e_1, e_3, e_5, e_7 at once, then e_2, e_6, then e_4 -- a frame's "separator" and "next" (chain_eliminate's X_s / X_n) are simply its left and
+// right neighbour at that moment, i -+ 2^(round - 1), and the fill-in between the two neighbours is what the role-1 and role-3 lanes produce
+// anyway.  Wavefront w holds e_{2w+1} and e_{2w+2}; after a round every lane leaves out[0..8] for the left and out[9..17] for the right
+// neighbour in LDS (one image of 9 x 64 per source and side), ONE workgroup barrier, and the wavefront that holds a neighbour adds the left
+// source's image, then the right one's (fixed order: bit-stable).  Border and A columns accumulate; the coupling columns are the fill-in of the
+// round before the frame's own.  The wavefront of the last round (e_{2^(K-1)}: both of its neighbours are separators) finishes a and r as
+// k_chain_fwd2's middle frame does: a absorbs the left-edge frames' updates in round order, r's update goes to the side image rw, the fill-in
+// between a and r becomes a's B block.  Images: [Y | z | X_s (left neighbour) | L | X_n (right neighbour)]; the back-substitution follows the
+// same order (chain_back_oe).  top: the chain's top level -- t <= 7 frames, no separators.
+constexpr int kOeSlot = 9 * 64;                                  // one hand-over image: nine values per lane
+constexpr int kOeWaveLds = 9 * kXsLd + 81 + 81 + 2;               // XS, An, Ls of one wavefront (344 doubles: 16-byte aligned)
+constexpr int kOeLds = kOeWaves * kOeWaveLds + 8 * kOeSlot;       // doubles of LDS of a group's workgroup
+// The image frame i leaves for its left (side 0) / right (side 1) neighbour.  The frames of round 1 own two images each; a frame of round 2
+// writes into the two images it read itself after round 1 (its own program order keeps that safe); the last round's frame writes none.
+// The kernels index a wavefront's frames, a round's sources and a round's frames in closed form (wave-uniform scalars, compile-time unrolling);
+// every one of those forms is the schedule's, checked here against oe_full for the whole group: vc_chain_order.hpp stays the one definition.
+constexpr bool oe_closed_forms_match() {
+  for (int i = 1; i <= kOeMaxQ; ++i) {
+    const OeFrame f = oe_full(i);
+    const int h = 1 << (f.step - 1);
+    if (f.wave != (i - 1) / 2) return false;                                            // wavefront w holds e_{2w+1}, e_{2w+2}
+    if (i % h != 0 || ((i / h) & 1) != 1) return false;                                 // round k: the frames h (2u + 1), h = 2^(k-1)
+    if (oe_slot(f.left) != i - h || oe_slot(f.right) != i + h) return false;            // neighbours i -+ h; slots 0 / kOeMaxQ + 1: the separators
+    // the sources of frame i after round j < step: the frames of round j whose neighbour it is -- i -+ 2^(j-1)
+    for (int j = 1; j < f.step; ++j) {
+      const int hs = 1 << (j - 1);
+      if (oe_full(i - hs).step != j || oe_slot(oe_full(i - hs).right) != i) return false;
+      if (i + hs <= kOeMaxQ && (oe_full(i + hs).step != j || oe_slot(oe_full(i + hs).left) != i)) return false;
+    }
+  }
+  for (int q = 1; q <= kOeMaxQ; ++q) {
+    const OeFrame f = oe_frame(q, true, true, oe_last(q));
+    if (f.step != oe_steps(q) || f.left != kOeLeftSep || f.right != kOeRightSep) return false;      // the last round's frame sees both separators
+    for (int k = 1; k <= oe_steps(q); ++k) if (oe_frame(q, true, true, oe_left_edge(k)).left != kOeLeftSep || oe_frame(q, true, true, oe_left_edge(k)).step != k) return false;
+  }
+  for (int k = 1; k <= kOeMaxSteps; ++k) if (oe_full(oe_right_edge(k)).right != kOeRightSep || oe_full(oe_right_edge(k)).step != k) return false;
+  return kOeWaves * 2 >= kOeMaxQ + 1 && kOeMaxQ == kChainM - 1;
+}
+static_assert(oe_closed_forms_match(), "the kernels' index arithmetic no longer matches vc_chain_order.hpp");
+__device__ __forceinline__ int oe_image(int i, int side) {
+  const int h = oe_low_bit(i);
+  return h == 1 ? i - 1 + side : (side == 0 ? i - h / 2 : i + h / 2 - 1);
+}
+// The barrier between two rounds waits for LDS only: the wavefront's LDS stores have been performed (lgkmcnt(0); LDS operations of a wavefront
+// execute in order), its global loads and stores stay in flight -- __syncthreads() carries a workgroup-scope fence that waits for the stores of
+// the solved image as well (vc_kutil.hpp: wave_lds_sync_local; the idiom of k_chain_l0's and k_chain_back_path's ready words).  Nothing the
+// wavefronts of a group hand each other goes through global memory: what one stores there is read by later launches, and what it loads (its
+// frames' columns, the left frame's B block) has arrived before its first elimination, a barrier ahead of whoever overwrites it.
+// Measured against __syncthreads() on one box: the levels the same, the top level's launch 12.3 against 13.0 us.
+__device__ __forceinline__ void oe_round_barrier() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_s_waitcnt(0xc07f);          // lgkmcnt(0)
+  __builtin_amdgcn_s_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+__device__ __forceinline__ void chain_oe_group(const DevView& v, int s, int lvl, int top, int group, double* lds) {
+  const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+  const int N = v.n_frames, D = v.D, ldw = v.ldw, ldx = v.ldx, nW = D + 1, ncol = nW + 27;
+  const long gs = (long)kChainM * s;
+  const int a = top ? -1 : (int)((long)group * gs), first = top ? 0 : a + s;
+  const int done = v.ctrl->done;
+  if (lvl == 1 && blockIdx.x == 0 && threadIdx.x == 0) signal_started(v, 7);      // the bottom level is complete: this launch runs (the weight update waits for it)
+  const bool pend = lvl > 0;
+  const double* rp = v.rX[(lvl + 1) & 1];
+  double* rw = v.rX[lvl & 1];
+  const size_t isz = (size_t)9 * ldx;
+  const int c = lane, e0 = c - nW;
+  const int role = c < nW ? 0 : (e0 < 9 ? 1 : e0 < 18 ? 2 : e0 < 27 ? 3 : 4);     // 0 border (W | g), 1 C, 2 A, 3 B, 4 none
+  const int pc = c < nW ? c : (c < ncol ? ldw + e0 : 0);
+  const int sub = e0 < 9 ? e0 : e0 < 18 ? e0 - 9 : e0 - 18;
+  if (first >= N) {            // a separator without interior frames: only its pending right contribution is folded in (uniform over the workgroup)
+    if (!done && wv == 0 && !top && a < N) {
+      double* img = v.cW + (size_t)a * isz + pc;
+      if ((role == 0 || role == 2) && pend && a > 0) {
+#pragma unroll
+        for (int k = 0; k < 9; ++k) img[k * ldx] += rp[(size_t)(a / s) * isz + k * ldx + pc];
+      } else if (role == 3) {
+#pragma unroll
+        for (int k = 0; k < 9; ++k) img[k * ldx] = 0.0;
+      }
+    }
+    return;
+  }
+  const int q = top ? (N - 1) / s + 1 : min(kOeMaxQ, (N - 1 - first) / s + 1);      // interior frames e_1 .. e_q
+  const int r = first + q * s;
+  const bool has_l = !top, has_r = !top && q == kOeMaxQ && r < N;
+  const int K = oe_steps(q), ilast = oe_last(q), wfin = (ilast - 1) / 2;
+  const int ia = 2 * wv + 1, ib = 2 * wv + 2;                 // this wavefront's frames: round 1, and a later round
+  const bool have_a = ia <= q, have_b = ib <= q;
+  const int sb = oe_frame(q, has_l, has_r, ib).step;
+  double* XS = lds + wv * kOeWaveLds; double* An = XS + 9 * kXsLd; double* Ls = An + 81;
+  double* IMG = lds + kOeWaves * kOeWaveLds;
+  // frame i of the group is base + i s; its pending image (the level below left it for a right separator) is number pq + i
+  const int base = top ? -s : a, pq = top ? -1 : group * kChainM;
+  const unsigned ldxb = 8u * (unsigned)ldx, iszb = 9u * ldxb;
+  // (k_chain_fwd2's load pattern: one byte offset per lane -- first entry c0b, step stb -- from wave-uniform bases.  A frame of round 1 reads
+  //  its own border, A and B columns and, as its coupling to the left, the row of the left frame's B block; a frame of a later round only
+  //  border and A: its couplings arrive as fill-in)
+  auto load_cols = [&](int i, bool round1, double* x) {
+    const int e = base + i * s;
+    const bool has_left = i > 1 || has_l;
+    const bool tr = round1 && role == 1;                      // the left frame's B block, transposed
+    const unsigned c0b = tr ? 8u * (unsigned)(sub * ldx + ldw + 18) : 8u * (unsigned)pc, stb = tr ? 8u : ldxb;
+    const unsigned fb = (unsigned)((tr && has_left) ? e - s : e) * iszb, pb = (unsigned)(pq + i) * iszb;
+    const bool live0 = role == 0 || role == 2 || (round1 && (role == 3 || (role == 1 && has_left)));
+    const bool live1 = pend && e > 0 && (role == 0 || role == 2);
+    double y0[9], y1[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) y0[k] = ld_boff(v.cW, fb + c0b + k * stb);
+    if (pend) {
+#pragma unroll
+      for (int k = 0; k < 9; ++k) y1[k] = ld_boff(rp, pb + c0b + k * stb);
+    } else {
+#pragma unroll
+      for (int k = 0; k < 9; ++k) y1[k] = 0.0;
+    }
+#pragma unroll
+    for (int k = 0; k < 9; ++k) x[k] = (live0 ? y0[k] : 0.0) + (live1 ? y1[k] : 0.0);
+  };
+  double xa[9], xb[9], sep0[9];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) { xa[k] = 0.0; xb[k] = 0.0; sep0[k] = 0.0; }
+  // all of the wavefront's columns are requested now; so is what the left separator will absorb into (nobody else writes it during this level)
+  if (have_a) load_cols(ia, true, xa);
+  if (have_b) load_cols(ib, false, xb);
+  // (every wavefront, branch-free like load_cols: behind a condition the compiler turned these into nine dependent round trips, each with a
+  //  wait for everything in flight, at the head of the wavefront the last round depends on)
+  {
+    const bool pa = pend && a > 0, mine = has_l && wv == wfin && (role == 0 || role == 1);
+    const int pcd = role == 1 ? ldw + 9 + sub : pc;
+    const unsigned c0b = 8u * (unsigned)pcd;
+    const unsigned ab = (unsigned)(has_l ? a : 0) * iszb, pab = (unsigned)(has_l ? a / s : 0) * iszb;
+    double y0[9], y1[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) y0[k] = ld_boff(v.cW, ab + c0b + k * ldxb);
+    if (pend) {
+#pragma unroll
+      for (int k = 0; k < 9; ++k) y1[k] = ld_boff(rp, pab + c0b + k * ldxb);
+    } else {
+#pragma unroll
+      for (int k = 0; k < 9; ++k) y1[k] = 0.0;
+    }
+#pragma unroll
+    for (int k = 0; k < 9; ++k) sep0[k] = mine ? y0[k] + (pa ? y1[k] : 0.0) : 0.0;
+  }
+  if (done) return;                      // (uniform over the workgroup: ahead of every barrier)
+  const ElimLds elds = {XS, An, Ls};
+  double out[18];
+#pragma unroll
+  for (int k = 0; k < 18; ++k) out[k] = 0.0;
+  // EVERY wavefront runs every round and meets every barrier, with or without a frame of its own
+  for (int st = 1; st <= K; ++st) {
+    if (st > 1) {
+      oe_round_barrier();                // the images of round st - 1 are complete
+      if (have_b && sb >= st) {
+        // e_ib receives from the two frames of round st - 1 beside it: left source (its right-going image), then right source (its left-going one)
+        const int hs = 1 << (st - 2), il = ib - hs, ir = ib + hs;
+        const bool has_rs = ir <= q, fin = sb == st;
+        const double* L = IMG + oe_image(il, 1) * kOeSlot + c;
+        const double* R = IMG + oe_image(has_rs ? ir : il, 0) * kOeSlot + (role == 2 ? c - 9 : c);      // (A's columns: the right source's C lanes carry their update)
+        double fl[9], fr[9];           // (all eighteen reads first, then selects: no branch per role, one LDS round trip)
+#pragma unroll
+        for (int k = 0; k < 9; ++k) { fl[k] = L[k * 64]; fr[k] = R[k * 64]; }
+#pragma unroll
+        for (int k = 0; k < 9; ++k) {
+          const double l = fl[k], r = has_rs ? fr[k] : 0.0;
+          const double acc = (xb[k] - l) - r;                 // border and A: left source, then right source
+          const double cpl = role == 1 ? -l : -r;             // coupling to the left / right neighbour: that side's fill-in of the round before
+          xb[k] = (role == 0 || role == 2) ? acc : ((fin && (role == 1 || role == 3)) ? cpl : 0.0);
+        }
+      }
+    }
+    const int i = st == 1 ? (have_a ? ia : 0) : ((have_b && sb == st) ? ib : 0);      // wave-uniform; 0: nothing to eliminate this round
+    if (i > 0) {
+      double x[9];
+#pragma unroll
+      for (int k = 0; k < 9; ++k) x[k] = st == 1 ? xa[k] : xb[k];
+      if (role == 2) {
+#pragma unroll
+        for (int k = 0; k < 9; ++k) An[k * 9 + sub] = x[k];
+      }
+      chain_eliminate<false>(v, v.cW + (size_t)(base + i * s) * isz, ldx, role, pc, sub, c == 0, elds, x, out);
+      if (i != ilast) {
+        double* L = IMG + oe_image(i, 0) * kOeSlot + c;
+        double* R = IMG + oe_image(i, 1) * kOeSlot + c;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) { L[k * 64] = out[k]; R[k * 64] = out[9 + k]; }
+      }
+    }
+  }
+  // ---- the last round's wavefront: out is e_ilast's; the separators' updates in round order
+  if (wv != wfin || !has_l) return;
+  double dl_[9], dr_[9];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) { dl_[k] = 0.0; dr_[k] = 0.0; }
+  for (int st = 1; st < K; ++st) {
+    const double* L = IMG + oe_image(oe_left_edge(st), 0) * kOeSlot + c;
+    const double* R = IMG + oe_image(oe_right_edge(st), 1) * kOeSlot + c;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) { dl_[k] += L[k * 64]; if (has_r) dr_[k] += R[k * 64]; }
+  }
+  if (has_r && role < 4) {               // the right separator's side image
+    double* ri = rw + (size_t)(r / gs) * isz + pc;
+    const bool keep = role == 0 || role == 2;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) ri[k * ldx] = keep ? -(dr_[k] + out[9 + k]) : 0.0;
+  }
+  if (role == 3) {                       // the separator's coupling to the right separator at the next level (none where the chain ends)
+    double* img = v.cW + (size_t)a * isz + pc;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) img[k * ldx] = has_r ? -out[k] : 0.0;
+  }
+  if (role == 0 || role == 1) {          // the left separator absorbs its group (the C lanes carry the update of A's columns)
+    const int pcd = role == 1 ? ldw + 9 + sub : pc;
+    double* img = v.cW + (size_t)a * isz + pcd;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) img[k * ldx] = sep0[k] - (dl_[k] + out[k]);
+  }
+}
 // ---- bottom level with the chain assembly folded in (round 5; verdict r3 / r4 item 1a) ---------------------------------------------------
 // One workgroup of FOUR wavefronts per group of 8 frames [a | e_1 .. e_7 | (r)]: wavefronts 0 / 1 are k_chain_fwd2<1>'s two sweeps,
 // wavefronts 2 / 3 are BUILDERS that do k_chain_init's work for the group's frames in the order the sweeps need them (builder 2: the left
@@ -2435,7 +2660,61 @@ constexpr int kBackT0Frames = 1;      // frames per extra workgroup of the top-l
 // polls the two ready words and takes the steps with device-coherent loads: no fence, no cache write-back (the pattern of the
 // cross-stream hand-overs).  Workgroups are laid out top level first: a group only ever waits for workgroups with a
 // smaller index, which the dispatcher has started before it.
-struct BackLevels { int n; int start[8]; int stride[8]; int m[8]; int two[8]; };
+struct BackLevels { int n; int start[8]; int stride[8]; int m[8]; int two[8] /* 0 one sweep, 1 two sweeps, 2 odd-even */; };
+// The dependent chain of a group that was eliminated odd-even (k_chain_oe, the top level; vc_chain_order.hpp): the last round first, every
+// frame from its two neighbours of elimination time, y_i = t0_i + X_s,i d_left(i) + X_n,i d_right(i), L_i^T x = y_i, d_i = -x.  The frames of
+// one round are independent chains of 9 x 9 products and triangular solves, interleaved instruction by instruction as the two sides of a
+// two-sided group are.  lane = 9 fi + k: row k of interior frame fi + 1; t = t0 (WITHOUT the separator's term); da / dr: the separators'
+// steps (zero where there is none).  The full group's order with compile-time indices, one slot per position 0 (a), 1 .. 7, 8 (r): frames
+// beyond q stay zero, which is what "nobody on that side" means.
+__device__ __forceinline__ double chain_back_oe(int q, int fi, int k, double t, const double* Xs, const double* Qrow, const double* Lcol, double dinv,
+                                                const double* da, const double* dr) {
+  double d[kOeMaxQ + 2][9];
+#pragma unroll
+  for (int j = 0; j < 9; ++j) {
+    d[0][j] = da[j]; d[kOeMaxQ + 1][j] = dr[j];
+#pragma unroll
+    for (int i = 1; i <= kOeMaxQ; ++i) d[i][j] = 0.0;
+  }
+  double my = 0.0;
+#pragma unroll
+  for (int st = kOeMaxSteps; st >= 1; --st) {
+    const int h = 1 << (st - 1);                                // the round's frames: h, 3 h, 5 h, .. (up to four)
+    if (h <= q) {                                               // (wave-uniform)
+      double y[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int i = h * (2 * u + 1);
+        y[u] = t;
+        if (i <= kOeMaxQ) {
+          const OeFrame f = oe_full(i);
+#pragma unroll
+          for (int c = 0; c < 9; ++c) y[u] += Xs[c] * d[oe_slot(f.left)][c] + Qrow[c] * d[oe_slot(f.right)][c];
+        }
+      }
+#pragma unroll
+      for (int j = 8; j >= 0; --j) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const int i = h * (2 * u + 1);
+          if (i <= kOeMaxQ) {
+            const double xj = readlane_f64(y[u] * dinv, (i - 1) * 9 + j);
+            if (i <= q) { d[i][j] = -xj; y[u] -= Lcol[j] * xj; }
+          }
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int i = h * (2 * u + 1);
+        if (i <= kOeMaxQ && i <= q && fi == i - 1) {
+#pragma unroll
+          for (int j = 0; j < 9; ++j) my = (j == k) ? d[i][j] : my;
+        }
+      }
+    }
+  }
+  return my;
+}
 template <bool FUSED>
 __device__ __forceinline__ void chain_back_group(const DevView& v, int s, int m, int top, int lvl, int two, int group, double* ds, double* dl) {
   const int done = v.ctrl->done;        // looked at once the level's inputs have been requested (see k_chain_fwd)
@@ -2462,7 +2741,8 @@ __device__ __forceinline__ void chain_back_group(const DevView& v, int s, int m,
   const int e = first + (mine ? fi : 0) * s;
   // a group eliminated from both ends (k_chain_fwd2: full groups of a level launched two-sided): frames right of the middle hang
   // on the right separator and on the frame to their left
-  const bool two_sided = two && !top && q >= 1;
+  const bool two_sided = two == 1 && !top && q >= 1;
+  const bool oe = two == 2;                                      // eliminated odd-even (k_chain_oe / the top level): chain_back_oe
   const int fmid = (q - 1) / 2;                                  // lane group of the middle frame (interior index fmid + 1)
   double t = 0.0, dinv = 1.0, Qrow[9], Lcol[9];
 #pragma unroll
@@ -2484,7 +2764,7 @@ __device__ __forceinline__ void chain_back_group(const DevView& v, int s, int m,
   }
   double Xs[9];
 #pragma unroll
-  for (int c = 0; c < 9; ++c) Xs[c] = (mine && a >= 0) ? v.cW[(size_t)e * isz + (size_t)k * ldx + ldw + c] : 0.0;
+  for (int c = 0; c < 9; ++c) Xs[c] = (mine && (a >= 0 || oe)) ? v.cW[(size_t)e * isz + (size_t)k * ldx + ldw + c] : 0.0;      // (oe: the left NEIGHBOUR's coupling, the top level's frames too)
   if (done) return;
   if (FUSED) {
     // everything else is on its way: now the separators' steps (the levels above publish them, see the kernel's header)
@@ -2510,7 +2790,7 @@ __device__ __forceinline__ void chain_back_group(const DevView& v, int s, int m,
       dn[k2] = has_r ? __hip_atomic_load(v.cdelta + (size_t)r * 9 + k2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0;
     }
   }
-  if (mine && a >= 0) {
+  if (mine && a >= 0 && !oe) {
     const bool right = two_sided && fi > fmid;
 #pragma unroll
     for (int c = 0; c < 9; ++c) t += Xs[c] * (right ? dn[c] : da[c]);       // (dn: still the right separator's step here)
@@ -2521,7 +2801,8 @@ __device__ __forceinline__ void chain_back_group(const DevView& v, int s, int m,
 #endif
   BSTAMP(2);
   double my = 0.0;
-  if (two_sided) {
+  if (oe) my = chain_back_oe(q, fi, k, t, Xs, Qrow, Lcol, dinv, da, dn);
+  else if (two_sided) {
     // the middle first (a on its left, r on its right), then outwards on both sides at once: two independent chains of 9 x 9
     // products and triangular solves, interleaved instruction by instruction
     {
@@ -2724,7 +3005,7 @@ __global__ __launch_bounds__(64) void k_chain_back_levels(DevView v, BackLevels 
 // the rows of the recomputed levels in every bottom group then costs more than a launch -- measured 218 us against 71 for the level-by-level
 // kernels at 6250 frames x D = 115, 120 us with t0 from its own launch); a pinned frame (separator / ghost of a sharded chain,
 // DevView::pin_first / pin_last) steps with the reduced system's solution in the epilogue.
-struct BackPath { int n; int stride[6]; int m[6]; int two[6]; int top_stride; int ldr; int dsw; int tail; };
+struct BackPath { int n; int stride[6]; int m[6]; int two[6] /* 0 one sweep, 1 two sweeps, 2 odd-even */; int oe_top; int top_stride; int ldr; int dsw; int tail; };
 // (round 6) the launch's LAST workgroup, when BackPath::tail is set, is not a bottom group: it forms what k_reduced left out
 // (DevView::tail_deferred) -- the trial cameras and the shared parameters' terms of the step scalars -- beside the back-substitution
 // instead of at the end of a one-workgroup kernel the whole chip waits for.  The first 256 threads; LDS: kTailLds doubles.
@@ -2783,7 +3064,7 @@ __global__ __launch_bounds__(64 * NWMAX) void k_chain_back_path(DevView v, BackP
   const size_t isz = (size_t)9 * ldx;
   const bool top = wv == P.n;
   const int lvl = top ? P.n : wv;
-  const int s = top ? P.top_stride : P.stride[lvl], m = top ? kChainM : P.m[lvl], two = top ? 0 : P.two[lvl];
+  const int s = top ? P.top_stride : P.stride[lvl], m = top ? kChainM : P.m[lvl], two = top ? (P.oe_top ? 2 : 0) : P.two[lvl];
   const long gs = (long)m * s;
   const long a0 = (long)blockIdx.x * P.m[0] * P.stride[0];        // the bottom group's left separator
   const int a = top ? -1 : (int)((a0 / gs) * gs);
@@ -2794,7 +3075,8 @@ __global__ __launch_bounds__(64 * NWMAX) void k_chain_back_path(DevView v, BackP
   const int fi = lane / 9, k = lane % 9;
   const bool mine = fi < q;
   const int e = first + (mine ? fi : 0) * s;
-  const bool two_sided = two && !top && q >= 1;
+  const bool two_sided = two == 1 && !top && q >= 1;
+  const bool oe = two == 2;
   const int fmid = (q - 1) / 2;
   // ---- requests: the rows [Y | z] of the group's frames (lane-strided, coalesced; narrow borders only -- CT0: t0 comes finished from
   // k_chain_t0), then this lane's blocks
@@ -2825,7 +3107,7 @@ __global__ __launch_bounds__(64 * NWMAX) void k_chain_back_path(DevView v, BackP
 #pragma unroll
     for (int c = 0; c < 9; ++c) {
       const double qv = Wr[ldw + 18 + c], lv = img[c * ldx + ldw + 9 + k], xv = Wr[ldw + c];
-      Qrow[c] = mine ? qv : 0.0; Lcol[c] = (mine && c > k) ? lv : 0.0; Xs[c] = (mine && a >= 0) ? xv : 0.0;
+      Qrow[c] = mine ? qv : 0.0; Lcol[c] = (mine && c > k) ? lv : 0.0; Xs[c] = (mine && (a >= 0 || oe)) ? xv : 0.0;
     }
     const double dg = Wr[ldw + 9 + k];
     dinv = mine ? 1.0 / dg : 1.0;
@@ -2872,13 +3154,14 @@ __global__ __launch_bounds__(64 * NWMAX) void k_chain_back_path(DevView v, BackP
   }
 #pragma unroll
   for (int c = 0; c < 9; ++c) dr_in[c] = dn[c];
-  if (mine && a >= 0) {
+  if (mine && a >= 0 && !oe) {
     const bool right = two_sided && fi > fmid;
 #pragma unroll
     for (int c = 0; c < 9; ++c) t += Xs[c] * (right ? dn[c] : da[c]);       // (dn: still the right separator's step here)
   }
   double my = 0.0;
-  if (two_sided) {
+  if (oe) my = chain_back_oe(q, fi, k, t, Xs, Qrow, Lcol, dinv, da, dn);
+  else if (two_sided) {
     {
       double y = t;
 #pragma unroll
@@ -3111,13 +3394,15 @@ __global__ __launch_bounds__(256, 2) void k_chain_gram(DevView v, int gather) {
 // borders, the chip idle beside it) and, in the same launch, the Gram sums of every frame below it -- final since the launch before:
 // workgroup 0 eliminates, workgroups 1 .. n_chunks are k_chain_gram's with the top level's frames masked out (DevView::gram_top_stride).
 template <int NW, int NQ, int NL>
-__global__ __launch_bounds__(256) void k_chain_top_gram(DevView v, int s, int m, int lvl) {
+__global__ __launch_bounds__(256) void k_chain_top_gram(DevView v, int s, int m, int lvl, int oe) {
   extern __shared__ __attribute__((aligned(16))) double R[];    // 36 x ld
   __shared__ unsigned short s_pair[128];
   __shared__ __attribute__((aligned(16))) double XS[9 * kXsLd];
   __shared__ double An[81];
   __shared__ double Ls_all[NW * 81];
   if (blockIdx.x == 0) {
+    // (oe: the top level's frames odd-even on all four wavefronts -- the launcher sized R for it, ChainPlan::oe_top)
+    if (NW == 1 && oe) { chain_oe_group(v, s, lvl, 1, 0, R); return; }
     if ((int)threadIdx.x >= 64 * NW) return;      // (a barrier counts the wavefronts that are still there)
     chain_fwd_group<1, NW>(v, s, m, 1, lvl, 0, (int)(threadIdx.x >> 6), XS, An, Ls_all);
     return;
@@ -3128,6 +3413,15 @@ __global__ __launch_bounds__(256) void k_chain_top_gram(DevView v, int s, int m,
   // ... and behind that one (flag hand-overs, DevView::part_ride): the fixed-order sums of the chunk records, k_part_sum's work without its launch
   if ((int)blockIdx.x > 1 + v.n_chunks) { part_sum_ride_job(v, (int)blockIdx.x - 2 - v.n_chunks, R); return; }
   chain_gram_chunk<NQ, NL>(v, (int)blockIdx.x - 1, R, s_pair, v.gram_top_stride, 0, v.part_ride != 0);
+}
+
+// one level of the odd-even elimination (chain_oe_group): a workgroup per group, one wavefront per SIMD; the workgroups behind the groups
+// carry the level-1 side job (see k_chain_fwd2)
+__global__ __launch_bounds__(256) void k_chain_oe(DevView v, int s, int lvl, int top, int n_groups) {
+  __shared__ __attribute__((aligned(16))) double oe_lds[kOeLds];
+  // (the side job on the first two wavefronts only, as under k_chain_fwd2<1>: 8 slices per entry, the same fixed order with the switch on and off)
+  if ((int)blockIdx.x >= n_groups) { if (threadIdx.x < 128) part_tail_sum_job(v, (int)blockIdx.x - n_groups, oe_lds, 128); return; }
+  chain_oe_group(v, s, lvl, top, (int)blockIdx.x, oe_lds);
 }
 
 // ------------------------------------------------------------------------------------------ launchers
@@ -3155,9 +3449,12 @@ static void chain_levels(const DevView& v, const ChainPlan& p, hipStream_t s, bo
   // four columns -- were kept for A/B runs until round 6 and are gone)
   // narrow borders: the levels ChainPlan::two marks are eliminated from both ends (k_chain_fwd2: 4 dependent eliminations per level instead of 7)
   auto fwd = [&](int groups, int stride, int m, int top, int lvl) {
-    if (!top && p.two[lvl]) {
-      // (hadd_early: the first launch above the bottom level carries the sums of the chunk records' entries behind S and g_red)
-      const int extra = (v.hadd_early && lvl == 1) ? (v.part_stride - (v.D * v.D + v.D) + 15) / 16 : 0;
+    // (hadd_early: the first launch above the bottom level carries the sums of the chunk records' entries behind S and g_red)
+    const int extra = (!top && v.hadd_early && lvl == 1) ? (v.part_stride - (v.D * v.D + v.D) + 15) / 16 : 0;
+    if (top ? p.oe_top : p.oe[lvl]) {      // odd-even inside a workgroup of four wavefronts (k_chain_oe: 3 dependent eliminations instead of 4)
+      hipLaunchKernelGGL(k_chain_oe, dim3(groups + extra), dim3(256), 0, s, v, stride, lvl, top, groups);
+    }
+    else if (!top && p.two[lvl]) {
       if (cpl <= 1) hipLaunchKernelGGL(k_chain_fwd2<1>, dim3(groups + extra), dim3(128), 0, s, v, stride, m, lvl, groups);
       else hipLaunchKernelGGL(k_chain_fwd2<2>, dim3(groups + extra), dim3(256), 0, s, v, stride, m, lvl, groups);
     }
@@ -3175,13 +3472,14 @@ static void chain_levels(const DevView& v, const ChainPlan& p, hipStream_t s, bo
     }
     if (v.gram_top_stride > 0) {
       // early Gram: the top level's one group and the Gram sums of all frames below it in one launch
-      const size_t lds = std::max((size_t)36 * v.ldw, (size_t)(v.hadd_early ? kHaddLds : 0)) * sizeof(double);      // (>= 512 doubles: part_sum_ride_job)
+      const size_t lds_gram = std::max((size_t)36 * v.ldw, (size_t)(v.hadd_early ? kHaddLds : 0)) * sizeof(double);      // (>= 512 doubles: part_sum_ride_job)
+      const size_t lds = std::max(lds_gram, (size_t)(p.oe_top ? kOeLds : 0) * sizeof(double));      // (the odd-even top group's images: below the default limit)
       const int ride_blocks = (v.part_ride && v.hadd_early) ? (v.D * v.D + v.D + 15) / 16 : 0;
       const int nT = (v.D + 1 + 15) / 16, nPairs = nT * (nT + 1) / 2, nq = std::min(kMaxPairsPerWaveI, (nPairs + 3) / 4);
       const int nlr = (36 * v.ldw + 255) / 256;
       auto go = [&](auto kern) {
-        if (lds > 40000) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(kern, dim3(1 + v.n_chunks + (v.hadd_early ? 1 : 0) + ride_blocks), dim3(256), lds, s, v, top_stride, m_top, nl);
+        if (lds_gram > 40000) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipLaunchKernelGGL(kern, dim3(1 + v.n_chunks + (v.hadd_early ? 1 : 0) + ride_blocks), dim3(256), lds, s, v, top_stride, m_top, nl, p.oe_top);
       };
       // (wavefronts of the top group by the border's width, Gram instance by the row image's size: the pairs that occur)
       if (cpl <= 1) { if (nq <= 1) go(k_chain_top_gram<1, 1, 7>); else go(k_chain_top_gram<1, 2, 7>); }
@@ -3195,9 +3493,9 @@ static void chain_levels(const DevView& v, const ChainPlan& p, hipStream_t s, bo
     // the whole back-substitution as one launch without hand-overs (k_chain_back_path): any border width, sharded passes included
     if (v.back_path && nl >= 1 && nl <= 5) {
       BackPath P; P.n = nl;
-      for (int l = 0; l < 6; ++l) { P.stride[l] = l < nl ? p.stride[l] : 1; P.m[l] = l < nl ? p.m[l] : 2; P.two[l] = l < nl ? p.two[l] : 0; }
+      for (int l = 0; l < 6; ++l) { P.stride[l] = l < nl ? p.stride[l] : 1; P.m[l] = l < nl ? p.m[l] : 2; P.two[l] = l < nl ? (p.oe[l] ? 2 : p.two[l]) : 0; }
       const bool ct0 = v.D + 1 > kPathRowCols;
-      P.top_stride = top_stride; P.ldr = ct0 ? 1 : ((v.D + 1) | 1); P.dsw = ((v.D + 63) / 64) * 64;
+      P.oe_top = p.oe_top; P.top_stride = top_stride; P.ldr = ct0 ? 1 : ((v.D + 1) | 1); P.dsw = ((v.D + 63) / 64) * 64;
       if (ct0) hipLaunchKernelGGL(k_chain_t0, dim3((N + 3) / 4), dim3(256), 0, s, v);
       const int nw = nl + 1;
       P.tail = (v.tail_deferred && nw >= 4) ? 1 : 0;
@@ -3211,7 +3509,7 @@ static void chain_levels(const DevView& v, const ChainPlan& p, hipStream_t s, bo
       else { if (ct0) go(k_chain_back_path<6, true>, g6); else go(k_chain_back_path<6, false>, g6); }
       return;
     }
-    hipLaunchKernelGGL(k_chain_back, dim3(1 + (nl > 0 ? (N + kBackT0Frames - 1) / kBackT0Frames : 0)), dim3(64), 0, s, v, top_stride, m_top, 1, nl, 0);
+    hipLaunchKernelGGL(k_chain_back, dim3(1 + (nl > 0 ? (N + kBackT0Frames - 1) / kBackT0Frames : 0)), dim3(64), 0, s, v, top_stride, m_top, 1, nl, p.oe_top ? 2 : 0);
     // the levels below: one launch (k_chain_back_levels: ready words instead of kernel boundaries)
     // (only while every workgroup of the launch can be resident at once -- 119 registers, 4 wavefronts per SIMD, 4096 on the chip; half of
     //  that here: a group that waits for its separators then never keeps a producer from starting, whatever order the dispatcher picks)
@@ -3230,14 +3528,14 @@ static void chain_levels(const DevView& v, const ChainPlan& p, hipStream_t s, bo
       int at = 0;
       for (int i = 0; i < nl; ++i) {
         const int l = nl - 1 - i;
-        L.start[i] = at; L.stride[i] = p.stride[l]; L.m[i] = p.m[l]; L.two[i] = p.two[l];
+        L.start[i] = at; L.stride[i] = p.stride[l]; L.m[i] = p.m[l]; L.two[i] = p.oe[l] ? 2 : p.two[l];
         at += p.groups[l];
       }
       for (int i = nl; i < 8; ++i) { L.start[i] = 1 << 30; L.stride[i] = 1; L.m[i] = 2; L.two[i] = 0; }
       hipLaunchKernelGGL(k_chain_back_levels, dim3(at), dim3(64), 0, s, v, L);
     } else
     for (int l = nl - 1; l >= 0; --l)
-      hipLaunchKernelGGL(k_chain_back, dim3(p.groups[l]), dim3(64), 0, s, v, p.stride[l], p.m[l], 0, l, p.two[l]);
+      hipLaunchKernelGGL(k_chain_back, dim3(p.groups[l]), dim3(64), 0, s, v, p.stride[l], p.m[l], 0, l, p.oe[l] ? 2 : p.two[l]);
   }
 }
 void launch_chain_init(const DevView& v, hipStream_t s) {

@@ -29,7 +29,7 @@ SYMBOLS = [
     "vc_get_biases", "vc_get_scale_factor", "vc_get_gravity", "vc_time_offset", "vc_mean_squared_error", "vc_get_camera_proj_rmse",
     "vc_get_num_iterations", "vc_num_imu_measurements", "vc_get_imu_measurements", "vc_get_integration_poses", "vc_print_results", "vc_write_camera_models", "vc_trace_len", "vc_get_trace", "vc_set_shard", "vc_get_stream", "vc_prepare",
     "vc_linearize", "vc_step_hold", "vc_shared_dim", "vc_run_iterations", "vc_download_state", "vc_evaluate", "vc_time_kernels", "vc_time_stages", "vc_get_imu_blocks", "vc_get_debug_stamps", "vc_num_observations", "vc_num_tiles",
-    "vc_init_frame_poses_pnp", "vc_pnp_planar", "vc_pnp_planar_ransac", "vc_set_pnp_ransac", "vc_rccl_unique_id", "vc_set_shard_rccl", "vc_shard_comm_create", "vc_set_shard_comm", "vc_shard_comm_destroy", "vc_allreduce_calls", "vc_shard_info", "vc_pass_paths", "vc_last_error", "vc_get_imu_weights",
+    "vc_init_frame_poses_pnp", "vc_pnp_planar", "vc_pnp_planar_ransac", "vc_set_pnp_ransac", "vc_rccl_unique_id", "vc_set_shard_rccl", "vc_shard_comm_create", "vc_set_shard_comm", "vc_shard_comm_destroy", "vc_allreduce_calls", "vc_shard_info", "vc_pass_paths", "vc_chain_order", "vc_last_error", "vc_get_imu_weights",
     "vc_solution_covariance_dim", "vc_get_solution_covariance", "vc_get_solution_covariance_names",
     "vc_target_make_pattern", "vc_target_find",
     "vc_report_compute", "vc_report_num_corners", "vc_report_corners", "vc_report_num_views", "vc_report_views", "vc_report_error_map", "vc_report_num_imu_blocks", "vc_report_imu", "vc_time_report_sweeps",
@@ -364,6 +364,12 @@ class ViCalibrator:
         out = (C.c_int * 6)()
         _check(self.L.vc_pass_paths(self.h, out), "pass_paths")
         return dict(fold_l0=out[0], back_path=out[1], early_gram=out[2], top_gram_launch=out[3], tail_deferred=out[4], shared_blocks_ahead=out[5])
+
+    def chain_order(self):
+        """Which levels of the chain elimination the uploaded problem eliminates odd-even inside a workgroup (vc_chain_order)."""
+        n, top, oe = C.c_int(0), C.c_int(0), (C.c_int * 16)()
+        _check(self.L.vc_chain_order(self.h, C.byref(n), oe, 16, C.byref(top)), "chain_order")
+        return dict(n_levels=n.value, oe=[int(oe[l]) for l in range(n.value)], oe_top=top.value)
 
     def shard_info(self):
         """rank / world size the calibrator shards with and, for the library's own communicator, what RCCL reports (-1: none attached)."""
