@@ -155,6 +155,12 @@ static void DefineFlags() {
   Define("uncertainty_fit_radius", "double", "0.5", "The absorbed rotation is fitted over the samples within this fraction of the half-diagonal of the image centre (<= 0: no rotation is removed).");
   Define("uncertainty_rings", "int32", "8", "Rings of equal width in normalised radius in uncertainty_summary.csv, 1 ... 64.");
   Define("uncertainty_noise", "double", "0", "Detection noise in px per coordinate that scales the covariance; 0 = the camera's own reprojection RMSE.");
+  Define("select_views", "string", "", "Behind a calibration, select this many of the calibrated frames by greedy D-optimal view selection (the log-determinant of the "
+         "information on the shared vision parameters, every frame's pose marginalised) with the result's cameras and poses; needs -select_dir and -gpus 1.");
+  Define("select_dir", "string", "", "Directory for selected_views.csv (rank, frame, gain, cum, share), select_frames.csv (frame, status, corners, behind, first-round gain) and, with "
+         "-holdout_every, select_holdout.csv (the held-out frames scored as candidates against the calibrated frames as start set).");
+  Define("select_prior", "double", "1e-6", "The prior on every scaled shared column that keeps the first log-determinants finite, > 0.");
+  Define("select_start", "string", "", "Frames the selection starts from, f0,f1,... (frame numbers of the recording, each one of the calibrated frames).");
   Define("convert_grid", "string", "64x48", "Lattice of the conversion, GXxGY: 2 ... image width by 2 ... image height, at most 2^22 samples.");
   Define("convert_fit_radius", "double", "1", "The target model is fitted over the samples within this fraction of the half-diagonal of the image centre (> 0; 1 = the whole image).");
 }
@@ -999,6 +1005,113 @@ static bool UncertaintyOutputs(const std::vector<vic::CameraAndPose>& cams, cons
   return ok;
 }
 
+// ---- -select_views K -select_dir DIR: the most informative of the calibrated frames (vc_selector*) -----------------------------------------
+struct SelectOptions { int k = 0; std::string dir; double prior = 1e-6; std::vector<long> start; };
+static bool SelectFlags(SelectOptions* o, std::string* err) {
+  const std::string k = FlagString("select_views");
+  o->dir = FlagString("select_dir");
+  if (k.empty()) {
+    if (!o->dir.empty() || !FlagString("select_start").empty()) { *err = "-select_dir and -select_start need -select_views"; return false; }
+    return true;
+  }
+  char* end = nullptr;
+  const long kv = std::strtol(k.c_str(), &end, 10);
+  if (end == k.c_str() || *end != '\0' || kv < 1 || kv > (1 << 30)) { *err = "illegal value '" + k + "' specified for flag 'select_views': expected a number of views >= 1"; return false; }
+  o->k = (int)kv;
+  if (o->dir.empty()) { *err = "-select_views needs -select_dir"; return false; }
+  if (FlagInt("gpus") > 1) { *err = "-select_views needs -gpus 1: the selection runs over the frames of one calibrator"; return false; }
+  {
+    std::string parent = o->dir;
+    while (parent.size() > 1 && parent.back() == '/') parent.pop_back();
+    const size_t slash = parent.rfind('/');
+    parent = slash == std::string::npos ? "." : (slash == 0 ? "/" : parent.substr(0, slash));
+    struct stat st;
+    if (!(stat(parent.c_str(), &st) == 0 && S_ISDIR(st.st_mode))) { *err = "the parent directory of -select_dir " + o->dir + " does not exist"; return false; }
+  }
+  o->prior = FlagDouble("select_prior");
+  if (!(o->prior > 0.0 && o->prior < 1e300)) { *err = "illegal value for flag 'select_prior': expected a finite prior > 0"; return false; }
+  for (const std::string& tok : Split(FlagString("select_start"), ',')) {
+    const long f = std::strtol(tok.c_str(), &end, 10);
+    if (tok.empty() || end == tok.c_str() || *end != '\0' || f < 0) { *err = "illegal value '" + FlagString("select_start") + "' specified for flag 'select_start': expected f0,f1,..."; return false; }
+    o->start.push_back(f);
+  }
+  return true;
+}
+// The held-out set as the scoring left it (-holdout_every): its tiles, the refitted poses and their status.
+struct SelectHeld { std::vector<int> tile_frame, tile_cam, point_id, status; std::vector<long long> tile_off; std::vector<double> points, T_wk; };
+// Writes the files of -select_dir and prints one line.  frame_ids: the recording's number of every calibrated frame; held_ids / held: the same of the
+// held-out frames, empty without -holdout_every.
+static bool SelectOutputs(vic::ViCalibrator& cal, const std::vector<long>& frame_ids, const std::vector<long>& held_ids, const SelectHeld& held, const SelectOptions& o,
+                          std::string* err) {
+  struct stat st;
+  if (mkdir(o.dir.c_str(), 0777) != 0 && !(stat(o.dir.c_str(), &st) == 0 && S_ISDIR(st.st_mode))) { *err = "cannot create the directory " + o.dir; return false; }
+  const int N = (int)frame_ids.size();
+  std::vector<int> start;
+  for (long f : o.start) {
+    const auto it = std::find(frame_ids.begin(), frame_ids.end(), f);
+    if (it == frame_ids.end() || std::find(start.begin(), start.end(), (int)(it - frame_ids.begin())) != start.end()) {
+      *err = "-select_start: frame " + std::to_string(f) + " is not one of the calibrated frames, or is given twice"; return false;
+    }
+    start.push_back((int)(it - frame_ids.begin()));
+  }
+  vic::Selector sel(cal);
+  sel.Run(1, start, o.prior);
+  const std::vector<double> first = sel.LastGains();
+  const vic::Selection r = sel.Run(o.k, start, o.prior);
+  const vic::SelectionFrames fr = sel.Frames();
+  FILE* f = std::fopen((o.dir + "/selected_views.csv").c_str(), "w");
+  if (!f) { *err = "cannot write into " + o.dir; return false; }
+  std::fprintf(f, "rank,frame,gain,cum,share\n");
+  int n90 = 0, n99 = 0;
+  for (size_t k = 0; k < r.order.size(); ++k) {
+    const double share = r.total > 0.0 ? std::min(1.0, r.cum[k] / r.total) : 1.0;
+    if (!n90 && share >= 0.90) n90 = (int)k + 1;
+    if (!n99 && share >= 0.99) n99 = (int)k + 1;
+    std::fprintf(f, "%zu,%ld,%.10g,%.10g,%.10g\n", k + 1, frame_ids[(size_t)r.order[k]], r.gain[k], r.cum[k], share);
+  }
+  std::fclose(f);
+  f = std::fopen((o.dir + "/select_frames.csv").c_str(), "w");
+  if (!f) { *err = "cannot write into " + o.dir; return false; }
+  std::fprintf(f, "frame,status,corners,behind,first_round_gain\n");
+  int usable = 0;
+  for (int i = 0; i < N; ++i) {
+    usable += fr.status[(size_t)i] != 1 ? 1 : 0;
+    std::fprintf(f, "%ld,%d,%d,%d,%.10g\n", frame_ids[(size_t)i], fr.status[(size_t)i], fr.corners[(size_t)i], fr.behind[(size_t)i], first[(size_t)i]);
+  }
+  std::fclose(f);
+  auto reach = [&](int n) { return n ? std::to_string(n) : "more than " + std::to_string(r.order.size()); };
+  std::printf("selected views: %zu of %d usable frames (%d shared columns); %s reach 90 %%, %s reach 99 %% of the attainable information, log-determinant gain %.6g\n",
+              r.order.size(), usable, sel.Dim(), reach(n90).c_str(), reach(n99).c_str(), r.total);
+  if (held_ids.empty()) return true;
+  // which new view adds most: the held-out frames, at their refitted poses, as candidates against all calibrated frames
+  const int H = (int)held_ids.size();
+  std::vector<int> tile_frame(held.tile_frame);
+  for (int& t : tile_frame) t += N;
+  std::vector<double> poses((size_t)(N + H) * 7);
+  for (int i = 0; i < N; ++i) { const vic::VicalibFrame fi = cal.GetFrame((size_t)i); std::copy(fi.t_wp_.data(), fi.t_wp_.data() + 7, &poses[(size_t)i * 7]); }
+  if (held.T_wk.size() != (size_t)H * 7) { *err = "the held-out frames have no refitted poses"; return false; }
+  std::copy(held.T_wk.begin(), held.T_wk.end(), poses.begin() + (size_t)N * 7);
+  vic::Selector both(cal);
+  both.SetPoses(poses.data(), N + H);
+  both.AddTiles((int)tile_frame.size(), tile_frame.data(), held.tile_cam.data(), held.tile_off.data(), held.points.data(), (int)(held.points.size() / 3), held.point_id.data());
+  std::vector<int> all(N);
+  for (int i = 0; i < N; ++i) all[(size_t)i] = i;
+  both.Run(1, all, o.prior);
+  const std::vector<double> hfirst = both.LastGains();
+  const vic::Selection hr = both.Run(H, all, o.prior);
+  const vic::SelectionFrames hfr = both.Frames();
+  std::vector<int> rank((size_t)H, 0);
+  for (size_t k = 0; k < hr.order.size(); ++k) if (hr.order[k] >= N) rank[(size_t)(hr.order[k] - N)] = (int)k + 1;
+  f = std::fopen((o.dir + "/select_holdout.csv").c_str(), "w");
+  if (!f) { *err = "cannot write into " + o.dir; return false; }
+  std::fprintf(f, "frame,holdout_status,status,corners,behind,first_round_gain,rank\n");
+  for (int i = 0; i < H; ++i)
+    std::fprintf(f, "%ld,%d,%d,%d,%d,%.10g,%d\n", held_ids[(size_t)i], held.status[(size_t)i], hfr.status[(size_t)(N + i)], hfr.corners[(size_t)(N + i)], hfr.behind[(size_t)(N + i)],
+                 hfirst[(size_t)(N + i)], rank[(size_t)i]);
+  std::fclose(f);
+  return true;
+}
+
 int main(int argc, char** argv) {
   DefineFlags();
   std::string err;
@@ -1020,6 +1133,8 @@ int main(int argc, char** argv) {
   }
   UncertaintyOptions uncertainty;
   if (!UncertaintyFlags(&uncertainty, &err)) { std::fprintf(stderr, "ERROR: %s\n", err.c_str()); return 1; }
+  SelectOptions select;
+  if (!SelectFlags(&select, &err)) { std::fprintf(stderr, "ERROR: %s\n", err.c_str()); return 1; }
   // ---- -compare_models a.xml,b.xml: file against file, nothing is calibrated; -compare_to b.xml: read now, compared behind the results
   CompareOptions compare;
   std::vector<vic::CameraAndPose> compare_b;
@@ -1412,6 +1527,7 @@ int main(int argc, char** argv) {
 
   // ---- held-out scoring (-holdout_every): rank 0's calibrator refits the poses of the frames kept out, cameras frozen at the result (the
   // shared parameters are identical on every rank), and reports how well the calibration predicts views it has not seen ---------------------
+  SelectHeld select_held;
   if (!held_ids.empty()) {
     try {
       std::map<long, int> held_index;
@@ -1442,6 +1558,11 @@ int main(int argc, char** argv) {
       cal.HoldoutAddTiles((int)tile_frame.size(), tile_frame.data(), tile_cam.data(), tile_off.data(), points.data(), (int)dets.size(), point_id.data(), pc.data());
       cal.HoldoutCompute(nullptr, 0);
       const vic::ViCalibrator::HoldoutFrames hf = cal.GetHoldoutFrames();
+      if (select.k > 0) {
+        select_held.tile_frame = tile_frame; select_held.tile_cam = tile_cam; select_held.tile_off = tile_off; select_held.point_id = point_id; select_held.points = points;
+        select_held.status = hf.status;
+        for (const vic::Se3& T : hf.T_wk) select_held.T_wk.insert(select_held.T_wk.end(), T.data(), T.data() + 7);
+      }
       const vic::ViCalibrator::HoldoutViews hv = cal.GetHoldoutViews();
       const vic::ViCalibrator::HoldoutCameraRmse hr = cal.GetHoldoutCameraRmse();
       for (size_t c = 0; c < n_cam; ++c) {
@@ -1528,6 +1649,12 @@ int main(int argc, char** argv) {
     if (covs[0].empty()) { std::fprintf(stderr, "E uncertainty map failed: the solution covariance cannot be computed\n"); uncertainty_failed = true; }
     else if (!UncertaintyOutputs(a, covs[0], dims[0], rmse, uncertainty, (int)FlagInt("device"), &err)) { std::fprintf(stderr, "E uncertainty map failed: %s\n", err.c_str()); uncertainty_failed = true; }
   }
+  bool select_failed = false;
+  if (select.k > 0) {                                    // -select_views: the most informative of the calibrated frames, at the result
+    try {
+      if (!SelectOutputs(cal, frame_ids, held_ids, select_held, select, &err)) { std::fprintf(stderr, "E view selection failed: %s\n", err.c_str()); select_failed = true; }
+    } catch (const std::exception& e) { std::fprintf(stderr, "E view selection failed: %s\n", e.what()); select_failed = true; }
+  }
   bool convert_failed = false;
   if (converting) {                                      // -convert_to: the cameras just written, converted
     std::vector<vic::CameraAndPose> a;
@@ -1574,5 +1701,6 @@ int main(int argc, char** argv) {
   if (compare_failed) std::fprintf(stderr, "E -compare_to: the comparison's files are incomplete (exit status %d)\n", success ? 1 : 2);
   if (convert_failed) std::fprintf(stderr, "E -convert_to: the converted rig is incomplete (exit status %d)\n", success ? 1 : 2);
   if (uncertainty_failed) std::fprintf(stderr, "E -uncertainty_dir: the uncertainty map's files are incomplete (exit status %d)\n", success ? 1 : 2);
-  return success ? ((undistort_failed || rectify_failed || compare_failed || convert_failed || uncertainty_failed) ? 1 : 0) : 2;
+  if (select_failed) std::fprintf(stderr, "E -select_views: the selection's files are incomplete (exit status %d)\n", success ? 1 : 2);
+  return success ? ((undistort_failed || rectify_failed || compare_failed || convert_failed || uncertainty_failed || select_failed) ? 1 : 0) : 2;
 }

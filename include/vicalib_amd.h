@@ -612,6 +612,54 @@ int vc_uncertainty_rings(vc_uncertainty* u, int n_rings, long long* count, long 
  * and C, [2] the map sweep, each with its reduction. */
 int vc_time_uncertainty(vc_uncertainty* u, int reps, double out_ms[3]);
 
+/* ---- view selection: which frames carry the information? -----------------------------------------------------------------------------
+ * Greedy D-optimal selection over candidate frames of a rig of up to 8 cameras.  Inputs are where the target was seen, not what was
+ * measured: per camera a model, intrinsics, T_ck and the solver's flags (1 rotation free, 2 translation free, 4 intrinsics free); per
+ * frame a rig pose T_wk and (frame, camera) groups of target points.  Information is taken at unit pixel noise without a robust loss.
+ * The shared columns are the solver's: per camera [w_ck (3)][t_ck (3)][K (nk)] as far as free, cameras in order, D columns in all.
+ * LIMIT: D <= 64; a rig beyond it is refused with VC_ERR_UNSUPPORTED.
+ * Frame information, the frame's pose marginalised: with J = [J_f (2n x 6) | J_s (2n x D)] over the frame's corners (the columns the
+ * solver forms), I_f = J_s^T J_s - J_s^T J_f (J_f^T J_f)^-1 J_f^T J_s.  A corner at camera depth <= 0 (any model but kb4) enters no sum
+ * and is counted as `behind`; it does not count as a corner.  Frame status: 0 usable; 1 underdetermined -- fewer than 4 corners over all
+ * views, or the Cholesky of J_f^T J_f meets a pivot <= 1e-12 x its largest diagonal entry --: I_f = 0, never selected; 2 some corner lay
+ * behind a camera, still usable.  Scaling: s_j = 1 / sqrt(sum_f I_f[j][j]) over usable frames (1 where the sum is 0) and I~_f =
+ * diag(s) I_f diag(s); differences of log-determinants do not depend on it.
+ * Selection: S_0 = prior I + sum over the start set of I~_f.  Round k gives every usable frame not yet in the set gain_k(f) =
+ * logdet(S_{k-1} + I~_f) - logdet(S_{k-1}), picks the largest (the lowest frame on exactly equal gains) and adds it.  It ends after k
+ * picks, when no candidate is left, or when the best gain is <= 0.  cum_k = logdet(S_k) - logdet(S_0); total = logdet(S_0 + sum of I~_f
+ * over every usable frame outside the start set) - logdet(S_0): cum_k / total is the share of the attainable information the first k
+ * views carry.  All rounds run on the device without a host synchronisation between them; two runs on the same input give the same bits.
+ * Accuracy (tests/select_cases.py): the device agrees with a float64 numpy reference to 16 x that reference's own distance from its
+ * long-double evaluation.  A handle is single-threaded with a stream of its own; nothing is allocated on the device before the first run;
+ * no CPU fallback (VC_ERR_NO_DEVICE).  Argument errors are VC_ERR_BAD_ARG and leave the handle unchanged.  The readers return
+ * VC_ERR_BAD_ARG, never stale data, before a run and after vc_select_add_tiles or vc_select_set_poses.  Any output pointer may be NULL. */
+typedef struct vc_selector vc_selector;
+int vc_selector_create(int device, int n_cameras, const int* model, const double* params /* x 10, padded */, const int* nparams,
+                       const double* T_ck /* x 7 */, const int* cam_flags, vc_selector** out);
+/* The cameras at the host state (what vc_get_camera returns), the calibrator's flags (camera 0 pinned unless the inertial terms are
+ * active, vc_fix_camera_intrinsics), its frames' poses and its observation tiles (corners the outlier pass removed are left out), on
+ * the calibrator's device.  VC_ERR_RUNNING while a solve runs. */
+int vc_selector_create_for_calibrator(vc_calibrator* h, vc_selector** out);
+void vc_selector_destroy(vc_selector* s);
+/* Same layout and rules as vc_holdout_add_tiles without the pixel column: tile_frame numbers the candidate frames; appends; the corners
+ * of one (frame, camera) given in several groups form one view, in order of arrival.  VC_ERR_BAD_ARG for a camera >= n_cameras, a point
+ * id >= n_points or tile_off not monotone. */
+int vc_select_add_tiles(vc_selector* s, int n_tiles, const int* tile_frame, const int* tile_cam, const long long* tile_off /* n_tiles + 1 */,
+                        const double* points, int n_points, const int* point_id);
+int vc_select_set_poses(vc_selector* s, const double* T_wk /* n_frames x 7 */, int n_frames);
+/* VC_ERR_BAD_ARG: k < 1, a start-set frame out of range or repeated, prior not finite or <= 0 (1e-6 is the tools' default), a tile that
+ * names a frame without a pose. */
+int vc_select_run(vc_selector* s, int k, const int* start_set, int n_start, double prior);
+int vc_select_get(vc_selector* s, int* n_picked, int* order /* k */, double* gain /* k */, double* cum /* k */, double* total);
+int vc_select_frames(vc_selector* s, int* status, int* corners, int* behind);      /* n_frames each */
+int vc_select_frame_information(vc_selector* s, int frame, double* I /* D x D, unscaled */, double* scale /* D */);
+/* the gains of all candidates in the last round that ran; -1 for frames that were selected before it, in the start set, or unusable */
+int vc_select_last_gains(vc_selector* s, double* gains /* n_frames */);
+int vc_select_dim(vc_selector* s);                      /* D (< 0: a status) */
+/* HIP events on the handle's stream, after a run: average ms of `reps` launches of [0] the information sweep, [1] one gain round at
+ * the last state over every candidate left, [2] one pick (it stores nothing). */
+int vc_time_select(vc_selector* s, int reps, double out_ms[3]);
+
 #ifdef __cplusplus
 }
 #endif

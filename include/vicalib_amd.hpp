@@ -481,4 +481,73 @@ class Uncertainty {
   int nk_ = 0, gx_ = 0, gy_ = 0;
 };
 
+// Greedy D-optimal selection of the most informative views (vc_selector*): which candidate frames carry the information on the shared
+// vision parameters, every frame's pose marginalised.  At most 64 shared columns.
+struct Selection { std::vector<int> order; std::vector<double> gain, cum; double total = 0; };      // cum[k] / total: the share of the first k + 1 views
+struct SelectionFrames { std::vector<int> status, corners, behind; };                                 // status: 0 usable, 1 underdetermined, 2 usable, corners behind
+class Selector {
+ public:
+  // cams: model, params and pose are read; flags: per camera 1 rotation free | 2 translation free | 4 intrinsics free
+  Selector(const std::vector<CameraAndPose>& cams, const std::vector<int>& flags, int device = 0) {
+    const int n = (int)cams.size();
+    std::vector<int> model(cams.size()), nparams(cams.size());
+    std::vector<double> params(10 * cams.size(), 0.0), T_ck(7 * cams.size());
+    for (size_t c = 0; c < cams.size(); ++c) {
+      model[c] = cams[c].model; nparams[c] = (int)cams[c].params.size();
+      for (size_t k = 0; k < cams[c].params.size() && k < 10; ++k) params[10 * c + k] = cams[c].params[k];
+      for (int k = 0; k < 7; ++k) T_ck[7 * c + k] = cams[c].T_ck.data()[k];
+    }
+    vc_checked(flags.size() == cams.size() ? vc_selector_create(device, n, model.data(), params.data(), nparams.data(), T_ck.data(), flags.data(), &s_) : VC_ERR_BAD_ARG, "Selector");
+  }
+  // the calibrator's cameras, flags, frame poses and observation tiles at its host state
+  explicit Selector(ViCalibrator& cal) {
+    vc_checked(vc_selector_create_for_calibrator(cal.handle(), &s_), "Selector");
+    n_frames_ = (int)cal.NumFrames();
+  }
+  ~Selector() { vc_selector_destroy(s_); }
+  Selector(const Selector&) = delete;
+  Selector& operator=(const Selector&) = delete;
+  void AddTiles(int n_tiles, const int* tile_frame, const int* tile_cam, const long long* tile_off, const double* points, int n_points, const int* point_id) {
+    vc_checked(vc_select_add_tiles(s_, n_tiles, tile_frame, tile_cam, tile_off, points, n_points, point_id), "AddTiles");
+  }
+  void SetPoses(const double* T_wk /* n_frames x 7 */, int n_frames) { vc_checked(vc_select_set_poses(s_, T_wk, n_frames), "SetPoses"); n_frames_ = n_frames; }
+  Selection Run(int k, const std::vector<int>& start = {}, double prior = 1e-6) {
+    vc_checked(vc_select_run(s_, k, start.empty() ? nullptr : start.data(), (int)start.size(), prior), "Run");
+    Selection r;
+    const size_t n = (size_t)(n_frames_ > 0 ? n_frames_ : 1);
+    r.order.resize(n); r.gain.resize(n); r.cum.resize(n);
+    int picked = 0;
+    vc_checked(vc_select_get(s_, &picked, r.order.data(), r.gain.data(), r.cum.data(), &r.total), "Run");
+    r.order.resize((size_t)picked); r.gain.resize((size_t)picked); r.cum.resize((size_t)picked);
+    return r;
+  }
+  SelectionFrames Frames() {
+    SelectionFrames f;
+    const size_t n = (size_t)(n_frames_ > 0 ? n_frames_ : 1);
+    f.status.resize(n); f.corners.resize(n); f.behind.resize(n);
+    vc_checked(vc_select_frames(s_, f.status.data(), f.corners.data(), f.behind.data()), "Frames");
+    return f;
+  }
+  // I: D x D row-major, unscaled; scale: D
+  void FrameInformation(int frame, std::vector<double>* I, std::vector<double>* scale) {
+    const size_t D = (size_t)Dim();
+    I->resize(D * D); scale->resize(D);
+    vc_checked(vc_select_frame_information(s_, frame, I->data(), scale->data()), "FrameInformation");
+  }
+  // the gains of all candidates in the last round that ran; -1 for frames selected before it, in the start set, or unusable
+  std::vector<double> LastGains() {
+    std::vector<double> g((size_t)(n_frames_ > 0 ? n_frames_ : 1));
+    vc_checked(vc_select_last_gains(s_, g.data()), "LastGains");
+    return g;
+  }
+  int Dim() { return vc_checked(vc_select_dim(s_), "Dim"); }
+  int NumFrames() const { return n_frames_; }
+  std::array<double, 3> Time(int reps = 20) { std::array<double, 3> ms{{0, 0, 0}}; vc_checked(vc_time_select(s_, reps, ms.data()), "Time"); return ms; }
+  vc_selector* handle() { return s_; }
+
+ private:
+  vc_selector* s_ = nullptr;
+  int n_frames_ = 0;
+};
+
 }  // namespace visual_inertial_calibration

@@ -375,6 +375,42 @@ int vc_uncertainty_create_for_camera(vc_calibrator* h, int c, int grid_x, int gr
   *out = u;
   return VC_OK;
 }
+// a selector (vc_select.hip) over the calibrator's own frames: cameras and poses at the host state, the flags of build_layout, the corners the
+// caller added (one group per corner run of equal frame and camera; corners without a copy left after the outlier pass are left out)
+int vc_selector_create_for_calibrator(vc_calibrator* h, vc_selector** out) {
+  if (!h || !out) return VC_ERR_BAD_ARG;
+  if (h->is_running) return VC_ERR_RUNNING;
+  const int C = (int)h->cams.size(), N = (int)h->frames.size();
+  if (C < 1 || C > 8 || N < 1) return VC_ERR_BAD_ARG;
+  std::vector<int> model(C), nparams(C), col_cam, col_local;
+  std::vector<double> params((size_t)C * 10, 0.0), T_ck((size_t)C * 7), poses((size_t)N * 7);
+  h->build_layout(col_cam, col_local);
+  {
+    std::lock_guard<std::mutex> lk(h->result_mutex);
+    for (int c = 0; c < C; ++c) {
+      const HostCam& cm = h->cams[c];
+      model[c] = cm.model; nparams[c] = cm.nk;
+      std::memcpy(&params[(size_t)c * 10], cm.K, (size_t)cm.nk * 8);
+      std::memcpy(&T_ck[(size_t)c * 7], cm.T_ck, 56);
+    }
+    for (int f = 0; f < N; ++f) std::memcpy(&poses[(size_t)f * 7], h->frames[f].T, 56);
+  }
+  vc_selector* s = nullptr;
+  int rc = vc_selector_create(h->device, C, model.data(), params.data(), nparams.data(), T_ck.data(), h->cam_flags.data(), &s);
+  if (rc != VC_OK) return rc;
+  std::vector<int> tf, tc, pid;
+  std::vector<long long> off(1, 0);
+  for (size_t o = 0; o < h->o_frame.size(); ++o) {
+    if (o < h->o_removed.size() && h->o_removed[o] == 1) continue;
+    if (tf.empty() || tf.back() != h->o_frame[o] || tc.back() != h->o_cam[o]) { tf.push_back(h->o_frame[o]); tc.push_back(h->o_cam[o]); off.push_back(off.back()); }
+    pid.push_back(h->o_pid[o]); ++off.back();
+  }
+  rc = vc_select_set_poses(s, poses.data(), N);
+  if (rc == VC_OK) rc = vc_select_add_tiles(s, (int)tf.size(), tf.data(), tc.data(), off.data(), h->pts.xyz.data(), h->pts.size(), pid.data());
+  if (rc != VC_OK) { vc_selector_destroy(s); return rc; }
+  *out = s;
+  return VC_OK;
+}
 int vc_get_frame(vc_calibrator* h, int f, double T_wk[7], double v_w[3], double* time) {
   if (!h || f < 0 || f >= (int)h->frames.size()) return VC_ERR_BAD_ARG;
   std::lock_guard<std::mutex> lk(h->result_mutex);

@@ -45,6 +45,8 @@ SYMBOLS = [
     "vc_converter_create", "vc_converter_create_for_camera", "vc_converter_destroy", "vc_convert_run", "vc_convert_get", "vc_convert_comparer", "vc_time_convert",
     "vc_uncertainty_create", "vc_uncertainty_create_for_camera", "vc_uncertainty_destroy", "vc_uncertainty_run", "vc_uncertainty_get_fit", "vc_uncertainty_get_map",
     "vc_uncertainty_summary", "vc_uncertainty_rings", "vc_time_uncertainty",
+    "vc_selector_create", "vc_selector_create_for_calibrator", "vc_selector_destroy", "vc_select_add_tiles", "vc_select_set_poses", "vc_select_run", "vc_select_get",
+    "vc_select_frames", "vc_select_frame_information", "vc_select_last_gains", "vc_select_dim", "vc_time_select",
 ]
 
 
@@ -113,7 +115,7 @@ def load():
         L.vc_allreduce_calls.restype = C.c_longlong
         L.vc_last_error.restype = C.c_char_p
         for name in ("vc_destroy", "vc_detector_destroy", "vc_shard_comm_destroy", "vc_undistorter_destroy", "vc_rectifier_destroy", "vc_comparer_destroy", "vc_converter_destroy",
-                     "vc_uncertainty_destroy"):
+                     "vc_uncertainty_destroy", "vc_selector_destroy"):
             getattr(L, name).restype = None
         _lib = L
     return _lib
@@ -1105,4 +1107,92 @@ class Uncertainty:
     def time(self, reps=20):
         out = np.zeros(3)
         _check(self.L.vc_time_uncertainty(self.h, int(reps), _d(out)), "time_uncertainty")
+        return out
+
+
+CAM_ROT_FREE, CAM_TRANS_FREE, CAM_K_FREE = 1, 2, 4
+
+
+class Selector:
+    """Greedy D-optimal selection of the most informative views (include/vicalib_amd.h: vc_selector*): cameras = [(model, params, T_ck, flags)]
+    with the solver's flags (CAM_ROT_FREE | CAM_TRANS_FREE | CAM_K_FREE); add_tiles() and set_poses() give the candidate frames; run(k, start,
+    prior) selects; result(), frames(), frame_information(f) and last_gains() read the last run; time(reps) -> ms per launch of the information
+    sweep, one gain round and one pick."""
+
+    def __init__(self, cameras, device=0, _calibrator=None):
+        self.L = load()
+        self.h = C.c_void_p()
+        if _calibrator is not None:
+            _check(self.L.vc_selector_create_for_calibrator(_calibrator.h, C.byref(self.h)), "selector_create_for_calibrator")
+        else:
+            n = len(cameras)
+            model = np.array([_model_id(c[0]) for c in cameras], dtype=np.int32)
+            nparams = np.array([len(c[1]) for c in cameras], dtype=np.int32)
+            params = np.zeros((n, 10))
+            for i, c in enumerate(cameras):
+                params[i, :min(len(c[1]), 10)] = np.asarray(c[1], dtype=np.float64)[:10]
+            T_ck = np.ascontiguousarray([c[2] for c in cameras], dtype=np.float64).reshape(n, 7)
+            flags = np.array([int(c[3]) for c in cameras], dtype=np.int32)
+            vp = lambda a: a.ctypes.data_as(C.c_void_p)      # noqa: E731
+            _check(self.L.vc_selector_create(int(device), n, vp(model), _d(params), vp(nparams), _d(T_ck), vp(flags), C.byref(self.h)), "selector_create")
+        self.D = _check(self.L.vc_select_dim(self.h), "select_dim")
+        self.n_frames = 0
+
+    @classmethod
+    def for_calibrator(cls, cal):
+        """The cameras, flags, frame poses and observation tiles of a ViCalibrator at its host state."""
+        s = cls(None, _calibrator=cal)
+        s.n_frames = cal.NumFrames()
+        return s
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.vc_selector_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+    def add_tiles(self, tile_frame, tile_cam, tile_off, points, point_id):
+        tf = np.ascontiguousarray(tile_frame, dtype=np.int32); tc = np.ascontiguousarray(tile_cam, dtype=np.int32)
+        off = np.ascontiguousarray(tile_off, dtype=np.int64); pid = np.ascontiguousarray(point_id, dtype=np.int32)
+        pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)      # noqa: E731
+        _check(self.L.vc_select_add_tiles(self.h, len(tf), vp(tf), vp(tc), vp(off), vp(pts), len(pts), vp(pid)), "select_add_tiles")
+
+    def set_poses(self, T_wk):
+        T = np.ascontiguousarray(T_wk, dtype=np.float64).reshape(-1, 7)
+        _check(self.L.vc_select_set_poses(self.h, _d(T), len(T)), "select_set_poses")
+        self.n_frames = len(T)
+
+    def run(self, k, start=(), prior=1e-6):
+        st = np.ascontiguousarray(start, dtype=np.int32)
+        _check(self.L.vc_select_run(self.h, int(k), st.ctypes.data_as(C.c_void_p) if len(st) else None, len(st), C.c_double(prior)), "select_run")
+        return self.result()
+
+    def result(self):
+        n = C.c_int(0); total = C.c_double(0)
+        order = np.zeros(max(self.n_frames, 1), dtype=np.int32); gain = np.zeros(max(self.n_frames, 1)); cum = np.zeros(max(self.n_frames, 1))
+        _check(self.L.vc_select_get(self.h, C.byref(n), order.ctypes.data_as(C.c_void_p), _d(gain), _d(cum), C.byref(total)), "select_get")
+        return dict(order=order[:n.value].copy(), gain=gain[:n.value].copy(), cum=cum[:n.value].copy(), total=total.value)
+
+    def frames(self):
+        a = [np.zeros(max(self.n_frames, 1), dtype=np.int32) for _ in range(3)]
+        _check(self.L.vc_select_frames(self.h, *[x.ctypes.data_as(C.c_void_p) for x in a]), "select_frames")
+        return dict(status=a[0][:self.n_frames], corners=a[1][:self.n_frames], behind=a[2][:self.n_frames])
+
+    def frame_information(self, frame):
+        """-> (I_f [D, D] unscaled, scale [D])"""
+        I = np.zeros((self.D, self.D)); s = np.zeros(self.D)
+        _check(self.L.vc_select_frame_information(self.h, int(frame), _d(I), _d(s)), "select_frame_information")
+        return I, s
+
+    def last_gains(self):
+        g = np.zeros(max(self.n_frames, 1))
+        _check(self.L.vc_select_last_gains(self.h, _d(g)), "select_last_gains")
+        return g[:self.n_frames]
+
+    def time(self, reps=20):
+        out = np.zeros(3)
+        _check(self.L.vc_time_select(self.h, int(reps), _d(out)), "time_select")
         return out
