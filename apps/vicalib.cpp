@@ -161,6 +161,19 @@ static void DefineFlags() {
          "-holdout_every, select_holdout.csv (the held-out frames scored as candidates against the calibrated frames as start set).");
   Define("select_prior", "double", "1e-6", "The prior on every scaled shared column that keeps the first log-determinants finite, > 0.");
   Define("select_start", "string", "", "Frames the selection starts from, f0,f1,... (frame numbers of the recording, each one of the calibrated frames).");
+  // a depth image registered into another camera of the rig (vc_regist*): off unless asked for
+  Define("register_models", "string", "", "rig.xml: register with the cameras of this rig file; needs no -cam, nothing is calibrated.  Without it -register_depth uses the "
+         "calibration just computed.");
+  Define("register_cams", "string", "0,1", "s,d: the depth camera s and the camera d its depth images are registered into.");
+  Define("register_depth", "string", "", "file://glob of the depth images of camera s: 16-bit binary PGM (maxval 65535, big-endian), 0 = no measurement.  Each is written "
+         "to -register_dir/<name>.pgm in camera d's pixels, with register_summary.csv (the eight counters per image).");
+  Define("register_dir", "string", "", "Directory for the registered images.  Its parent must exist.");
+  Define("register_unit", "double", "0.001", "Metres per count of the depth images, in and out (> 0).");
+  Define("register_kind", "string", "z", "What a depth value measures: z (distance along the optical axis) or range (distance along the pixel's ray).");
+  Define("register_splat", "string", "nearest", "Where a depth pixel lands: nearest (one pixel) or footprint (the rectangle its corners span, for a finer camera d).");
+  Define("register_color", "string", "", "file://glob of 8-bit PGM images of camera d, k-th with k-th depth image: each is taken into camera s's pixels as "
+         "-register_dir/color_in_depth_<name>.pgm (0 where camera d does not see the surface).");
+  Define("register_occlusion_tol", "double", "10", "A depth pixel sees camera d's image where it lies at most this many counts behind the nearest surface there (>= 0).");
   Define("convert_grid", "string", "64x48", "Lattice of the conversion, GXxGY: 2 ... image width by 2 ... image height, at most 2^22 samples.");
   Define("convert_fit_radius", "double", "1", "The target model is fitted over the samples within this fraction of the half-diagonal of the image centre (> 0; 1 = the whole image).");
 }
@@ -819,6 +832,131 @@ static int CompareRigs(const std::vector<vic::CameraAndPose>& A, const std::vect
   return rc;
 }
 
+// ---- -register_*: a depth image of camera s registered into camera d, and d's image into s (vc_regist*) ----------------------------------
+// 16-bit binary PGM, maxval 65535, most significant byte first (the Netpbm rule)
+static bool ReadPgm16(const std::string& path, int* w, int* h, std::vector<unsigned short>* px, std::string* err) {
+  std::ifstream f(path, std::ios::binary);
+  if (!f) { *err = "cannot open image " + path; return false; }
+  std::string magic; f >> magic;
+  if (magic != "P5") { *err = path + ": not a binary PGM (P5)"; return false; }
+  auto next_int = [&](long* v) {
+    while (true) { f >> std::ws; if (f.peek() == '#') { std::string c; std::getline(f, c); } else break; }
+    return (bool)(f >> *v);
+  };
+  long W = 0, H = 0, M = 0;
+  if (!next_int(&W) || !next_int(&H) || !next_int(&M) || W < 1 || H < 1 || M != 65535) { *err = path + ": expected a 16-bit PGM header (maxval 65535)"; return false; }
+  if (W > 8192 || H > 8192) { *err = path + ": " + std::to_string(W) + " x " + std::to_string(H) + " pixels, more than the 8192 x 8192 a camera can have"; return false; }
+  f.get();                                          // the single whitespace byte behind the header
+  std::vector<unsigned char> raw((size_t)W * H * 2);
+  f.read((char*)raw.data(), (std::streamsize)raw.size());
+  if ((size_t)f.gcount() != raw.size()) { *err = path + ": truncated image data"; return false; }
+  px->resize((size_t)W * H);
+  for (size_t k = 0; k < px->size(); ++k) (*px)[k] = (unsigned short)((raw[2 * k] << 8) | raw[2 * k + 1]);
+  *w = (int)W; *h = (int)H;
+  return true;
+}
+static bool WritePgm16(const std::string& path, int w, int h, const unsigned short* px, std::string* err) {
+  FILE* f = std::fopen(path.c_str(), "wb");
+  if (!f) { *err = "cannot write " + path; return false; }
+  std::fprintf(f, "P5\n%d %d\n65535\n", w, h);
+  std::vector<unsigned char> raw((size_t)w * h * 2);
+  for (size_t k = 0; k < (size_t)w * h; ++k) { raw[2 * k] = (unsigned char)(px[k] >> 8); raw[2 * k + 1] = (unsigned char)(px[k] & 255); }
+  const bool written = std::fwrite(raw.data(), 1, raw.size(), f) == raw.size();
+  if (std::fclose(f) != 0 || !written) { *err = "cannot write " + path + " in full"; return false; }
+  return true;
+}
+struct RegisterOptions { bool on = false; int s = 0, d = 1, kind = 0, splat = 0; double unit = 0.001, occl_tol = 10.0; std::string depth, color, dir; };
+// the flags of a registration, checked before anything else runs
+static bool RegisterFlags(RegisterOptions* o, std::string* err) {
+  o->depth = FlagString("register_depth"); o->color = FlagString("register_color"); o->dir = FlagString("register_dir");
+  o->on = !o->depth.empty() || !FlagString("register_models").empty();
+  if (!o->on) return true;
+  if (o->depth.empty() || o->dir.empty()) { *err = "-register_models / -register_depth need -register_depth and -register_dir"; return false; }
+  char tail = 0;
+  if (std::sscanf(FlagString("register_cams").c_str(), "%d,%d%c", &o->s, &o->d, &tail) != 2 || o->s < 0 || o->d < 0) {
+    *err = "illegal value '" + FlagString("register_cams") + "' specified for flag 'register_cams': expected s,d"; return false;
+  }
+  o->unit = FlagDouble("register_unit");
+  if (!(o->unit > 0.0 && o->unit <= 1e6)) { *err = "illegal value for flag 'register_unit': expected metres per count above 0"; return false; }
+  const std::string kind = FlagString("register_kind"), splat = FlagString("register_splat");
+  if (kind != "z" && kind != "range") { *err = "illegal value '" + kind + "' specified for flag 'register_kind': expected z or range"; return false; }
+  if (splat != "nearest" && splat != "footprint") { *err = "illegal value '" + splat + "' specified for flag 'register_splat': expected nearest or footprint"; return false; }
+  o->kind = kind == "range" ? 1 : 0; o->splat = splat == "footprint" ? 1 : 0;
+  o->occl_tol = FlagDouble("register_occlusion_tol");
+  if (!(o->occl_tol >= 0.0 && o->occl_tol <= 1e300)) { *err = "illegal value for flag 'register_occlusion_tol': expected a tolerance of at least 0"; return false; }
+  return true;
+}
+// Registers the depth images of camera s into camera d, in batches of at most 16.  Everything that can be said without a device -- camera
+// indices, file counts, image sizes -- is said first.  Exit status: 0, 1 (an error said in *err) or 3 (no device).
+static int RegisterRig(const std::vector<vic::CameraAndPose>& cams, const RegisterOptions& o, int device, std::string* err) {
+  if ((size_t)o.s >= cams.size() || (size_t)o.d >= cams.size()) {
+    *err = "illegal value for flag 'register_cams': camera " + std::to_string(std::max(o.s, o.d)) + " of a rig of " + std::to_string(cams.size()) + " cameras"; return 1;
+  }
+  const vic::CameraAndPose& S = cams[o.s];
+  const vic::CameraAndPose& D = cams[o.d];
+  std::vector<std::string> dfiles, cfiles;
+  if (!GlobSorted(StripScheme(o.depth), &dfiles)) { *err = "no depth image matches " + o.depth; return 1; }
+  if (!o.color.empty()) {
+    if (!GlobSorted(StripScheme(o.color), &cfiles)) { *err = "no image matches " + o.color; return 1; }
+    if (cfiles.size() != dfiles.size()) { *err = "-register_depth matches " + std::to_string(dfiles.size()) + " files and -register_color " + std::to_string(cfiles.size()); return 1; }
+  }
+  const size_t ns = (size_t)S.width * S.height, nd = (size_t)D.width * D.height, n = dfiles.size();
+  std::vector<unsigned short> depth(ns * n);
+  std::vector<unsigned char> color(cfiles.empty() ? 0 : nd * n);
+  for (size_t k = 0; k < n; ++k) {
+    int w = 0, h = 0;
+    std::vector<unsigned short> px;
+    if (!ReadPgm16(dfiles[k], &w, &h, &px, err)) return 1;
+    if (w != S.width || h != S.height) { *err = dfiles[k] + ": " + std::to_string(w) + " x " + std::to_string(h) + " pixels, camera " + std::to_string(o.s) + " has " + std::to_string(S.width) + " x " + std::to_string(S.height); return 1; }
+    std::copy(px.begin(), px.end(), depth.begin() + k * ns);
+    if (cfiles.empty()) continue;
+    std::vector<unsigned char> c8;
+    if (!ReadPgm(cfiles[k], &w, &h, &c8, err)) return 1;
+    if (w != D.width || h != D.height) { *err = cfiles[k] + ": " + std::to_string(w) + " x " + std::to_string(h) + " pixels, camera " + std::to_string(o.d) + " has " + std::to_string(D.width) + " x " + std::to_string(D.height); return 1; }
+    std::copy(c8.begin(), c8.end(), color.begin() + k * nd);
+  }
+  struct stat st;
+  if (mkdir(o.dir.c_str(), 0777) != 0 && !(stat(o.dir.c_str(), &st) == 0 && S_ISDIR(st.st_mode))) { *err = "cannot create the directory " + o.dir; return 1; }      // (one level)
+  vc_registrar* r = nullptr;
+  const int st_create = vc_registrar_create(device, S.model, S.params.data(), (int)S.params.size(), S.width, S.height, S.T_ck.data(), D.model, D.params.data(),
+                                            (int)D.params.size(), D.width, D.height, D.T_ck.data(), o.unit, o.unit, o.kind, o.splat, &r);
+  if (st_create == VC_ERR_NO_DEVICE) { *err = "no HIP device (there is no CPU fallback)"; return 3; }
+  if (st_create != VC_OK) { *err = "the registration refuses these cameras (status " + std::to_string(st_create) + ")"; return 1; }
+  FILE* csv = std::fopen((o.dir + "/register_summary.csv").c_str(), "w");
+  if (!csv) { vc_registrar_destroy(r); *err = "cannot write " + o.dir + "/register_summary.csv"; return 1; }
+  std::fprintf(csv, "image,zero,no_ray,behind,outside,value_range,footprint,candidates,filled\n");
+  long long filled = 0, candidates = 0;
+  int status = 0;
+  for (size_t first = 0; first < n && status == 0; first += 16) {
+    const int m = (int)std::min<size_t>(16, n - first);
+    std::vector<unsigned short> out(nd * m);
+    std::vector<long long> cnt(8 * (size_t)m);
+    int q = vc_register_depth(r, m, depth.data() + first * ns, 2 * S.width, (long long)(2 * ns), out.data(), 2 * D.width, (long long)(2 * nd), nullptr, cnt.data());
+    std::vector<unsigned char> cin;
+    if (q == VC_OK && !cfiles.empty()) {
+      cin.resize(ns * m);
+      q = vc_register_color(r, m, depth.data() + first * ns, 2 * S.width, (long long)(2 * ns), color.data() + first * nd, D.width, (long long)nd, o.occl_tol, 0, cin.data(),
+                            S.width, (long long)ns, nullptr);
+    }
+    if (q != VC_OK) { *err = "the registration failed (status " + std::to_string(q) + ")"; status = q == VC_ERR_NO_DEVICE ? 3 : 1; break; }
+    for (int k = 0; k < m && status == 0; ++k) {
+      const std::string name = BaseName(dfiles[first + k]);
+      if (!WritePgm16(o.dir + "/" + name + ".pgm", D.width, D.height, out.data() + k * nd, err)) status = 1;
+      if (status == 0 && !cfiles.empty() && !WritePgm(o.dir + "/color_in_depth_" + name + ".pgm", S.width, S.height, cin.data() + k * ns, err)) status = 1;
+      std::fprintf(csv, "%s", name.c_str());
+      for (int c = 0; c < 8; ++c) std::fprintf(csv, ",%lld", cnt[8 * (size_t)k + c]);
+      std::fprintf(csv, "\n");
+      candidates += cnt[8 * (size_t)k + 6]; filled += cnt[8 * (size_t)k + 7];
+    }
+  }
+  if (std::fclose(csv) != 0 && status == 0) { *err = "cannot write " + o.dir + "/register_summary.csv in full"; status = 1; }
+  vc_registrar_destroy(r);
+  if (status != 0) return status;
+  std::printf("registered %zu depth images of camera %d (%s) into camera %d (%s), %s: %lld candidates, %lld pixels filled -> %s\n", n, o.s, ModelName(S.model), o.d,
+              ModelName(D.model), o.splat ? "footprint" : "nearest", candidates, filled, o.dir.c_str());
+  return 0;
+}
+
 // ---- -convert_models / -convert_to: calibrated cameras converted to other camera models (vc_convert*) ------------------------------------
 static const char* ModelXmlType(int id) {
   static const char* n[] = {"calibu_fu_fv_u0_v0_w", "calibu_fu_fv_u0_v0_k1_k2", "calibu_fu_fv_u0_v0_k1_k2_k3", "calibu_fu_fv_u0_v0_kb4", "calibu_fu_fv_u0_v0", "calibu_fu_fv_u0_v0_rational6"};
@@ -1152,6 +1290,19 @@ int main(int argc, char** argv) {
       if (!CompareFlags(&compare, &err)) { std::fprintf(stderr, "ERROR: %s\n", err.c_str()); return 1; }
       compare.identity = true; compare.gx = convert.gx; compare.gy = convert.gy;      // (the conversion's own lattice; -compare_grid is not read)
     }
+  }
+  // ---- -register_models rig.xml -register_depth ...: file to file, nothing is calibrated; -register_depth alone: the result registers behind it
+  RegisterOptions reg;
+  if (!RegisterFlags(&reg, &err)) { std::fprintf(stderr, "ERROR: %s\n", err.c_str()); return 1; }
+  if (reg.on && (!FlagString("compare_models").empty() || !FlagString("convert_models").empty())) {
+    std::fprintf(stderr, "ERROR: -register_models / -register_depth and -compare_models / -convert_models exclude each other\n"); return 1;
+  }
+  if (!FlagString("register_models").empty()) {
+    std::vector<vic::CameraAndPose> a;
+    if (!ReadRigFile(FlagString("register_models"), &a, &err)) { std::fprintf(stderr, "F %s\n", err.c_str()); return 1; }
+    const int rc = RegisterRig(a, reg, (int)FlagInt("device"), &err);
+    if (rc != 0) std::fprintf(stderr, "%s %s\n", rc == 3 ? "F" : "E registration failed:", err.c_str());
+    return rc;
   }
   if (!FlagString("convert_models").empty()) {
     std::vector<vic::CameraAndPose> a;
@@ -1662,6 +1813,13 @@ int main(int argc, char** argv) {
       std::fprintf(stderr, "E conversion failed: %s\n", err.c_str()); convert_failed = true;
     }
   }
+  bool register_failed = false;
+  if (reg.on) {                                          // -register_depth: with the cameras just written
+    std::vector<vic::CameraAndPose> a;
+    if (!ReadRigFile(FlagString("output"), &a, &err) || RegisterRig(a, reg, (int)FlagInt("device"), &err) != 0) {
+      std::fprintf(stderr, "E registration failed: %s\n", err.c_str()); register_failed = true;
+    }
+  }
   if (FlagBool("print_poses")) {
     if (FILE* f = std::fopen("poses.txt", "w")) {
       for (size_t i = 0; i < all_frames.size(); ++i) { double c[6]; T2Cart(all_frames[i].t_wp_.data(), c); std::fprintf(f, "%f\t%f\t%f\t%f\t%f\t%f\n", c[0], c[1], c[2], c[3], c[4], c[5]); }
@@ -1702,5 +1860,6 @@ int main(int argc, char** argv) {
   if (convert_failed) std::fprintf(stderr, "E -convert_to: the converted rig is incomplete (exit status %d)\n", success ? 1 : 2);
   if (uncertainty_failed) std::fprintf(stderr, "E -uncertainty_dir: the uncertainty map's files are incomplete (exit status %d)\n", success ? 1 : 2);
   if (select_failed) std::fprintf(stderr, "E -select_views: the selection's files are incomplete (exit status %d)\n", success ? 1 : 2);
-  return success ? ((undistort_failed || rectify_failed || compare_failed || convert_failed || uncertainty_failed || select_failed) ? 1 : 0) : 2;
+  if (register_failed) std::fprintf(stderr, "E -register_depth: the registered images are incomplete (exit status %d)\n", success ? 1 : 2);
+  return success ? ((undistort_failed || rectify_failed || compare_failed || convert_failed || uncertainty_failed || select_failed || register_failed) ? 1 : 0) : 2;
 }

@@ -660,6 +660,77 @@ int vc_select_dim(vc_selector* s);                      /* D (< 0: a status) */
  * the last state over every candidate left, [2] one pick (it stores nothing). */
 int vc_time_select(vc_selector* s, int reps, double out_ms[3]);
 
+/* ---- registering a depth image into another camera of the rig ------------------------------------------------------------------------
+ * What the owner of a rig with a depth sensor does with cameras.xml first: put the depth image into the colour camera's pixels, or the
+ * colour image into the depth camera's.  The SOURCE camera S is the depth camera, the DESTINATION camera D the other one; each has a
+ * model (any of the six), params and a size from 2 x 2 to 8192 x 8192, checked as by vc_undistorter_create.  Poses T_ck_s, T_ck_d as
+ * vc_get_camera returns them; with p_c = R_ck p_k + t_ck: R = R_dk R_sk^T, t = t_dk - R t_sk, p_d = R p_s + t (the rectifier's pair
+ * relation).  A pose that is not finite or whose quaternion is not of unit length to 1e-6 is VC_ERR_BAD_ARG.
+ * Depth image: uint16, rows `pitch` bytes apart (even; the buffer 2-byte aligned).  0 = no measurement; v = v * unit_src metres;
+ * unit_src > 0, unit_dst > 0, both finite.  kind 0 (Z): the value is the distance along S's optical axis; kind 1 (range): along the
+ * pixel's ray.  Pixel centres are at integers.
+ * The ray r of a source position (u, v) is the Newton inversion of vc_undistort_points.  The centre of pixel (i, j) with measured distance
+ * m lies at p_s = r (m / r_z) under kind Z (needs r_z > 0), p_s = r m / |r| under kind range; its value in D is m_d = (p_d)_z under kind Z,
+ * |p_d| under kind range, and w = floor(m_d / unit_dst + 0.5).
+ * A source pixel is dropped by the FIRST of these rules that applies; each has a counter:
+ *   0  value 0
+ *   1  no ray: the inversion failed, or r_z <= 0 under kind Z
+ *   2  (p_d)_z <= 0 unless D is kb4 (the undistorter's rule), or the projection is not finite
+ *   3  lands outside [0, w_d - 1] x [0, h_d - 1]
+ *   4  w outside 1..65535
+ *   5  footprint larger than 8 pixels in x or y (footprint mode only)
+ *   6  candidates that reached the depth test (not a drop)
+ *   7  destination pixels filled (not a drop)
+ * splat 0 (nearest): the candidate lands on (floor(q_x + 0.5), floor(q_y + 0.5)), q = the projection of p_d into D.
+ * splat 1 (footprint), for a D finer than S: the positions (i - 0.5, j - 0.5) and (i + 0.5, j + 0.5) are unprojected, placed at the
+ * pixel's own measured distance m by the formula of the centre, transformed and projected to qa, qb; either corner failing rule 1 or 2
+ * drops the pixel under that rule.  The rectangle x0 = floor(min(qa_x, qb_x) + 0.5) .. x1 = floor(max(qa_x, qb_x) + 0.5), likewise y:
+ * empty after clipping to the image is rule 3, more than 8 wide or high before clipping rule 5; the candidate lands on every pixel of the
+ * clipped rectangle.  The value w is always that of the pixel centre: the mode changes where a value lands, never the value.
+ * Depth test: a candidate's key is (w << 32) | (j w_s + i); a destination pixel takes the SMALLEST key that landed on it -- the nearest
+ * surface, among equal values the lowest source index.  Where nothing landed the depth is 0 and the index -1.  A minimum does not depend
+ * on the order of arrival: two runs, and an image alone or in a batch, give the same bytes.
+ * Colour into depth geometry: D's 8-bit image taken into S's pixels.  Source pixel (i, j) is VISIBLE when its centre passes rules 0-2, its centre
+ * projection q lies in D's image under the undistorter's border rule (within 1e-9 px it is on the border), and the pixel
+ * (floor(q_x + 0.5), floor(q_y + 0.5)) of the depth test just run (in the handle's splat mode) holds a value w_win with
+ * w <= w_win + occl_tol (occl_tol >= 0, in units of unit_dst).  A visible pixel gets D's image at q by the bilinear rule of
+ * vc_undistort_images (double precision, rounded half-up), every other pixel `fill`.
+ * The ray tables (every pixel centre and every node of the corner lattice) are built once, at create.  A handle is single-threaded, with
+ * a stream and pinned staging of its own that grow with the batch size.  Argument errors are VC_ERR_BAD_ARG and come before the device is
+ * looked for; no CPU fallback (VC_ERR_NO_DEVICE).  n = 0 is VC_OK without a launch; n <= 65535. */
+typedef struct vc_registrar vc_registrar;
+int vc_registrar_create(int device, int model_s, const double* params_s, int nparams_s, int w_s, int h_s, const double T_ck_s[7], int model_d,
+                        const double* params_d, int nparams_d, int w_d, int h_d, const double T_ck_d[7], double unit_src, double unit_dst, int kind,
+                        int splat, vc_registrar** out);
+/* the same for cameras cam_s and cam_d of a calibrator as vc_get_camera returns them, on the calibrator's device */
+int vc_registrar_create_for_cameras(vc_calibrator* h, int cam_s, int cam_d, double unit_src, double unit_dst, int kind, int splat, vc_registrar** out);
+void vc_registrar_destroy(vc_registrar* r);
+/* R (row-major), t, both sizes (w, h), units = [unit_src, unit_dst], kind, splat; any pointer may be NULL */
+int vc_register_get(vc_registrar* r, double R[9], double t[3], int size_s[2], int size_d[2], double units[2], int* kind, int* splat);
+/* n depth images of S, HOST buffers (image k at src + k * src_stride BYTES, rows src_pitch bytes apart; likewise dst) -> n depth images
+ * in D's pixels; a destination row's padding is not written.  index (nullable): n x h_d x w_d int32, the source index j w_s + i that won,
+ * -1 where nothing landed.  counters (nullable): n x 8, the table above.  One upload, the launches (clear, scatter, resolve), one
+ * download and one synchronisation per call. */
+int vc_register_depth(vc_registrar* r, int n, const unsigned short* src, int src_pitch, long long src_stride, unsigned short* dst, int dst_pitch,
+                      long long dst_stride, int* index, long long* counters);
+/* the same on DEVICE pointers, enqueued on the handle's stream (vc_register_stream, a hipStream_t) without synchronisation; a batch larger
+ * than any before first waits for the stream and grows the key buffer */
+int vc_register_depth_device(vc_registrar* r, int n, const unsigned short* d_src, int src_pitch, long long src_stride, unsigned short* d_dst,
+                             int dst_pitch, long long dst_stride, int* d_index, long long* d_counters);
+void* vc_register_stream(vc_registrar* r);
+/* n depth images of S and n 8-bit images of D (HOST buffers) -> n 8-bit images of w_s x h_s: the depth test, then the gather.  mask
+ * (nullable): n x h_s x w_s bytes, 1 = visible.  VC_ERR_BAD_ARG: occl_tol < 0 or not finite, fill outside 0..255. */
+int vc_register_color(vc_registrar* r, int n, const unsigned short* depth, int depth_pitch, long long depth_stride, const unsigned char* color,
+                      int color_pitch, long long color_stride, double occl_tol, int fill, unsigned char* out, int out_pitch, long long out_stride,
+                      unsigned char* mask);
+/* The continuous face: n rows (u, v, value) at arbitrary sub-pixel positions of S -- the Newton inversion runs per point, the tables are
+ * not read -- -> n rows (q_x, q_y, m_d / unit_dst) before any rounding.  valid (nullable) = 0 and a NaN row: rule 1 or 2, or a value that
+ * is not positive and finite. */
+int vc_register_points(vc_registrar* r, int n, const double* in /* n x 3 */, double* out /* n x 3 */, unsigned char* valid /* n */);
+/* HIP events on the handle's stream, `reps` launches each: out_ms[0] the table build, [1] clear + scatter + resolve of n_images
+ * device-resident images (a slanted surface of 1000..2499 counts), [2] the gather, [3] 65536 points. */
+int vc_time_register(vc_registrar* r, int n_images, int reps, double out_ms[4]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -550,4 +550,48 @@ class Selector {
   int n_frames_ = 0;
 };
 
+// A depth image of one camera of the rig registered into another (vc_regist*): the depth camera `src` into `dst`'s pixels by a forward warp
+// with a depth test, and dst's 8-bit image into src's pixels with an occlusion test.  kind: 0 Z, 1 range; splat: 0 nearest, 1 footprint.
+struct RegisterInfo { double R[9], t[3]; int src_size[2], dst_size[2]; double unit_src = 0, unit_dst = 0; int kind = 0, splat = 0; };
+class Registrar {
+ public:
+  Registrar(const CameraAndPose& src, const CameraAndPose& dst, double unit_src = 0.001, double unit_dst = 0.001, int kind = 0, int splat = 0, int device = 0) {
+    vc_checked(vc_registrar_create(device, src.model, src.params.data(), (int)src.params.size(), src.width, src.height, src.T_ck.data(), dst.model, dst.params.data(),
+                                   (int)dst.params.size(), dst.width, dst.height, dst.T_ck.data(), unit_src, unit_dst, kind, splat, &r_), "Registrar");
+  }
+  Registrar(ViCalibrator& cal, int cam_s, int cam_d, double unit_src = 0.001, double unit_dst = 0.001, int kind = 0, int splat = 0) {
+    vc_checked(vc_registrar_create_for_cameras(cal.handle(), cam_s, cam_d, unit_src, unit_dst, kind, splat, &r_), "Registrar");
+  }
+  ~Registrar() { vc_registrar_destroy(r_); }
+  Registrar(const Registrar&) = delete;
+  Registrar& operator=(const Registrar&) = delete;
+  RegisterInfo Get() {
+    RegisterInfo g; double units[2] = {0, 0};
+    vc_checked(vc_register_get(r_, g.R, g.t, g.src_size, g.dst_size, units, &g.kind, &g.splat), "Get");
+    g.unit_src = units[0]; g.unit_dst = units[1];
+    return g;
+  }
+  // index (n x h_d x w_d) and counters (n x 8) may be nullptr; pitches and strides in bytes
+  void Depth(int n, const unsigned short* src, int src_pitch, long long src_stride, unsigned short* dst, int dst_pitch, long long dst_stride, int* index = nullptr,
+             long long* counters = nullptr) {
+    vc_checked(vc_register_depth(r_, n, src, src_pitch, src_stride, dst, dst_pitch, dst_stride, index, counters), "Depth");
+  }
+  void DepthDevice(int n, const unsigned short* d_src, int src_pitch, long long src_stride, unsigned short* d_dst, int dst_pitch, long long dst_stride,
+                   int* d_index = nullptr, long long* d_counters = nullptr) {
+    vc_checked(vc_register_depth_device(r_, n, d_src, src_pitch, src_stride, d_dst, dst_pitch, dst_stride, d_index, d_counters), "DepthDevice");
+  }
+  void* Stream() { return vc_register_stream(r_); }      // hipStream_t
+  void Color(int n, const unsigned short* depth, int depth_pitch, long long depth_stride, const unsigned char* color, int color_pitch, long long color_stride,
+             double occl_tol, int fill, unsigned char* out, int out_pitch, long long out_stride, unsigned char* mask = nullptr) {
+    vc_checked(vc_register_color(r_, n, depth, depth_pitch, depth_stride, color, color_pitch, color_stride, occl_tol, fill, out, out_pitch, out_stride, mask), "Color");
+  }
+  // rows (u, v, value) -> rows (q_x, q_y, m_d / unit_dst)
+  void Points(int n, const double* in, double* out, unsigned char* valid = nullptr) { vc_checked(vc_register_points(r_, n, in, out, valid), "Points"); }
+  std::array<double, 4> Time(int n_images = 8, int reps = 20) { std::array<double, 4> ms{{0, 0, 0, 0}}; vc_checked(vc_time_register(r_, n_images, reps, ms.data()), "Time"); return ms; }
+  vc_registrar* handle() { return r_; }
+
+ private:
+  vc_registrar* r_ = nullptr;
+};
+
 }  // namespace visual_inertial_calibration

@@ -347,6 +347,14 @@ int vc_converter_create_for_camera(vc_calibrator* h, int c, int model_b, int gri
   { std::lock_guard<std::mutex> lk(h->result_mutex); cm = h->cams[c]; }
   return vc_converter_create(h->device, cm.model, cm.K, cm.nk, cm.width, cm.height, model_b, grid_x, grid_y, out);
 }
+// a registrar (vc_register.hip) from depth camera s into camera d as vc_get_camera returns them, on the calibrator's device
+int vc_registrar_create_for_cameras(vc_calibrator* h, int s, int d, double unit_src, double unit_dst, int kind, int splat, vc_registrar** out) {
+  if (!h || s < 0 || d < 0 || s >= (int)h->cams.size() || d >= (int)h->cams.size()) return VC_ERR_BAD_ARG;
+  HostCam cs, cd;
+  { std::lock_guard<std::mutex> lk(h->result_mutex); cs = h->cams[s]; cd = h->cams[d]; }
+  return vc_registrar_create(h->device, cs.model, cs.K, cs.nk, cs.width, cs.height, cs.T_ck, cd.model, cd.K, cd.nk, cd.width, cd.height, cd.T_ck, unit_src, unit_dst,
+                             kind, splat, out);
+}
 // an uncertainty map (vc_uncertainty.hip) of camera c as vc_get_camera returns it, on the calibrator's device, with the camera's params block of
 // vc_get_solution_covariance at the current state (the layout of covariance_layout: q_ck (4), p_ck (3), params (nk) per camera)
 int vc_uncertainty_create_for_camera(vc_calibrator* h, int c, int grid_x, int grid_y, vc_uncertainty** out) {

@@ -47,6 +47,8 @@ SYMBOLS = [
     "vc_uncertainty_summary", "vc_uncertainty_rings", "vc_time_uncertainty",
     "vc_selector_create", "vc_selector_create_for_calibrator", "vc_selector_destroy", "vc_select_add_tiles", "vc_select_set_poses", "vc_select_run", "vc_select_get",
     "vc_select_frames", "vc_select_frame_information", "vc_select_last_gains", "vc_select_dim", "vc_time_select",
+    "vc_registrar_create", "vc_registrar_create_for_cameras", "vc_registrar_destroy", "vc_register_get", "vc_register_depth", "vc_register_depth_device",
+    "vc_register_stream", "vc_register_color", "vc_register_points", "vc_time_register",
 ]
 
 
@@ -109,13 +111,14 @@ def load():
         L.vc_get_stream.restype = C.c_void_p
         L.vc_undistort_stream.restype = C.c_void_p
         L.vc_rectifier_side.restype = C.c_void_p
+        L.vc_register_stream.restype = C.c_void_p
         L.vc_num_observations.restype = C.c_longlong
         L.vc_report_num_corners.restype = C.c_longlong
         L.vc_holdout_num_corners.restype = C.c_longlong
         L.vc_allreduce_calls.restype = C.c_longlong
         L.vc_last_error.restype = C.c_char_p
         for name in ("vc_destroy", "vc_detector_destroy", "vc_shard_comm_destroy", "vc_undistorter_destroy", "vc_rectifier_destroy", "vc_comparer_destroy", "vc_converter_destroy",
-                     "vc_uncertainty_destroy", "vc_selector_destroy"):
+                     "vc_uncertainty_destroy", "vc_selector_destroy", "vc_registrar_destroy"):
             getattr(L, name).restype = None
         _lib = L
     return _lib
@@ -1196,3 +1199,107 @@ class Selector:
         out = np.zeros(3)
         _check(self.L.vc_time_select(self.h, int(reps), _d(out)), "time_select")
         return out
+
+
+class Registrar:
+    """A depth image of one camera of the rig taken into another camera, and that camera's image taken into the depth camera's pixels
+    (include/vicalib_amd.h: vc_regist*).  cam_s (the depth camera) and cam_d are (model, params, (w, h), T_ck) each; unit_src / unit_dst
+    metres per count; kind "z" or "range"; splat "nearest" or "footprint".  depth(arr) -> (depth in D's pixels, index map, counters);
+    color(depth, images) -> (images in S's pixels, visibility mask); points(rows) -> ((q_x, q_y, m_d / unit_dst) rows, valid)."""
+    KINDS = {"z": 0, "range": 1}
+    SPLATS = {"nearest": 0, "footprint": 1}
+
+    def __init__(self, cam_s, cam_d, unit_src=0.001, unit_dst=0.001, kind="z", splat="nearest", device=0, _cameras_of=None):
+        self.L = load()
+        self.h = C.c_void_p()
+        kind = self.KINDS.get(kind, kind); splat = self.SPLATS.get(splat, splat)
+        if _cameras_of is not None:
+            cal, s, d = _cameras_of
+            _check(self.L.vc_registrar_create_for_cameras(cal.h, int(s), int(d), C.c_double(unit_src), C.c_double(unit_dst), int(kind), int(splat), C.byref(self.h)),
+                   "registrar_create_for_cameras")
+        else:
+            (ms, Ks, size_s, Ts), (md, Kd, size_d, Td) = cam_s, cam_d
+            Ks = np.ascontiguousarray(Ks, dtype=np.float64); Kd = np.ascontiguousarray(Kd, dtype=np.float64)
+            _check(self.L.vc_registrar_create(int(device), _model_id(ms), _d(Ks), len(Ks), int(size_s[0]), int(size_s[1]), _d(Ts), _model_id(md), _d(Kd), len(Kd),
+                                              int(size_d[0]), int(size_d[1]), _d(Td), C.c_double(unit_src), C.c_double(unit_dst), int(kind), int(splat),
+                                              C.byref(self.h)), "registrar_create")
+        g = self.get()                                       # the sizes are the handle's, whichever way it was made
+        self.src_size, self.dst_size = g["src_size"], g["dst_size"]
+
+    @classmethod
+    def for_cameras(cls, cal, cam_s, cam_d, unit_src=0.001, unit_dst=0.001, kind="z", splat="nearest"):
+        """For two cameras of a ViCalibrator, with the models, parameters, sizes and poses it holds for them."""
+        return cls(None, None, unit_src, unit_dst, kind, splat, _cameras_of=(cal, cam_s, cam_d))
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.vc_registrar_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+    def get(self):
+        """-> dict(R, t, src_size, dst_size, unit_src, unit_dst, kind, splat)"""
+        R = np.zeros((3, 3)); t = np.zeros(3); ss = (C.c_int * 2)(); sd = (C.c_int * 2)(); units = np.zeros(2); kind = C.c_int(0); splat = C.c_int(0)
+        _check(self.L.vc_register_get(self.h, _d(R), _d(t), ss, sd, _d(units), C.byref(kind), C.byref(splat)), "register_get")
+        return dict(R=R, t=t, src_size=(ss[0], ss[1]), dst_size=(sd[0], sd[1]), unit_src=units[0], unit_dst=units[1], kind=kind.value, splat=splat.value)
+
+    @staticmethod
+    def _batch(arr, dtype, size):
+        """[h, w] or [n, h, w] of `dtype`, rows and images possibly strided (pixels of a row contiguous) -> (array [n, h, w], single)"""
+        arr = np.asarray(arr)
+        single = arr.ndim == 2
+        a = arr[None] if single else arr
+        assert a.dtype == dtype and a.ndim == 3 and a.shape[1:] == (size[1], size[0]), (a.dtype, a.shape)
+        if a.strides[2] != a.itemsize or a.strides[1] < a.shape[2] * a.itemsize or (len(a) > 1 and a.strides[0] < a.strides[1] * a.shape[1]):
+            a = np.ascontiguousarray(a)
+        return a, single
+
+    def depth(self, arr, out=None):
+        """arr: uint16 [h_s, w_s] or [n, h_s, w_s] -> (uint16 [n, h_d, w_d], index int32 [n, h_d, w_d], counters int64 [n, 8]); out: where the
+        depth images go (strided rows allowed; only its pixels are written)"""
+        a, single = self._batch(arr, np.uint16, self.src_size)
+        n = len(a)
+        if out is None:
+            o = np.zeros((n, self.dst_size[1], self.dst_size[0]), dtype=np.uint16)
+        else:
+            o = out[None] if out.ndim == 2 else out
+            assert o.dtype == np.uint16 and o.shape == (n, self.dst_size[1], self.dst_size[0]) and o.strides[2] == 2 and o.flags.writeable
+        idx = np.zeros((n, self.dst_size[1], self.dst_size[0]), dtype=np.int32); cnt = np.zeros((n, 8), dtype=np.int64)
+        _check(self.L.vc_register_depth(self.h, n, C.c_void_p(a.ctypes.data), int(a.strides[1]), C.c_longlong(a.strides[0]), C.c_void_p(o.ctypes.data), int(o.strides[1]),
+                                        C.c_longlong(o.strides[0]), C.c_void_p(idx.ctypes.data), C.c_void_p(cnt.ctypes.data)), "register_depth")
+        return (o[0], idx[0], cnt[0]) if single else (o, idx, cnt)
+
+    def depth_device(self, n, d_src, src_pitch, src_stride, d_dst, dst_pitch, dst_stride, d_index=None, d_counters=None):
+        """Device pointers (integers), enqueued on stream() without synchronisation (vc_register_depth_device)."""
+        vp = lambda x: None if x is None else C.c_void_p(int(x))      # noqa: E731
+        _check(self.L.vc_register_depth_device(self.h, int(n), vp(d_src), int(src_pitch), C.c_longlong(src_stride), vp(d_dst), int(dst_pitch), C.c_longlong(dst_stride),
+                                               vp(d_index), vp(d_counters)), "register_depth_device")
+
+    def stream(self): return self.L.vc_register_stream(self.h)
+
+    def color(self, depth, images, occl_tol=0.0, fill=0):
+        """depth: uint16 [n, h_s, w_s] of S; images: uint8 [n, h_d, w_d] of D -> (uint8 [n, h_s, w_s], visible [n, h_s, w_s] bool)"""
+        a, single = self._batch(depth, np.uint16, self.src_size)
+        c, _ = self._batch(images, np.uint8, self.dst_size)
+        n = len(a)
+        assert len(c) == n
+        o = np.zeros((n, self.src_size[1], self.src_size[0]), dtype=np.uint8); m = np.zeros_like(o)
+        ll = C.c_longlong
+        _check(self.L.vc_register_color(self.h, n, C.c_void_p(a.ctypes.data), int(a.strides[1]), ll(a.strides[0]), C.c_void_p(c.ctypes.data), int(c.strides[1]),
+                                        ll(c.strides[0]), C.c_double(occl_tol), int(fill), C.c_void_p(o.ctypes.data), int(o.strides[1]), ll(o.strides[0]),
+                                        C.c_void_p(m.ctypes.data)), "register_color")
+        return (o[0], m[0].astype(bool)) if single else (o, m.astype(bool))
+
+    def points(self, rows):
+        rows = np.ascontiguousarray(rows, dtype=np.float64).reshape(-1, 3)
+        out = np.zeros_like(rows); valid = np.zeros(len(rows), dtype=np.uint8)
+        _check(self.L.vc_register_points(self.h, len(rows), _d(rows), out.ctypes.data_as(C.c_void_p), valid.ctypes.data_as(C.c_void_p)), "register_points")
+        return out, valid.astype(bool)
+
+    def time(self, n_images=8, reps=20):
+        """Average ms per launch: table build, clear + scatter + resolve of n_images device-resident images, gather, 65536 points."""
+        out = np.zeros(4)
+        _check(self.L.vc_time_register(self.h, int(n_images), int(reps), _d(out)), "time_register")
+        return dict(tables=out[0], depth=out[1], gather=out[2], points=out[3])
