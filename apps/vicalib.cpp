@@ -174,6 +174,25 @@ static void DefineFlags() {
   Define("register_color", "string", "", "file://glob of 8-bit PGM images of camera d, k-th with k-th depth image: each is taken into camera s's pixels as "
          "-register_dir/color_in_depth_<name>.pgm (0 where camera d does not see the surface).");
   Define("register_occlusion_tol", "double", "10", "A depth pixel sees camera d's image where it lies at most this many counts behind the nearest surface there (>= 0).");
+  Define("depthcal_models", "string", "", "rig.xml: calibrate the range error of a depth camera of this rig file against the target, from -depthcal_poses and "
+         "-depthcal_depth; needs no -cam, nothing is calibrated.  Without it -depthcal_depth uses the calibration's result and the poses of its frames.");
+  Define("depthcal_cam", "int32", "0", "The depth camera.");
+  Define("depthcal_poses", "string", "", "The frames' poses in the format -save_poses writes; the k-th line belongs to the k-th file of -depthcal_depth in sorted order.");
+  Define("depthcal_depth", "string", "", "file://glob of the depth images: 16-bit binary PGM (maxval 65535, big-endian), 0 = no measurement.");
+  Define("depthcal_dir", "string", "", "Directory for depth_correction.csv, depthcal_cells.csv and depthcal_frames.csv (fit) or the corrected images and "
+         "depthcal_apply.csv (apply).  Its parent must exist.");
+  Define("depthcal_apply", "string", "", "depth_correction.csv: correct the images of -depthcal_depth with it and write them to -depthcal_dir under their own names.");
+  Define("depthcal_interp", "string", "cell", "The cells' terms of a correction: cell (the pixel's own cell) or bilinear (between cell centres).");
+  Define("depthcal_unit", "double", "0.001", "Metres per count of the depth images (> 0).");
+  Define("depthcal_kind", "string", "z", "What a depth value measures: z (distance along the optical axis) or range (distance along the pixel's ray).");
+  Define("depthcal_bins", "string", "4,3", "bx,by: image cells of the correction, 1..32 each.");
+  Define("depthcal_vref", "double", "1000", "A typical value of the working range in counts (> 0); it only centres the arithmetic.");
+  Define("depthcal_min_cos", "double", "0.5", "Pixels that see the board at a cosine of incidence below this are dropped (in (0, 1]).");
+  Define("depthcal_max_dev", "double", "100", "Pixels whose value differs from the expected one by more than this many counts are dropped (> 0).");
+  Define("depthcal_degree", "int32", "2", "Degree of the global polynomial in the value: 0, 1 or 2.");
+  Define("depthcal_min_count", "int32", "50", "A cell with fewer pixels gets no term of its own (>= 1).");
+  Define("depthcal_min_spread", "double", "0.02", "A cell whose values spread less than this (standard deviation of (v - vref) / vref) gets an offset only (>= 0).");
+  Define("depthcal_margin", "double", "0", "The board rectangle is the dot lattice [0, (grid_width - 1) spacing] x [0, (grid_height - 1) spacing] grown by this (m).");
   Define("convert_grid", "string", "64x48", "Lattice of the conversion, GXxGY: 2 ... image width by 2 ... image height, at most 2^22 samples.");
   Define("convert_fit_radius", "double", "1", "The target model is fitted over the samples within this fraction of the half-diagonal of the image centre (> 0; 1 = the whole image).");
 }
@@ -957,6 +976,225 @@ static int RegisterRig(const std::vector<vic::CameraAndPose>& cams, const Regist
   return 0;
 }
 
+// ---- -depthcal_*: the range error of a depth camera against the target, and its correction (vc_depthcal*) ------------------------------
+struct DepthCalCli {
+  bool on = false, apply = false;
+  int cam = 0, kind = 0, bx = 4, by = 3, degree = 2, min_count = 50, interp = 0;
+  double unit = 0.001, v_ref = 1000.0, min_cos = 0.5, max_dev = 100.0, min_spread = 0.02, rect[4] = {0, 0, 0, 0};
+  std::string models, poses, depth, dir, file;
+};
+// the flags of a depth calibration, checked before anything else runs
+static bool DepthCalFlags(DepthCalCli* o, std::string* err) {
+  o->models = FlagString("depthcal_models"); o->poses = FlagString("depthcal_poses"); o->depth = FlagString("depthcal_depth"); o->dir = FlagString("depthcal_dir");
+  o->file = FlagString("depthcal_apply");
+  o->apply = !o->file.empty();
+  o->on = !o->models.empty() || !o->poses.empty() || !o->depth.empty() || o->apply;
+  if (!o->on) return true;
+  if (o->depth.empty() || o->dir.empty()) { *err = "-depthcal_models / -depthcal_depth / -depthcal_apply need -depthcal_depth and -depthcal_dir"; return false; }
+  if (o->apply && (!o->models.empty() || !o->poses.empty())) { *err = "-depthcal_apply and -depthcal_models / -depthcal_poses exclude each other"; return false; }
+  if (!o->apply && o->models.empty() != o->poses.empty()) { *err = "-depthcal_models and -depthcal_poses need each other"; return false; }
+  o->cam = (int)FlagInt("depthcal_cam");
+  if (o->cam < 0) { *err = "illegal value for flag 'depthcal_cam': expected a camera index"; return false; }
+  o->unit = FlagDouble("depthcal_unit");
+  if (!(o->unit > 0.0 && o->unit <= 1e6)) { *err = "illegal value for flag 'depthcal_unit': expected metres per count above 0"; return false; }
+  const std::string kind = FlagString("depthcal_kind"), interp = FlagString("depthcal_interp");
+  if (kind != "z" && kind != "range") { *err = "illegal value '" + kind + "' specified for flag 'depthcal_kind': expected z or range"; return false; }
+  if (interp != "cell" && interp != "bilinear") { *err = "illegal value '" + interp + "' specified for flag 'depthcal_interp': expected cell or bilinear"; return false; }
+  o->kind = kind == "range" ? 1 : 0; o->interp = interp == "bilinear" ? 1 : 0;
+  char tail = 0;
+  if (std::sscanf(FlagString("depthcal_bins").c_str(), "%d,%d%c", &o->bx, &o->by, &tail) != 2 || o->bx < 1 || o->by < 1 || o->bx > 32 || o->by > 32) {
+    *err = "illegal value '" + FlagString("depthcal_bins") + "' specified for flag 'depthcal_bins': expected bx,by of 1..32 each"; return false;
+  }
+  o->v_ref = FlagDouble("depthcal_vref"); o->min_cos = FlagDouble("depthcal_min_cos"); o->max_dev = FlagDouble("depthcal_max_dev");
+  o->degree = (int)FlagInt("depthcal_degree"); o->min_count = (int)FlagInt("depthcal_min_count"); o->min_spread = FlagDouble("depthcal_min_spread");
+  if (!(o->v_ref > 0.0 && o->v_ref <= 1e300)) { *err = "illegal value for flag 'depthcal_vref': expected counts above 0"; return false; }
+  if (!(o->min_cos > 0.0 && o->min_cos <= 1.0)) { *err = "illegal value for flag 'depthcal_min_cos': expected a cosine in (0, 1]"; return false; }
+  if (!(o->max_dev > 0.0 && o->max_dev <= 1e300)) { *err = "illegal value for flag 'depthcal_max_dev': expected counts above 0"; return false; }
+  if (o->degree < 0 || o->degree > 2) { *err = "illegal value for flag 'depthcal_degree': expected 0, 1 or 2"; return false; }
+  if (o->min_count < 1) { *err = "illegal value for flag 'depthcal_min_count': expected at least 1"; return false; }
+  if (!(o->min_spread >= 0.0 && o->min_spread <= 1e300)) { *err = "illegal value for flag 'depthcal_min_spread': expected at least 0"; return false; }
+  const double margin = FlagDouble("depthcal_margin"), sp = FlagDouble("grid_spacing");
+  const double gw = (double)(FlagInt("grid_width") - 1) * sp, gh = (double)(FlagInt("grid_height") - 1) * sp;
+  o->rect[0] = -margin; o->rect[1] = -margin; o->rect[2] = gw + margin; o->rect[3] = gh + margin;
+  if (!std::isfinite(margin) || !(o->rect[0] < o->rect[2] && o->rect[1] < o->rect[3])) { *err = "illegal value for flag 'depthcal_margin': the board rectangle is empty"; return false; }
+  return true;
+}
+// a pose file in the format -save_poses writes: lines of 12 numbers, the top three rows of T_wk, '%' starts a comment -> [q (x y z w), t]
+static bool ReadPoseFile(const std::string& path, std::vector<std::array<double, 7>>* poses, std::string* err) {
+  std::ifstream f(path);
+  if (!f) { *err = "cannot open pose file " + path; return false; }
+  std::string line;
+  while (std::getline(f, line)) {
+    if (line.find_first_not_of(" \t\r") == std::string::npos || line[line.find_first_not_of(" \t\r")] == '%') continue;
+    double m[12];
+    std::istringstream is(line);
+    for (int k = 0; k < 12; ++k) if (!(is >> m[k])) { *err = path + ": expected 12 numbers in a line"; return false; }
+    const double R[9] = {m[0], m[1], m[2], m[4], m[5], m[6], m[8], m[9], m[10]};
+    double q[4];                                         // the largest of the four components first (Shepperd), then unit length
+    const double tr = R[0] + R[4] + R[8];
+    if (tr > 0.0) { const double s = std::sqrt(tr + 1.0) * 2.0; q[3] = 0.25 * s; q[0] = (R[7] - R[5]) / s; q[1] = (R[2] - R[6]) / s; q[2] = (R[3] - R[1]) / s; }
+    else if (R[0] > R[4] && R[0] > R[8]) { const double s = std::sqrt(1.0 + R[0] - R[4] - R[8]) * 2.0; q[3] = (R[7] - R[5]) / s; q[0] = 0.25 * s; q[1] = (R[1] + R[3]) / s; q[2] = (R[2] + R[6]) / s; }
+    else if (R[4] > R[8]) { const double s = std::sqrt(1.0 + R[4] - R[0] - R[8]) * 2.0; q[3] = (R[2] - R[6]) / s; q[0] = (R[1] + R[3]) / s; q[1] = 0.25 * s; q[2] = (R[5] + R[7]) / s; }
+    else { const double s = std::sqrt(1.0 + R[8] - R[0] - R[4]) * 2.0; q[3] = (R[3] - R[1]) / s; q[0] = (R[2] + R[6]) / s; q[1] = (R[5] + R[7]) / s; q[2] = 0.25 * s; }
+    const double n = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+    if (!(n > 0.5 && n < 2.0)) { *err = path + ": a line holds no rotation"; return false; }
+    poses->push_back({{q[0] / n, q[1] / n, q[2] / n, q[3] / n, m[3], m[7], m[11]}});
+  }
+  return true;
+}
+static bool ReadDepthFiles(const std::vector<std::string>& files, int w, int h, const std::string& who, std::vector<unsigned short>* depth, std::string* err) {
+  const size_t ns = (size_t)w * h;
+  for (size_t k = 0; k < files.size(); ++k) {
+    int fw = 0, fh = 0;
+    std::vector<unsigned short> px;
+    if (!ReadPgm16(files[k], &fw, &fh, &px, err)) return false;
+    if (k == 0 && w == 0) { w = fw; h = fh; }
+    if (fw != w || fh != h) { *err = files[k] + ": " + std::to_string(fw) + " x " + std::to_string(fh) + " pixels, " + who + " has " + std::to_string(w) + " x " + std::to_string(h); return false; }
+    depth->insert(depth->end(), px.begin(), px.end());
+  }
+  (void)ns;
+  return true;
+}
+static bool MakeDir(const std::string& dir, std::string* err) {
+  struct stat st;
+  if (mkdir(dir.c_str(), 0777) != 0 && !(stat(dir.c_str(), &st) == 0 && S_ISDIR(st.st_mode))) { *err = "cannot create the directory " + dir; return false; }      // (one level)
+  return true;
+}
+// Fits the correction of camera o.cam from the depth images and the frames' poses (n x 7), in batches of at most 16.  Everything that can be
+// said without a device is said first.  Exit status: 0, 1 (an error said in *err) or 3 (no device).
+static int DepthCalFit(const std::vector<vic::CameraAndPose>& cams, const std::vector<std::array<double, 7>>& poses, const char* poses_from, const DepthCalCli& o, int device,
+                       std::string* err) {
+  if ((size_t)o.cam >= cams.size()) { *err = "illegal value for flag 'depthcal_cam': camera " + std::to_string(o.cam) + " of a rig of " + std::to_string(cams.size()) + " cameras"; return 1; }
+  const vic::CameraAndPose& S = cams[o.cam];
+  std::vector<std::string> files;
+  if (!GlobSorted(StripScheme(o.depth), &files)) { *err = "no depth image matches " + o.depth; return 1; }
+  if (files.size() != poses.size()) { *err = "-depthcal_depth matches " + std::to_string(files.size()) + " files and " + poses_from + " has " + std::to_string(poses.size()) + " frames"; return 1; }
+  std::vector<unsigned short> depth;
+  if (!ReadDepthFiles(files, S.width, S.height, "camera " + std::to_string(o.cam), &depth, err)) return 1;
+  if (!MakeDir(o.dir, err)) return 1;
+  vc_depthcal* d = nullptr;
+  const int st_create = vc_depthcal_create(device, S.model, S.params.data(), (int)S.params.size(), S.width, S.height, S.T_ck.data(), o.unit, o.kind, o.rect, o.bx, o.by,
+                                           o.v_ref, o.min_cos, o.max_dev, &d);
+  if (st_create == VC_ERR_NO_DEVICE) { *err = "no HIP device (there is no CPU fallback)"; return 3; }
+  if (st_create != VC_OK) { *err = "the depth calibration refuses this camera (status " + std::to_string(st_create) + ")"; return 1; }
+  const size_t ns = (size_t)S.width * S.height, n = files.size();
+  const int cells = o.bx * o.by;
+  int status = 0;
+  FILE* ff = std::fopen((o.dir + "/depthcal_frames.csv").c_str(), "w");
+  if (!ff) { vc_depthcal_destroy(d); *err = "cannot write " + o.dir + "/depthcal_frames.csv"; return 1; }
+  std::fprintf(ff, "image,zero,no_ray,behind,outside,grazing,value_range,gate,used,qx,qy,qz,qw,tx,ty,tz\n");
+  for (size_t first = 0; first < n && status == 0; first += 16) {
+    const int m = (int)std::min<size_t>(16, n - first);
+    std::vector<long long> cnt(8 * (size_t)m);
+    const int q = vc_depthcal_add(d, m, depth.data() + first * ns, 2 * S.width, (long long)(2 * ns), poses[first].data(), cnt.data());
+    if (q != VC_OK) { *err = q == VC_ERR_BAD_ARG ? "a frame's pose is not a rigid motion" : "the accumulation failed (status " + std::to_string(q) + ")"; status = q == VC_ERR_NO_DEVICE ? 3 : 1; break; }
+    for (int k = 0; k < m; ++k) {
+      std::fprintf(ff, "%s", BaseName(files[first + k]).c_str());
+      for (int c = 0; c < 8; ++c) std::fprintf(ff, ",%lld", cnt[8 * (size_t)k + c]);
+      for (int c = 0; c < 7; ++c) std::fprintf(ff, ",%.17g", poses[first + k][c]);
+      std::fprintf(ff, "\n");
+    }
+  }
+  if (std::fclose(ff) != 0 && status == 0) { *err = "cannot write " + o.dir + "/depthcal_frames.csv in full"; status = 1; }
+  std::vector<double> sums((size_t)cells * 9), a(cells), b(cells);
+  std::vector<int> st(cells);
+  double c[3], rms[3];
+  long long total[8];
+  if (status == 0) {
+    int q = vc_depthcal_sums(d, sums.data(), nullptr, total, nullptr);
+    if (q == VC_OK) q = vc_depthcal_fit(d, o.degree, o.min_count, o.min_spread);
+    if (q == VC_OK) q = vc_depthcal_get_fit(d, c, a.data(), b.data(), st.data(), rms, nullptr);
+    if (q == VC_ERR_NUMERIC) { *err = "no correction can be fitted: " + std::to_string(total[7]) + " pixels of " + std::to_string(n) + " frames see the board"; status = 1; }
+    else if (q != VC_OK) { *err = "the fit failed (status " + std::to_string(q) + ")"; status = q == VC_ERR_NO_DEVICE ? 3 : 1; }
+  }
+  vc_depthcal_destroy(d);
+  if (status != 0) return status;
+  FILE* fc = std::fopen((o.dir + "/depthcal_cells.csv").c_str(), "w");
+  if (!fc) { *err = "cannot write " + o.dir + "/depthcal_cells.csv"; return 1; }
+  std::fprintf(fc, "cx,cy,n,sum_x,sum_x2,sum_x3,sum_x4,sum_d,sum_dx,sum_dx2,sum_dd\n");
+  for (int k = 0; k < cells; ++k) {
+    std::fprintf(fc, "%d,%d", k % o.bx, k / o.bx);
+    for (int t = 0; t < 9; ++t) std::fprintf(fc, ",%.17g", sums[(size_t)k * 9 + t]);
+    std::fprintf(fc, "\n");
+  }
+  if (std::fclose(fc) != 0) { *err = "cannot write " + o.dir + "/depthcal_cells.csv in full"; return 1; }
+  FILE* fo = std::fopen((o.dir + "/depth_correction.csv").c_str(), "w");
+  if (!fo) { *err = "cannot write " + o.dir + "/depth_correction.csv"; return 1; }
+  std::fprintf(fo, "size,%d,%d\nbins,%d,%d\nv_ref,%.17g\nunit,%.17g\ndegree,%d\nc,%.17g,%.17g,%.17g\ncx,cy,n,status,a,b\n", S.width, S.height, o.bx, o.by, o.v_ref, o.unit, o.degree,
+               c[0], c[1], c[2]);
+  int n_status[3] = {0, 0, 0};
+  for (int k = 0; k < cells; ++k) {
+    std::fprintf(fo, "%d,%d,%.17g,%d,%.17g,%.17g\n", k % o.bx, k / o.bx, sums[(size_t)k * 9], st[k], a[k], b[k]);
+    ++n_status[st[k]];
+  }
+  if (std::fclose(fo) != 0) { *err = "cannot write " + o.dir + "/depth_correction.csv in full"; return 1; }
+  std::printf("depth calibration of camera %d (%s) from %zu frames, %lld pixels: rms %.4g counts raw, %.4g after the polynomial, %.4g after the cells; %d cells fitted, "
+              "%d with an offset only, %d with too few pixels -> %s\n", o.cam, ModelName(S.model), n, total[7], rms[0], rms[1], rms[2], n_status[0], n_status[1], n_status[2],
+              o.dir.c_str());
+  return 0;
+}
+struct DepthCorrectionFile { int w = 0, h = 0, bx = 0, by = 0, degree = 0; double v_ref = 0, unit = 0, c[3] = {0, 0, 0}; std::vector<double> a, b; };
+static bool ReadDepthCorrection(const std::string& path, DepthCorrectionFile* f, std::string* err) {
+  std::ifstream in(path);
+  if (!in) { *err = "cannot open correction file " + path; return false; }
+  std::string line;
+  bool ok = true;
+  auto header = [&](const char* fmt, auto... ptr) { ok = ok && std::getline(in, line) && std::sscanf(line.c_str(), fmt, ptr...) == (int)sizeof...(ptr); };
+  header("size,%d,%d", &f->w, &f->h); header("bins,%d,%d", &f->bx, &f->by); header("v_ref,%lf", &f->v_ref); header("unit,%lf", &f->unit); header("degree,%d", &f->degree);
+  header("c,%lf,%lf,%lf", &f->c[0], &f->c[1], &f->c[2]);
+  ok = ok && std::getline(in, line) && line.compare(0, 5, "cx,cy") == 0;
+  if (!ok || f->w < 2 || f->h < 2 || f->w > 8192 || f->h > 8192 || f->bx < 1 || f->by < 1 || f->bx > 32 || f->by > 32 || f->degree < 0 || f->degree > 2 || !(f->v_ref > 0.0) ||
+      !(f->unit > 0.0)) { *err = path + ": not a depth correction file"; return false; }
+  f->a.assign((size_t)f->bx * f->by, 0.0); f->b = f->a;
+  for (int k = 0; k < f->bx * f->by; ++k) {
+    int cx, cy, st; double n;
+    if (!std::getline(in, line) || std::sscanf(line.c_str(), "%d,%d,%lf,%d,%lf,%lf", &cx, &cy, &n, &st, &f->a[k], &f->b[k]) != 6 || cx != k % f->bx || cy != k / f->bx) {
+      *err = path + ": expected the row of cell " + std::to_string(k); return false;
+    }
+  }
+  return true;
+}
+// Corrects the images of -depthcal_depth with a correction file.  Exit status as above.
+static int DepthCalApply(const DepthCalCli& o, int device, std::string* err) {
+  DepthCorrectionFile f;
+  if (!ReadDepthCorrection(o.file, &f, err)) return 1;
+  std::vector<std::string> files;
+  if (!GlobSorted(StripScheme(o.depth), &files)) { *err = "no depth image matches " + o.depth; return 1; }
+  std::vector<unsigned short> depth;
+  if (!ReadDepthFiles(files, f.w, f.h, "the correction", &depth, err)) return 1;
+  if (!MakeDir(o.dir, err)) return 1;
+  // the correction needs no camera: any camera of the file's size serves the handle
+  const double K[4] = {(double)f.w, (double)f.w, 0.5 * (f.w - 1), 0.5 * (f.h - 1)}, T[7] = {0, 0, 0, 1, 0, 0, 0}, rect[4] = {0, 0, 1, 1};
+  vc_depthcal* d = nullptr;
+  const int st_create = vc_depthcal_create(device, 4 /* linear */, K, 4, f.w, f.h, T, f.unit, 0, rect, f.bx, f.by, f.v_ref, 1.0, 1.0, &d);
+  if (st_create == VC_ERR_NO_DEVICE) { *err = "no HIP device (there is no CPU fallback)"; return 3; }
+  if (st_create != VC_OK || vc_depthcal_set_fit(d, f.degree, f.c, f.a.data(), f.b.data()) != VC_OK) { vc_depthcal_destroy(d); *err = "the correction file is refused"; return 1; }
+  const size_t ns = (size_t)f.w * f.h, n = files.size();
+  FILE* csv = std::fopen((o.dir + "/depthcal_apply.csv").c_str(), "w");
+  if (!csv) { vc_depthcal_destroy(d); *err = "cannot write " + o.dir + "/depthcal_apply.csv"; return 1; }
+  std::fprintf(csv, "image,zero,corrected,out_of_range\n");
+  int status = 0;
+  long long done = 0, lost = 0;
+  for (size_t first = 0; first < n && status == 0; first += 16) {
+    const int m = (int)std::min<size_t>(16, n - first);
+    long long cnt[3 * 16];
+    unsigned short* img = depth.data() + first * ns;
+    const int q = vc_depthcal_apply(d, m, img, 2 * f.w, (long long)(2 * ns), img, 2 * f.w, (long long)(2 * ns), o.interp, cnt);
+    if (q != VC_OK) { *err = "the correction failed (status " + std::to_string(q) + ")"; status = q == VC_ERR_NO_DEVICE ? 3 : 1; break; }
+    for (int k = 0; k < m && status == 0; ++k) {
+      const std::string name = BaseName(files[first + k]);
+      if (!WritePgm16(o.dir + "/" + name + ".pgm", f.w, f.h, img + k * ns, err)) status = 1;
+      std::fprintf(csv, "%s,%lld,%lld,%lld\n", name.c_str(), cnt[3 * k], cnt[3 * k + 1], cnt[3 * k + 2]);
+      done += cnt[3 * k + 1]; lost += cnt[3 * k + 2];
+    }
+  }
+  if (std::fclose(csv) != 0 && status == 0) { *err = "cannot write " + o.dir + "/depthcal_apply.csv in full"; status = 1; }
+  vc_depthcal_destroy(d);
+  if (status != 0) return status;
+  std::printf("corrected %zu depth images (%s): %lld values corrected, %lld out of range -> %s\n", n, o.interp ? "bilinear" : "cell", done, lost, o.dir.c_str());
+  return 0;
+}
+
 // ---- -convert_models / -convert_to: calibrated cameras converted to other camera models (vc_convert*) ------------------------------------
 static const char* ModelXmlType(int id) {
   static const char* n[] = {"calibu_fu_fv_u0_v0_w", "calibu_fu_fv_u0_v0_k1_k2", "calibu_fu_fv_u0_v0_k1_k2_k3", "calibu_fu_fv_u0_v0_kb4", "calibu_fu_fv_u0_v0", "calibu_fu_fv_u0_v0_rational6"};
@@ -1296,6 +1534,25 @@ int main(int argc, char** argv) {
   if (!RegisterFlags(&reg, &err)) { std::fprintf(stderr, "ERROR: %s\n", err.c_str()); return 1; }
   if (reg.on && (!FlagString("compare_models").empty() || !FlagString("convert_models").empty())) {
     std::fprintf(stderr, "ERROR: -register_models / -register_depth and -compare_models / -convert_models exclude each other\n"); return 1;
+  }
+  // ---- -depthcal_models rig.xml -depthcal_poses ... / -depthcal_apply file: file to file, nothing is calibrated; -depthcal_depth alone: behind the result
+  DepthCalCli depthcal;
+  if (!DepthCalFlags(&depthcal, &err)) { std::fprintf(stderr, "ERROR: %s\n", err.c_str()); return 1; }
+  if (depthcal.on && (!FlagString("compare_models").empty() || !FlagString("convert_models").empty() || !FlagString("register_models").empty())) {
+    std::fprintf(stderr, "ERROR: -depthcal_models / -depthcal_depth / -depthcal_apply and -compare_models / -convert_models / -register_models exclude each other\n"); return 1;
+  }
+  if (depthcal.apply) {
+    const int rc = DepthCalApply(depthcal, (int)FlagInt("device"), &err);
+    if (rc != 0) std::fprintf(stderr, "%s %s\n", rc == 3 ? "F" : "E depth correction failed:", err.c_str());
+    return rc;
+  }
+  if (!depthcal.models.empty()) {
+    std::vector<vic::CameraAndPose> a;
+    std::vector<std::array<double, 7>> poses;
+    if (!ReadRigFile(depthcal.models, &a, &err) || !ReadPoseFile(depthcal.poses, &poses, &err)) { std::fprintf(stderr, "F %s\n", err.c_str()); return 1; }
+    const int rc = DepthCalFit(a, poses, "-depthcal_poses", depthcal, (int)FlagInt("device"), &err);
+    if (rc != 0) std::fprintf(stderr, "%s %s\n", rc == 3 ? "F" : "E depth calibration failed:", err.c_str());
+    return rc;
   }
   if (!FlagString("register_models").empty()) {
     std::vector<vic::CameraAndPose> a;
@@ -1820,6 +2077,15 @@ int main(int argc, char** argv) {
       std::fprintf(stderr, "E registration failed: %s\n", err.c_str()); register_failed = true;
     }
   }
+  bool depthcal_failed = false;
+  if (depthcal.on) {                                     // -depthcal_depth: with the cameras just written and the poses of the calibration's frames, in their order
+    std::vector<vic::CameraAndPose> a;
+    std::vector<std::array<double, 7>> poses;
+    for (size_t i = 0; i < all_frames.size(); ++i) { std::array<double, 7> T; for (int k = 0; k < 7; ++k) T[k] = all_frames[i].t_wp_.v[k]; poses.push_back(T); }
+    if (!ReadRigFile(FlagString("output"), &a, &err) || DepthCalFit(a, poses, "the calibration", depthcal, (int)FlagInt("device"), &err) != 0) {
+      std::fprintf(stderr, "E depth calibration failed: %s\n", err.c_str()); depthcal_failed = true;
+    }
+  }
   if (FlagBool("print_poses")) {
     if (FILE* f = std::fopen("poses.txt", "w")) {
       for (size_t i = 0; i < all_frames.size(); ++i) { double c[6]; T2Cart(all_frames[i].t_wp_.data(), c); std::fprintf(f, "%f\t%f\t%f\t%f\t%f\t%f\n", c[0], c[1], c[2], c[3], c[4], c[5]); }
@@ -1861,5 +2127,6 @@ int main(int argc, char** argv) {
   if (uncertainty_failed) std::fprintf(stderr, "E -uncertainty_dir: the uncertainty map's files are incomplete (exit status %d)\n", success ? 1 : 2);
   if (select_failed) std::fprintf(stderr, "E -select_views: the selection's files are incomplete (exit status %d)\n", success ? 1 : 2);
   if (register_failed) std::fprintf(stderr, "E -register_depth: the registered images are incomplete (exit status %d)\n", success ? 1 : 2);
-  return success ? ((undistort_failed || rectify_failed || compare_failed || convert_failed || uncertainty_failed || select_failed || register_failed) ? 1 : 0) : 2;
+  if (depthcal_failed) std::fprintf(stderr, "E -depthcal_depth: the depth correction is incomplete (exit status %d)\n", success ? 1 : 2);
+  return success ? ((undistort_failed || rectify_failed || compare_failed || convert_failed || uncertainty_failed || select_failed || register_failed || depthcal_failed) ? 1 : 0) : 2;
 }

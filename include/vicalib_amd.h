@@ -731,6 +731,83 @@ int vc_register_points(vc_registrar* r, int n, const double* in /* n x 3 */, dou
  * device-resident images (a slanted surface of 1000..2499 counts), [2] the gather, [3] 65536 points. */
 int vc_time_register(vc_registrar* r, int n_images, int reps, double out_ms[4]);
 
+/* ---- calibrating a depth camera's range error against the target ---------------------------------------------------------------------
+ * A calibration run holds what is needed to measure the range error of a depth sensor directly: every frame has a pose T_wk, the depth
+ * camera S has intrinsics and T_ck, and the target is a plane at z_w = 0 of known extent.  For every depth pixel that looks at the board
+ * the distance the sensor should have reported is known; compared with what it did report, over all frames and pixels, that gives the
+ * error as a function of value and image position, and from it a correction to apply before vc_register_depth.
+ * The handle holds S (any of the six models, params, a size from 2 x 2 to 8192 x 8192, T_ck; checked as by vc_registrar_create), unit
+ * (metres per count) and kind (0 Z, 1 range) as the registrar defines them, the board rectangle rect = [x0, y0, x1, y1] in the target plane
+ * (metres; x0 < x1, y0 < y1, finite), bins_x, bins_y in 1..32, v_ref > 0 (counts: a typical value of the working range, which only
+ * centres the arithmetic), min_cos in (0, 1] and max_dev > 0 (counts).
+ * Geometry.  With p_c = R_ck p_k + t_ck and p_w = R_wk p_k + t_wk: R_wc = R_wk R_ck^T, c_w = t_wk - R_wc t_ck.  For pixel (i, j) of a
+ * frame with value v: the ray r is the registrar's (Newton inversion of vc_undistort_points at the pixel centre; r_z > 0 required under
+ * kind Z); d_w = R_wc r; s = -c_w.z / d_w.z; hit = c_w + s d_w; the expected distance e = s r_z (kind Z) or s |r| (kind range); in
+ * counts y = e / unit.
+ * A pixel is dropped by the FIRST of these rules that applies; each is counted per frame:
+ *   0  v == 0
+ *   1  no ray (the registrar's rule 1)
+ *   2  s not finite or s <= 0: the plane is not in front along the ray
+ *   3  hit outside rect (closed)
+ *   4  |d_w.z| < min_cos |d_w|: grazing incidence
+ *   5  y outside [1, 65535]
+ *   6  |y - v| > max_dev: the gate (an occluder, a hand, a multipath blunder)
+ *   7  pixels used (not a drop)
+ * A used pixel adds, with x = (v - v_ref) / v_ref and d = y - v, to the nine sums [1, x, x^2, x^3, x^4, d, d x, d x^2, d^2] of its image
+ * cell (report_cell(i, bins_x, w), report_cell(j, bins_y, h)), the binning of the report's error maps; cell index cy * bins_x + cx.  The
+ * handle keeps bins_x * bins_y * 9 running sums, 8 running counters and a frame count over everything added since create or clear.  The
+ * order in which a pixel's terms enter a cell's sums depends on the image size, the bins and the order of the frames only: a batch of 8,
+ * 3 + 5 and eight single calls give the same bits, as do two runs and two handles.
+ * Fit, from the sums alone, on the host.  Stage 1: P(x) = c0 + c1 x + c2 x^2 of degree g in {0, 1, 2} fitted to d by least squares over
+ * the totals (VC_ERR_NUMERIC without a pixel or without a positive pivot).  Stage 2, per cell: a + b x fitted to the remainder d - P(x),
+ * whose sums follow from the nine.  status 0: n >= min_count and the variance of x in the cell >= min_spread^2 -- a and b fitted;
+ * 1: enough pixels but too little spread -- a alone, b = 0; 2: too few pixels -- a = b = 0.  rms[3] in counts, from the sums: raw
+ * (sqrt(S_dd / n)), after stage 1, after stage 2.
+ * Correction of a value v != 0 at pixel (i, j): delta = P(x) + A + B x, v' = floor(v + delta + 0.5); a v' outside 1..65535 becomes 0 and
+ * is counted.  interp 0: (A, B) are the pixel's own cell's (a, b); interp 1: bilinear between cell centres, fx = (i + 0.5) bins_x / w - 0.5
+ * clamped to [0, bins_x - 1], k0 = floor(fx), k1 = min(k0 + 1, bins_x - 1), likewise in y.
+ * Images are HOST buffers under the registrar's pitch / stride / alignment rules.  A handle is single-threaded, with a stream and pinned
+ * staging of its own.  Argument errors are VC_ERR_BAD_ARG and come before the device is looked for; no CPU fallback (VC_ERR_NO_DEVICE).
+ * n = 0 is VC_OK without a launch; n <= 65535. */
+typedef struct vc_depthcal vc_depthcal;
+int vc_depthcal_create(int device, int model, const double* params, int nparams, int w, int h, const double T_ck[7], double unit, int kind,
+                       const double rect[4], int bins_x, int bins_y, double v_ref, double min_cos, double max_dev, vc_depthcal** out);
+/* the same for camera cam of a calibrator as vc_get_camera returns it, on the calibrator's device */
+int vc_depthcal_create_for_camera(vc_calibrator* h, int cam, double unit, int kind, const double rect[4], int bins_x, int bins_y, double v_ref,
+                                  double min_cos, double max_dev, vc_depthcal** out);
+void vc_depthcal_destroy(vc_depthcal* d);
+/* size (w, h), bins, unit, kind, rect, v_ref, min_cos, max_dev, R_ck (row-major), t_ck; any pointer may be NULL */
+int vc_depthcal_get(vc_depthcal* d, int size[2], int bins[2], double* unit, int* kind, double rect[4], double* v_ref, double* min_cos,
+                    double* max_dev, double R_ck[9], double t_ck[3]);
+/* sums, counters and the frame count back to zero; a fit that came from the sums is dropped */
+int vc_depthcal_clear(vc_depthcal* d);
+/* n depth images with their frames' poses T_wk (n x 7) added to the sums.  counters (nullable): n x 8, the table above, per frame.  One
+ * upload, the launches and one synchronisation per call.  A pose that is not finite or not of unit length to 1e-6 is VC_ERR_BAD_ARG and
+ * nothing is added.  A fit that came from the sums is dropped. */
+int vc_depthcal_add(vc_depthcal* d, int n, const unsigned short* depth, int pitch, long long stride, const double* T_wk /* n x 7 */,
+                    long long* counters /* n x 8, nullable */);
+/* The per-pixel face, and the depth image the calibration predicts: y (n x h x w doubles) the expected value in counts, rule (n x h x w
+ * bytes) the first rule that drops the pixel or 7; y = NaN under rules 1 and 2.  Without depth (NULL) rules 0 and 6 are not applied. */
+int vc_depthcal_expected(vc_depthcal* d, int n, const double* T_wk /* n x 7 */, const unsigned short* depth /* nullable */, int pitch,
+                         long long stride, double* y, unsigned char* rule);
+/* sums: cells x 9; totals: the cells' sums added in cell order; the running counters; the frame count.  Any pointer may be NULL. */
+int vc_depthcal_sums(vc_depthcal* d, double* sums, double totals[9], long long counters[8], long long* n_frames);
+/* the fit of the sums as they stand (min_count >= 1, min_spread >= 0) */
+int vc_depthcal_fit(vc_depthcal* d, int degree, int min_count, double min_spread);
+/* c[3], a / b / status (cells each), rms[3], degree; any pointer may be NULL.  VC_ERR_BAD_ARG before a fit: adding frames or clearing
+ * drops a fit that came from the sums, and nothing stale is returned. */
+int vc_depthcal_get_fit(vc_depthcal* d, double c[3], double* a, double* b, int* status, double rms[3], int* degree);
+/* a correction read from a file, for a fresh handle to apply: it stays until the next fit or set_fit (its rms are NaN) */
+int vc_depthcal_set_fit(vc_depthcal* d, int degree, const double c[3], const double* a, const double* b);
+/* n depth images corrected by the handle's fit (VC_ERR_BAD_ARG without one).  dst == src is allowed; a destination row's padding is not
+ * written.  counters (nullable): n x 3 -- zeros in, values corrected, values out of range.  One upload, one launch, one download and one
+ * synchronisation per call. */
+int vc_depthcal_apply(vc_depthcal* d, int n, const unsigned short* src, int src_pitch, long long src_stride, unsigned short* dst, int dst_pitch,
+                      long long dst_stride, int interp, long long* counters /* n x 3, nullable */);
+/* HIP events on the handle's stream, `reps` launches each: out_ms[0] the table build, [1] accumulate + fold of n_images device-resident
+ * images (into sums of the timer's own), [2] the apply. */
+int vc_time_depthcal(vc_depthcal* d, int n_images, int reps, double out_ms[3]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -594,4 +594,58 @@ class Registrar {
   vc_registrar* r_ = nullptr;
 };
 
+// The range error of a depth camera measured against the calibration target and its correction (vc_depthcal*): frames with their poses are
+// added to binned sums, a polynomial in the value plus an affine term per image cell is fitted from the sums, and depth images are corrected.
+struct DepthCalOptions {
+  double unit = 0.001; int kind = 0; double rect[4] = {0, 0, 1, 1}; int bins_x = 4, bins_y = 3; double v_ref = 1000.0, min_cos = 0.5, max_dev = 100.0;
+};
+struct DepthCalFit { int degree = 0; double c[3] = {0, 0, 0}, rms[3] = {0, 0, 0}; std::vector<double> a, b; std::vector<int> status; };
+struct DepthCalSums { std::vector<double> sums; double totals[9]; long long counters[8]; long long n_frames = 0; };
+class DepthCalibrator {
+ public:
+  DepthCalibrator(const CameraAndPose& cam, const DepthCalOptions& o, int device = 0) : cells_(o.bins_x * o.bins_y) {
+    vc_checked(vc_depthcal_create(device, cam.model, cam.params.data(), (int)cam.params.size(), cam.width, cam.height, cam.T_ck.data(), o.unit, o.kind, o.rect, o.bins_x,
+                                  o.bins_y, o.v_ref, o.min_cos, o.max_dev, &d_), "DepthCalibrator");
+  }
+  DepthCalibrator(ViCalibrator& cal, int cam, const DepthCalOptions& o) : cells_(o.bins_x * o.bins_y) {
+    vc_checked(vc_depthcal_create_for_camera(cal.handle(), cam, o.unit, o.kind, o.rect, o.bins_x, o.bins_y, o.v_ref, o.min_cos, o.max_dev, &d_), "DepthCalibrator");
+  }
+  ~DepthCalibrator() { vc_depthcal_destroy(d_); }
+  DepthCalibrator(const DepthCalibrator&) = delete;
+  DepthCalibrator& operator=(const DepthCalibrator&) = delete;
+  void Clear() { vc_checked(vc_depthcal_clear(d_), "Clear"); }
+  // T_wk: n x 7; counters (n x 8) may be nullptr; pitch and stride in bytes
+  void Add(int n, const unsigned short* depth, int pitch, long long stride, const double* T_wk, long long* counters = nullptr) {
+    vc_checked(vc_depthcal_add(d_, n, depth, pitch, stride, T_wk, counters), "Add");
+  }
+  // y: n x h x w, rule: n x h x w; depth may be nullptr
+  void Expected(int n, const double* T_wk, const unsigned short* depth, int pitch, long long stride, double* y, unsigned char* rule) {
+    vc_checked(vc_depthcal_expected(d_, n, T_wk, depth, pitch, stride, y, rule), "Expected");
+  }
+  DepthCalSums Sums() {
+    DepthCalSums s; s.sums.resize((size_t)cells_ * 9);
+    vc_checked(vc_depthcal_sums(d_, s.sums.data(), s.totals, s.counters, &s.n_frames), "Sums");
+    return s;
+  }
+  DepthCalFit Fit(int degree = 2, int min_count = 50, double min_spread = 0.02) { vc_checked(vc_depthcal_fit(d_, degree, min_count, min_spread), "Fit"); return GetFit(); }
+  DepthCalFit GetFit() {
+    DepthCalFit f; f.a.resize(cells_); f.b.resize(cells_); f.status.resize(cells_);
+    vc_checked(vc_depthcal_get_fit(d_, f.c, f.a.data(), f.b.data(), f.status.data(), f.rms, &f.degree), "GetFit");
+    return f;
+  }
+  void SetFit(int degree, const double c[3], const double* a, const double* b) { vc_checked(vc_depthcal_set_fit(d_, degree, c, a, b), "SetFit"); }
+  // counters (n x 3: zeros in, corrected, out of range) may be nullptr; dst == src is allowed
+  void Apply(int n, const unsigned short* src, int src_pitch, long long src_stride, unsigned short* dst, int dst_pitch, long long dst_stride, int interp = 0,
+             long long* counters = nullptr) {
+    vc_checked(vc_depthcal_apply(d_, n, src, src_pitch, src_stride, dst, dst_pitch, dst_stride, interp, counters), "Apply");
+  }
+  std::array<double, 3> Time(int n_images = 8, int reps = 20) { std::array<double, 3> ms{{0, 0, 0}}; vc_checked(vc_time_depthcal(d_, n_images, reps, ms.data()), "Time"); return ms; }
+  int Cells() const { return cells_; }
+  vc_depthcal* handle() { return d_; }
+
+ private:
+  vc_depthcal* d_ = nullptr;
+  int cells_ = 0;
+};
+
 }  // namespace visual_inertial_calibration

@@ -355,6 +355,14 @@ int vc_registrar_create_for_cameras(vc_calibrator* h, int s, int d, double unit_
   return vc_registrar_create(h->device, cs.model, cs.K, cs.nk, cs.width, cs.height, cs.T_ck, cd.model, cd.K, cd.nk, cd.width, cd.height, cd.T_ck, unit_src, unit_dst,
                              kind, splat, out);
 }
+// a depth calibrator (vc_depthcal.hip) of depth camera c as vc_get_camera returns it, on the calibrator's device
+int vc_depthcal_create_for_camera(vc_calibrator* h, int c, double unit, int kind, const double rect[4], int bins_x, int bins_y, double v_ref, double min_cos,
+                                  double max_dev, vc_depthcal** out) {
+  if (!h || c < 0 || c >= (int)h->cams.size()) return VC_ERR_BAD_ARG;
+  HostCam cm;
+  { std::lock_guard<std::mutex> lk(h->result_mutex); cm = h->cams[c]; }
+  return vc_depthcal_create(h->device, cm.model, cm.K, cm.nk, cm.width, cm.height, cm.T_ck, unit, kind, rect, bins_x, bins_y, v_ref, min_cos, max_dev, out);
+}
 // an uncertainty map (vc_uncertainty.hip) of camera c as vc_get_camera returns it, on the calibrator's device, with the camera's params block of
 // vc_get_solution_covariance at the current state (the layout of covariance_layout: q_ck (4), p_ck (3), params (nk) per camera)
 int vc_uncertainty_create_for_camera(vc_calibrator* h, int c, int grid_x, int grid_y, vc_uncertainty** out) {

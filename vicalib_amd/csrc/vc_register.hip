@@ -2,7 +2,7 @@
 // the pixels of the destination camera D, and D's 8-bit image taken into S's pixels, on the GPU.  Definitions: include/vicalib_amd.h; the
 // arithmetic: vc_register.hpp.
 //
-//   k_reg_rays       built once at create: the ray of every pixel centre (w_s x h_s) and of every node of the corner lattice
+//   k_reg_rays       (vc_reg_rays.hpp) built once at create: the ray of every pixel centre (w_s x h_s) and of every node of the corner lattice
 //                    ((w_s + 1) x (h_s + 1), node (i, j) at (i - 0.5, j - 0.5)) by Newton inversion; a ray is an fp64 pair (x, y) plus z, and
 //                    z = NaN says that the position has no ray
 //   k_reg_scatter    one thread per source pixel of the batch: a forward warp.  The depth test is ONE 64-bit atomicMin per destination pixel
@@ -19,49 +19,27 @@
 #include <cstring>
 #include "../../include/vicalib_amd.h"
 #include "vc_hostutil.hpp"
+#include "vc_reg_rays.hpp"
 #include "vc_register.hpp"
 
 namespace {
 
 using vc::RegisterPlan;
+using vc::RegTables;
+using vc::load_ray;
 typedef unsigned long long u64;
 constexpr int kTimePoints = 65536;
 constexpr int kMaxImages = 65535;                      // (the image index is the grid's y)
 
-// the ray tables: centres [h_s][w_s], lattice [h_s + 1][w_s + 1]
-struct RegTables {
-  double2* c_xy; double* c_z;
-  double2* l_xy; double* l_z;
-};
 // a batch of images of one camera: rows `pitch` bytes apart, images `stride` bytes apart
 struct RegImages {
   unsigned char* p; int pitch; size_t stride;
 };
 
-__device__ __forceinline__ bool load_ray(const double2* xy, const double* z, size_t k, double* ray) {
-  const double2 a = xy[k];
-  ray[0] = a.x; ray[1] = a.y; ray[2] = z[k];
-  return ray[2] == ray[2];
-}
 // the lanes of this wavefront that hold `pred`, added to *counter by one atomic of lane 0
 __device__ __forceinline__ void count_wave(bool pred, u64* counter) {
   const u64 b = __ballot(pred);
   if ((threadIdx.x & 63) == 0 && b) atomicAdd(counter, (u64)__popcll(b));
-}
-
-__global__ __launch_bounds__(256) void k_reg_rays(RegisterPlan p, RegTables t) {
-  const int ns = p.s.w * p.s.h, lw = p.s.w + 1, nl = lw * (p.s.h + 1);
-  const int k = blockIdx.x * 256 + threadIdx.x;
-  if (k >= ns + nl) return;
-  const bool centre = k < ns;
-  const int e = centre ? k : k - ns, rw = centre ? p.s.w : lw;
-  const int j = e / rw, i = e - j * rw;
-  const double off = centre ? 0.0 : -0.5;
-  double ray[3];
-  const bool ok = vc::reg_ray(p, (double)i + off, (double)j + off, ray);
-  const double nan = __builtin_nan("");
-  (centre ? t.c_xy : t.l_xy)[e] = ok ? make_double2(ray[0], ray[1]) : make_double2(nan, nan);
-  (centre ? t.c_z : t.l_z)[e] = ok ? ray[2] : nan;
 }
 
 // keys: n x key_stride (key_stride >= w_d h_d); counters: n x 8
@@ -233,7 +211,7 @@ bool reserve_points(vc_registrar* r, int n) {
 dim3 grid_of(size_t threads, int n) { return dim3((unsigned)((threads + 255) / 256), (unsigned)n); }
 void launch_rays(vc_registrar* r) {
   const size_t total = r->ns() + (size_t)(r->p.s.w + 1) * (r->p.s.h + 1);
-  hipLaunchKernelGGL(k_reg_rays, grid_of(total, 1), dim3(256), 0, r->stream, r->p, r->tab);
+  hipLaunchKernelGGL(vc::k_reg_rays, grid_of(total, 1), dim3(256), 0, r->stream, r->p, r->tab, 1);
 }
 // clear, scatter and (with a destination) resolve of n images whose depth is on the device; counters: n x 8, zeroed here
 void launch_depth(vc_registrar* r, int n, RegImages src, bool resolve, RegImages dst, int* index, u64* counters) {

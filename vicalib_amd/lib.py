@@ -49,6 +49,8 @@ SYMBOLS = [
     "vc_select_frames", "vc_select_frame_information", "vc_select_last_gains", "vc_select_dim", "vc_time_select",
     "vc_registrar_create", "vc_registrar_create_for_cameras", "vc_registrar_destroy", "vc_register_get", "vc_register_depth", "vc_register_depth_device",
     "vc_register_stream", "vc_register_color", "vc_register_points", "vc_time_register",
+    "vc_depthcal_create", "vc_depthcal_create_for_camera", "vc_depthcal_destroy", "vc_depthcal_get", "vc_depthcal_clear", "vc_depthcal_add", "vc_depthcal_expected",
+    "vc_depthcal_sums", "vc_depthcal_fit", "vc_depthcal_get_fit", "vc_depthcal_set_fit", "vc_depthcal_apply", "vc_time_depthcal",
 ]
 
 
@@ -118,7 +120,7 @@ def load():
         L.vc_allreduce_calls.restype = C.c_longlong
         L.vc_last_error.restype = C.c_char_p
         for name in ("vc_destroy", "vc_detector_destroy", "vc_shard_comm_destroy", "vc_undistorter_destroy", "vc_rectifier_destroy", "vc_comparer_destroy", "vc_converter_destroy",
-                     "vc_uncertainty_destroy", "vc_selector_destroy", "vc_registrar_destroy"):
+                     "vc_uncertainty_destroy", "vc_selector_destroy", "vc_registrar_destroy", "vc_depthcal_destroy"):
             getattr(L, name).restype = None
         _lib = L
     return _lib
@@ -1303,3 +1305,129 @@ class Registrar:
         out = np.zeros(4)
         _check(self.L.vc_time_register(self.h, int(n_images), int(reps), _d(out)), "time_register")
         return dict(tables=out[0], depth=out[1], gather=out[2], points=out[3])
+
+
+class DepthCalibrator:
+    """The range error of a depth camera measured against the calibration target, and its correction (include/vicalib_amd.h:
+    vc_depthcal*).  cam is (model, params, (w, h), T_ck) of the depth camera; rect = (x0, y0, x1, y1) the board in the target plane;
+    kind "z" or "range".  add(depth, T_wk) -> counters [n, 8]; expected(T_wk, depth=None) -> (y [n, h, w], rule [n, h, w]);
+    sums() -> dict; fit(degree) -> dict; apply(depth, interp) -> (corrected, counters [n, 3])."""
+    KINDS = Registrar.KINDS
+    INTERPS = {"cell": 0, "bilinear": 1}
+
+    def __init__(self, cam, rect, bins=(4, 3), unit=0.001, kind="z", v_ref=1000.0, min_cos=0.5, max_dev=100.0, device=0, _camera_of=None):
+        self.L = load()
+        self.h = C.c_void_p()
+        kind = self.KINDS.get(kind, kind)
+        tail = (C.c_double(unit), int(kind), _d(rect), int(bins[0]), int(bins[1]), C.c_double(v_ref), C.c_double(min_cos), C.c_double(max_dev), C.byref(self.h))
+        if _camera_of is not None:
+            cal, c = _camera_of
+            _check(self.L.vc_depthcal_create_for_camera(cal.h, int(c), *tail), "depthcal_create_for_camera")
+        else:
+            m, K, size, T = cam
+            K = np.ascontiguousarray(K, dtype=np.float64)
+            _check(self.L.vc_depthcal_create(int(device), _model_id(m), _d(K), len(K), int(size[0]), int(size[1]), _d(T), *tail), "depthcal_create")
+        g = self.get()
+        self.size, self.bins = g["size"], g["bins"]
+        self.cells = self.bins[0] * self.bins[1]
+
+    @classmethod
+    def for_camera(cls, cal, cam, rect, **kw):
+        """For a camera of a ViCalibrator, with the model, parameters, size and pose it holds for it."""
+        return cls(None, rect, _camera_of=(cal, cam), **kw)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.vc_depthcal_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+    def get(self):
+        """-> dict(size, bins, unit, kind, rect, v_ref, min_cos, max_dev, R_ck, t_ck)"""
+        size = (C.c_int * 2)(); bins = (C.c_int * 2)(); unit = C.c_double(0); kind = C.c_int(0); rect = np.zeros(4)
+        v_ref = C.c_double(0); min_cos = C.c_double(0); max_dev = C.c_double(0); R = np.zeros((3, 3)); t = np.zeros(3)
+        _check(self.L.vc_depthcal_get(self.h, size, bins, C.byref(unit), C.byref(kind), _d(rect), C.byref(v_ref), C.byref(min_cos), C.byref(max_dev), _d(R), _d(t)),
+               "depthcal_get")
+        return dict(size=(size[0], size[1]), bins=(bins[0], bins[1]), unit=unit.value, kind=kind.value, rect=rect, v_ref=v_ref.value, min_cos=min_cos.value,
+                    max_dev=max_dev.value, R_ck=R, t_ck=t)
+
+    def clear(self):
+        _check(self.L.vc_depthcal_clear(self.h), "depthcal_clear")
+
+    def _images(self, arr):
+        a, _ = Registrar._batch(arr, np.uint16, self.size)
+        return a
+
+    @staticmethod
+    def _poses(T_wk, n):
+        T = np.ascontiguousarray(T_wk, dtype=np.float64).reshape(-1, 7)
+        assert len(T) == n, (len(T), n)
+        return T
+
+    def add(self, depth, T_wk):
+        """depth: uint16 [h, w] or [n, h, w] (strided rows and images allowed); T_wk: [n, 7] -> counters int64 [n, 8]"""
+        a = self._images(depth)
+        n = len(a)
+        T = self._poses(T_wk, n)
+        cnt = np.zeros((n, 8), dtype=np.int64)
+        _check(self.L.vc_depthcal_add(self.h, n, C.c_void_p(a.ctypes.data), int(a.strides[1]), C.c_longlong(a.strides[0]), _d(T), C.c_void_p(cnt.ctypes.data)), "depthcal_add")
+        return cnt
+
+    def expected(self, T_wk, depth=None):
+        """-> (y float64 [n, h, w], rule uint8 [n, h, w]); without depth rules 0 and 6 are not applied"""
+        T = np.ascontiguousarray(T_wk, dtype=np.float64).reshape(-1, 7)
+        n = len(T)
+        y = np.zeros((n, self.size[1], self.size[0])); rule = np.zeros(y.shape, dtype=np.uint8)
+        if depth is None:
+            ptr, pitch, stride = None, 0, 0
+        else:
+            a = self._images(depth)
+            assert len(a) == n
+            ptr, pitch, stride = C.c_void_p(a.ctypes.data), int(a.strides[1]), int(a.strides[0])
+        _check(self.L.vc_depthcal_expected(self.h, n, _d(T), ptr, pitch, C.c_longlong(stride), C.c_void_p(y.ctypes.data), C.c_void_p(rule.ctypes.data)), "depthcal_expected")
+        return y, rule
+
+    def sums(self):
+        """-> dict(sums [cells, 9], totals [9], counters [8], n_frames)"""
+        s = np.zeros((self.cells, 9)); tot = np.zeros(9); cnt = np.zeros(8, dtype=np.int64); nf = C.c_longlong(0)
+        _check(self.L.vc_depthcal_sums(self.h, C.c_void_p(s.ctypes.data), C.c_void_p(tot.ctypes.data), C.c_void_p(cnt.ctypes.data), C.byref(nf)), "depthcal_sums")
+        return dict(sums=s, totals=tot, counters=cnt, n_frames=nf.value)
+
+    def fit(self, degree=2, min_count=50, min_spread=0.02):
+        _check(self.L.vc_depthcal_fit(self.h, int(degree), int(min_count), C.c_double(min_spread)), "depthcal_fit")
+        return self.get_fit()
+
+    def get_fit(self):
+        """-> dict(c [3], a, b, status [cells], rms [3], degree)"""
+        c = np.zeros(3); a = np.zeros(self.cells); b = np.zeros(self.cells); st = np.zeros(self.cells, dtype=np.int32); rms = np.zeros(3); deg = C.c_int(0)
+        _check(self.L.vc_depthcal_get_fit(self.h, C.c_void_p(c.ctypes.data), C.c_void_p(a.ctypes.data), C.c_void_p(b.ctypes.data), C.c_void_p(st.ctypes.data),
+                                          C.c_void_p(rms.ctypes.data), C.byref(deg)), "depthcal_get_fit")
+        return dict(c=c, a=a, b=b, status=st, rms=rms, degree=deg.value)
+
+    def set_fit(self, degree, c, a, b):
+        a = np.ascontiguousarray(a, dtype=np.float64).ravel(); b = np.ascontiguousarray(b, dtype=np.float64).ravel()
+        assert len(a) == self.cells and len(b) == self.cells and len(c) == 3
+        _check(self.L.vc_depthcal_set_fit(self.h, int(degree), _d(c), _d(a), _d(b)), "depthcal_set_fit")
+
+    def apply(self, depth, interp="cell", out=None):
+        """depth: uint16 [h, w] or [n, h, w] -> (corrected uint16 [n, h, w], counters int64 [n, 3]: zeros in, corrected, out of range); out: where
+        the images go (strided rows allowed, `depth` itself included; only its pixels are written)"""
+        a = self._images(depth)
+        n = len(a)
+        if out is None:
+            o = np.zeros((n, self.size[1], self.size[0]), dtype=np.uint16)
+        else:
+            o = out[None] if out.ndim == 2 else out
+            assert o.dtype == np.uint16 and o.shape == a.shape and o.strides[2] == 2 and o.flags.writeable
+        cnt = np.zeros((n, 3), dtype=np.int64)
+        _check(self.L.vc_depthcal_apply(self.h, n, C.c_void_p(a.ctypes.data), int(a.strides[1]), C.c_longlong(a.strides[0]), C.c_void_p(o.ctypes.data), int(o.strides[1]),
+                                        C.c_longlong(o.strides[0]), int(self.INTERPS.get(interp, interp)), C.c_void_p(cnt.ctypes.data)), "depthcal_apply")
+        return o, cnt
+
+    def time(self, n_images=8, reps=20):
+        """Average ms per launch: table build, accumulate + fold of n_images device-resident images, apply."""
+        out = np.zeros(3)
+        _check(self.L.vc_time_depthcal(self.h, int(n_images), int(reps), _d(out)), "time_depthcal")
+        return dict(tables=out[0], accumulate=out[1], apply=out[2])
