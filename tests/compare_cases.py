@@ -21,6 +21,11 @@ SIZE = (640, 480)
 GRID = (53, 41)                                   # 2173 samples: no multiple of 64 or 256, nine workgroups of 256
 R_MAX = 400.0 * 0.745356 * (1 - 0.6 * 0.745356 ** 2)      # 198.76 px: where undistort_cases.BEYOND_K's image ends
 RING_COUNTS = (8, 5, 64)
+# (grid, fit radius): the sample counts at which the lattice core's workgroup record and its fold change shape -- 256: exactly one sweep
+# workgroup; 258: one and two samples; 1024: exactly one fit / Gram workgroup; 1025: one and one sample.  The two columns of 2 x 128 sit at
+# rho >= 0.8: its fit set is empty at 0.5, so it is fitted over the whole image.
+BOUNDARY_LATTICES = (((2, 128), 1.5), ((6, 43), 0.5), ((32, 32), 0.5), ((25, 41), 0.5))
+BOUNDARY_RING_COUNTS = (1, 8, 5, 64)
 FLAG_A, FLAG_B, FLAG_INVALID = 1, 2, 4
 
 

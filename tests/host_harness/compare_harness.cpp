@@ -13,11 +13,7 @@ extern "C" {
 int vch_run(int model_a, const double* Ka, int nka, int model_b, const double* Kb, int nkb, int w, int h, int gx, int gy, double fit_radius, int max_iters,
             const double* R_ba, int n_rings, double* fit_out, double* diff, unsigned char* flags, double* summary, double* rings) {
   vc::CmpPlan p;
-  std::memset(&p, 0, sizeof(p));
-  p.model_a = model_a; p.model_b = model_b; p.w = w; p.h = h; p.gx = gx; p.gy = gy; p.n = gx * gy;
-  for (int k = 0; k < nka; ++k) p.Ka[k] = Ka[k];
-  for (int k = 0; k < nkb; ++k) p.Kb[k] = Kb[k];
-  vc::model_precompute(model_a, p.Ka, &p.pre_a); vc::model_precompute(model_b, p.Kb, &p.pre_b);
+  vc::cmp_plan_set(&p, model_a, Ka, nka, model_b, Kb, nkb, w, h, gx, gy);
   const int n = p.n;
   std::vector<double> rays(3 * (size_t)n), qs(3 * (size_t)n);
   std::vector<unsigned char> f0(n);

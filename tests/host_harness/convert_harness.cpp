@@ -16,10 +16,9 @@ struct Lattice {
 };
 void make_lattice(Lattice* L, int model_a, const double* Ka, int nka, int w, int h, int model_b, int gx, int gy, double fit_radius) {
   vc::CmpPlan& p = L->p;
-  std::memset(&p, 0, sizeof(p));
-  p.model_a = model_a; p.model_b = model_b; p.w = w; p.h = h; p.gx = gx; p.gy = gy; p.n = gx * gy;
-  for (int k = 0; k < nka; ++k) p.Ka[k] = Ka[k];
-  vc::model_precompute(model_a, p.Ka, &p.pre_a);
+  double K0[10];
+  vc::cvt_default_start(model_b, Ka, K0);                          // (the plan's B outside a cost sweep, as the library has it)
+  vc::cmp_plan_set(&p, model_a, Ka, nka, model_b, K0, 10, w, h, gx, gy);
   const int n = p.n;
   L->rays.resize(3 * (size_t)n); L->qs.resize(3 * (size_t)n); L->flags.resize(n);
   for (int s = 0; s < n; ++s) {
@@ -88,11 +87,7 @@ int vch_convert(int model_a, const double* Ka, int nka, int w, int h, int model_
 // cmp_diff_sample, cmp_norm2): out = [count, sum |d|^2, max |d|, worst].
 int vch_convert_compare(int model_a, const double* Ka, int nka, int w, int h, int model_b, const double* Kb, int nkb, int gx, int gy, double* out) {
   vc::CmpPlan p;
-  std::memset(&p, 0, sizeof(p));
-  p.model_a = model_a; p.model_b = model_b; p.w = w; p.h = h; p.gx = gx; p.gy = gy; p.n = gx * gy;
-  for (int k = 0; k < nka; ++k) p.Ka[k] = Ka[k];
-  for (int k = 0; k < nkb; ++k) p.Kb[k] = Kb[k];
-  vc::model_precompute(model_a, p.Ka, &p.pre_a); vc::model_precompute(model_b, p.Kb, &p.pre_b);
+  vc::cmp_plan_set(&p, model_a, Ka, nka, model_b, Kb, nkb, w, h, gx, gy);
   const double I[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
   double count = 0.0, sum = 0.0, best = -1.0; long long best_i = -1;
   for (int s = 0; s < p.n; ++s) {

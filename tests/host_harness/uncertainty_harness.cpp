@@ -45,10 +45,7 @@ int vch_uncertainty(int model, const double* K, int nk, int w, int h, int gx, in
   if (!vc::unc_run_args_ok(cov, nk, sigma_px, fit_radius)) return -2;
   Lattice L;
   vc::CmpPlan& p = L.p;
-  std::memset(&p, 0, sizeof(p));
-  p.model_a = model; p.model_b = model; p.w = w; p.h = h; p.gx = gx; p.gy = gy; p.n = gx * gy;
-  for (int k = 0; k < nk; ++k) p.Ka[k] = K[k];
-  vc::model_precompute(model, p.Ka, &p.pre_a);
+  vc::cmp_plan_set(&p, model, K, nk, model, K, nk, w, h, gx, gy);      // (B is A again)
   const int n = p.n;
   L.rays.resize(3 * (size_t)n); L.qs.resize(3 * (size_t)n); L.f0.resize(n);
   for (int s = 0; s < n; ++s) {

@@ -114,6 +114,22 @@ def test_full_lattice():
     assert between <= 1e-4
 
 
+@pytest.mark.parametrize("grid,fit_radius", cc.BOUNDARY_LATTICES)
+def test_workgroup_boundary_lattices(grid, fit_radius):
+    """the shift case where a sweep or a fit fills its workgroups exactly or by one or two samples more, rings at 1, 5, 8 and 64: check 6 and
+    the same bits from a second run"""
+    q, rho = cc.lattice(cc.SIZE, grid)
+    cc.assert_thresholds_decided(rho, 0.5, cc.BOUNDARY_RING_COUNTS)
+    cc.assert_thresholds_decided(rho, fit_radius, cc.BOUNDARY_RING_COUNTS)
+    cmp = comparer(cc.case("shift"), grid=grid)
+    fit = cmp.run(fit_radius)
+    first = collect(cmp, cc.BOUNDARY_RING_COUNTS)
+    assert fit["n_fit"] == (rho <= fit_radius).sum() and fit["n_left_out"] == 0 and first["summary"]["count"] == grid[0] * grid[1]
+    cc.check_sums(rho, first)
+    cmp.run(fit_radius)
+    assert same_bits(first, collect(cmp, cc.BOUNDARY_RING_COUNTS))
+
+
 def test_for_camera_of_a_calibrator():
     """a calibrator that only had a camera added: A is that camera"""
     c = cc.case("cross")

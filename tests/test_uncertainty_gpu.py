@@ -9,6 +9,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import compare_cases as cc
 import uncertainty_cases as un
 import undistort_cases as uc
 import vicalib_amd.lib as lib
@@ -77,6 +78,22 @@ def test_exact_properties():
     # a change of the fit radius on one handle equals a fresh handle at that radius
     for radius in (1.0, 0.5, 0.0, 0.5):
         assert un.same_bits(run_on(u, c.cov, 1.0, radius), run_on(handle(c), c.cov, 1.0, radius)), radius
+
+
+@pytest.mark.parametrize("grid,fit_radius", cc.BOUNDARY_LATTICES)
+def test_workgroup_boundary_lattices(grid, fit_radius):
+    """poly3 with its dense covariance where a sweep or the Gram sweep fills its workgroups exactly or by one or two samples more, rings at
+    1, 5, 8 and 64: checks 1 and 2 and the same bits from a second run"""
+    c = un.Case("boundary", "poly3", uc.gt("poly3"), fit_radius, grid=grid)
+    ref = un.Reference(c.model, c.K, grid, fit_radius)
+    cc.assert_thresholds_decided(ref.rho, 0.5, cc.BOUNDARY_RING_COUNTS)
+    cc.assert_thresholds_decided(ref.rho, fit_radius, cc.BOUNDARY_RING_COUNTS)
+    u = handle(c)
+    first = run_on(u, c.cov, c.sigma_px, fit_radius, cc.BOUNDARY_RING_COUNTS)
+    assert first["n_fit"] == (ref.rho <= fit_radius).sum() and first["summary"]["count"] == grid[0] * grid[1]
+    un.check_map(ref, c.cov, c.sigma_px, first, "boundary %dx%d" % grid)
+    un.check_sums(ref, c.cov, c.sigma_px, first)
+    assert un.same_bits(first, run_on(u, c.cov, c.sigma_px, fit_radius, cc.BOUNDARY_RING_COUNTS))
 
 
 def test_readers_before_a_run_errors_and_timing():

@@ -7,13 +7,12 @@
 //                 workgroup's partial of Horn's H = sum over the fit set of a b^T with the size of the fit set.  It runs once per handle and
 //                 again only when a run asks for another fit radius (the fit set is part of H).
 //   k_cmp_fit     one Gauss-Newton evaluation at a rotation R: 1024 samples per 256-thread workgroup, a lane takes its four samples in index
-//                 order and keeps J^T J (6), J^T d (3), E and the two counts in registers; wave_allsum, then the four waves' sums in wave
-//                 order -> one partial record per workgroup.
+//                 order and keeps J^T J (6), J^T d (3), E and the two counts in registers.
 //   k_cmp_diff    the difference sweep at the final R, one sample per thread: d and the flags stored, the workgroup's partial of the summary
-//                 (the maximum by the xor butterfly that keeps the lower index) and of the rings.  The rings are built in LDS: every thread
-//                 leaves its ring and |d|^2 there, then thread k adds up ring k's entries in thread order.  With rings_only it reads the
-//                 stored d instead of computing it: vc_compare_rings at another ring count inverts and projects nothing.
-//   k_cmp_reduce  one wavefront: lane c adds column c of the workgroup partials in workgroup order (maxima: the first of equal ones).
+//                 and of the rings, for which every thread leaves its ring and |d|^2 in LDS.  With rings_only it reads the stored d instead
+//                 of computing it: vc_compare_rings at another ring count inverts and projects nothing.
+// The workgroup's record (lat_block_record), the rings (lat_ring_walk), the fold of the records (k_lat_reduce) and the handle's device side
+// (LatticeHandle) are the lattice core's, vc_lattice.hpp, shared with the converter and the uncertainty map.
 // No floating-point atomic anywhere; the workgroup decomposition depends on n alone: two runs, and two handles, give the same bits.
 // One host synchronisation per Gauss-Newton evaluation and one for the difference sweep.  No CPU fallback: vc_comparer_create fails with
 // VC_ERR_NO_DEVICE without a HIP device.  vc_compare_extrinsics is host code and needs none.
@@ -22,9 +21,7 @@
 #include <cstring>
 #include <vector>
 #include "../../include/vicalib_amd.h"
-#include "vc_kutil.hpp"
-#include "vc_hostutil.hpp"
-#include "vc_compare.hpp"
+#include "vc_lattice.hpp"
 
 namespace {
 
@@ -32,7 +29,7 @@ using vc::CmpPlan;
 constexpr int kFitPerWg = 1024;
 constexpr int kRayDoubles = 10;                                                       // H (9), size of the fit set
 constexpr int kDiffDoubles = vc::kCmpSumDoubles + vc::kCmpRingDoubles * vc::kCmpMaxRings;   // a workgroup's record of the difference sweep
-enum { kReduceSums = 0, kReduceDiff = 1 };
+static_assert(vc::kCmpRingDoubles == vc::kLatRingDoubles, "a ring's record is the lattice core's");
 
 struct CmpView {
   CmpPlan plan;
@@ -41,19 +38,10 @@ struct CmpView {
   unsigned char* flags;        // n: the last difference sweep's, bit 2 added
   double2* diff;               // n
   double* part;                // workgroup partials of the kernel in flight
-  double* out;                 // the reduced record
 };
 struct CmpRot { double R[9]; };
 
-// the four waves' values of `x` (the same in every lane of a wave) added in wave order; the result in every thread.  `slot` separates the
-// uses within one kernel.
-__device__ __forceinline__ void block_stage(double (*s)[16], int slot, double x) {
-  if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6][slot] = x;
-}
-__device__ __forceinline__ double block_total(double (*s)[16], int slot) { return ((s[0][slot] + s[1][slot]) + s[2][slot]) + s[3][slot]; }
-
 __global__ __launch_bounds__(256) void k_cmp_rays(CmpView v, double fit_radius) {
-  __shared__ double s_w[4][16];
   const int s = blockIdx.x * 256 + threadIdx.x;
   double H[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, nf = 0.0;
   if (s < v.plan.n) {
@@ -71,15 +59,11 @@ __global__ __launch_bounds__(256) void k_cmp_rays(CmpView v, double fit_radius) 
         for (int c = 0; c < 3; ++c) H[3 * r + c] = a[r] * b[c];
     }
   }
-#pragma unroll
-  for (int k = 0; k < 9; ++k) block_stage(s_w, k, vc::wave_allsum(H[k]));
-  block_stage(s_w, 9, vc::wave_allsum(nf));
-  __syncthreads();
-  if (threadIdx.x < kRayDoubles) v.part[(size_t)blockIdx.x * kRayDoubles + threadIdx.x] = block_total(s_w, threadIdx.x);
+  const double sums[kRayDoubles] = {H[0], H[1], H[2], H[3], H[4], H[5], H[6], H[7], H[8], nf};
+  vc::lat_block_record(v.part + (size_t)blockIdx.x * kRayDoubles, sums);
 }
 
 __global__ __launch_bounds__(256) void k_cmp_fit(CmpView v, CmpRot rot, double fit_radius) {
-  __shared__ double s_w[4][16];
   double acc[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, used = 0.0, left = 0.0;
   const int base = blockIdx.x * kFitPerWg + threadIdx.x;
   for (int it = 0; it < kFitPerWg / 256; ++it) {                  // (ascending sample index within a lane)
@@ -92,16 +76,11 @@ __global__ __launch_bounds__(256) void k_cmp_fit(CmpView v, CmpRot rot, double f
     const double a[3] = {src[0], src[1], src[2]};
     if (vc::cmp_fit_sample(v.plan, rot.R, a, qx, qy, acc)) used += 1.0; else left += 1.0;
   }
-#pragma unroll
-  for (int k = 0; k < 10; ++k) block_stage(s_w, k, vc::wave_allsum(acc[k]));
-  block_stage(s_w, 10, vc::wave_allsum(used));
-  block_stage(s_w, 11, vc::wave_allsum(left));
-  __syncthreads();
-  if (threadIdx.x < vc::kCmpFitDoubles) v.part[(size_t)blockIdx.x * vc::kCmpFitDoubles + threadIdx.x] = block_total(s_w, threadIdx.x);
+  const double sums[vc::kCmpFitDoubles] = {acc[0], acc[1], acc[2], acc[3], acc[4], acc[5], acc[6], acc[7], acc[8], acc[9], used, left};
+  vc::lat_block_record(v.part + (size_t)blockIdx.x * vc::kCmpFitDoubles, sums);
 }
 
 __global__ __launch_bounds__(256) void k_cmp_diff(CmpView v, CmpRot rot, int n_rings, int rings_only) {
-  __shared__ double s_w[4][16];
   __shared__ double s_sq[256];          // |d|^2 of a valid sample, -1 of an invalid one
   __shared__ int s_ring[256];           // -1: no sample
   const int s = blockIdx.x * 256 + threadIdx.x;
@@ -134,71 +113,18 @@ __global__ __launch_bounds__(256) void k_cmp_diff(CmpView v, CmpRot rot, int n_r
   const double sq = vc::cmp_norm2(du, dv);
   s_sq[threadIdx.x] = valid ? sq : -1.0;
   s_ring[threadIdx.x] = ring;
-  // ---- the summary: sums by the butterfly; the maximum keeps the lower sample on ties
-  const double cnt = vc::wave_allsum(valid ? 1.0 : 0.0), inv = vc::wave_allsum(in && !valid ? 1.0 : 0.0);
-  const double s_du = vc::wave_allsum(du), s_dv = vc::wave_allsum(dv), s_q = vc::wave_allsum(sq);
-  double best = valid ? sq : -1.0;
-  int best_i = valid ? s : -1;
-  vc::wave_argmax_low(&best, &best_i);
-  block_stage(s_w, 0, cnt); block_stage(s_w, 1, inv); block_stage(s_w, 2, s_du); block_stage(s_w, 3, s_dv); block_stage(s_w, 4, s_q);
-  block_stage(s_w, 5, best); block_stage(s_w, 6, (double)best_i);
-  __syncthreads();
+  // the summary (count, invalid, sum du, sum dv, sum |d|^2, the largest |d|^2 and its sample), then the rings: |d|^2 is summed and is the key
   double* rec = v.part + (size_t)blockIdx.x * kDiffDoubles;
-  if (threadIdx.x < 5) rec[threadIdx.x] = block_total(s_w, threadIdx.x);
-  if (threadIdx.x == 5) {                                          // waves hold ascending samples: a later wave wins only when larger
-    double b = s_w[0][5], bi = s_w[0][6];
-#pragma unroll
-    for (int w = 1; w < 4; ++w) if (s_w[w][5] > b) { b = s_w[w][5]; bi = s_w[w][6]; }
-    rec[5] = b; rec[6] = bi;
-  }
-  // ---- the rings: thread k owns ring k and walks the workgroup's entries in thread order
-  if ((int)threadIdx.x < n_rings) {
-    double rc = 0.0, ri = 0.0, rs = 0.0, rm = -1.0;
-    for (int j = 0; j < 256; ++j) {
-      if (s_ring[j] != (int)threadIdx.x) continue;
-      const double q = s_sq[j];
-      if (q >= 0.0) { rc += 1.0; rs += q; rm = q > rm ? q : rm; } else ri += 1.0;
-    }
-    double* r = rec + vc::kCmpSumDoubles + vc::kCmpRingDoubles * threadIdx.x;
-    r[0] = rc; r[1] = ri; r[2] = rs; r[3] = rm;
-  }
-}
-
-// columns of n_wg records of `stride` doubles added in workgroup order.  kReduceDiff: column 5 is a maximum that carries column 6 (its sample;
-// strictly larger wins: workgroups hold ascending samples), every fourth ring column is a maximum.
-__global__ __launch_bounds__(64) void k_cmp_reduce(const double* __restrict__ part, int n_wg, int stride, int m, int kind, double* __restrict__ out) {
-  for (int c = threadIdx.x; c < m; c += 64) {
-    const bool is_worst = kind == kReduceDiff && c == 5, is_idx = kind == kReduceDiff && c == 6;
-    const bool is_max = kind == kReduceDiff && c >= vc::kCmpSumDoubles && ((c - vc::kCmpSumDoubles) & 3) == 3;
-    if (is_idx) continue;                                          // (written with column 5)
-    if (is_worst) {
-      double b = -1.0, bi = -1.0;
-      for (int g = 0; g < n_wg; ++g) {
-        const double x = part[(size_t)g * stride + 5];
-        if (x > b) { b = x; bi = part[(size_t)g * stride + 6]; }
-      }
-      out[5] = b; out[6] = bi;
-    } else if (is_max) {
-      double b = -1.0;
-      for (int g = 0; g < n_wg; ++g) { const double x = part[(size_t)g * stride + c]; b = x > b ? x : b; }
-      out[c] = b;
-    } else {
-      double t = 0.0;
-      for (int g = 0; g < n_wg; ++g) t += part[(size_t)g * stride + c];
-      out[c] = t;
-    }
-  }
+  const double sums[5] = {valid ? 1.0 : 0.0, in && !valid ? 1.0 : 0.0, du, dv, sq};
+  vc::lat_block_record<5, true>(rec, sums, valid ? sq : -1.0, valid ? s : -1);
+  vc::lat_ring_walk(rec + vc::kCmpSumDoubles, n_rings, s_ring, s_sq, s_sq);
 }
 
 }  // namespace
 
-struct vc_comparer {
-  int device = 0;
+struct vc_comparer : vc::LatticeHandle {      // d_buf: [rays | diff | flags0 | flags | part]
   CmpView v;
-  hipStream_t stream = nullptr;
-  unsigned char* d_buf = nullptr;      // [rays | diff | flags0 | flags | part | out]
-  double* h_res = nullptr;             // pinned: the reduced record of the sweep in flight
-  bool have_rays = false, have_run = false, in_flight = false;
+  bool have_rays = false, have_run = false;
   double rays_radius = 0.0;            // the fit radius H was summed for
   double H[9];
   long long n_fit = 0;
@@ -215,28 +141,18 @@ namespace {
 
 void launch_rays(vc_comparer* c, double radius) {
   hipLaunchKernelGGL(k_cmp_rays, dim3(c->n_wg()), dim3(256), 0, c->stream, c->v, radius);
-  hipLaunchKernelGGL(k_cmp_reduce, dim3(1), dim3(64), 0, c->stream, c->v.part, c->n_wg(), kRayDoubles, kRayDoubles, (int)kReduceSums, c->v.out);
+  c->reduce(c->v.part, c->n_wg(), kRayDoubles, kRayDoubles);
 }
 void launch_fit(vc_comparer* c, const double* R, double radius) {
   CmpRot rot; std::memcpy(rot.R, R, 72);
   hipLaunchKernelGGL(k_cmp_fit, dim3(c->n_wg_fit()), dim3(256), 0, c->stream, c->v, rot, radius);
-  hipLaunchKernelGGL(k_cmp_reduce, dim3(1), dim3(64), 0, c->stream, c->v.part, c->n_wg_fit(), (int)vc::kCmpFitDoubles, (int)vc::kCmpFitDoubles, (int)kReduceSums, c->v.out);
+  c->reduce(c->v.part, c->n_wg_fit(), vc::kCmpFitDoubles, vc::kCmpFitDoubles);
 }
 void launch_diff(vc_comparer* c, const double* R, int n_rings, int rings_only) {
   CmpRot rot; std::memcpy(rot.R, R, 72);
   hipLaunchKernelGGL(k_cmp_diff, dim3(c->n_wg()), dim3(256), 0, c->stream, c->v, rot, n_rings, rings_only);
-  hipLaunchKernelGGL(k_cmp_reduce, dim3(1), dim3(64), 0, c->stream, c->v.part, c->n_wg(), kDiffDoubles, vc::kCmpSumDoubles + vc::kCmpRingDoubles * n_rings,
-                     (int)kReduceDiff, c->v.out);
+  c->reduce(c->v.part, c->n_wg(), kDiffDoubles, vc::kCmpSumDoubles + vc::kCmpRingDoubles * n_rings, vc::kCmpSumDoubles - 2, vc::kCmpSumDoubles);
 }
-// the reduced record of what was just enqueued, in h_res: the one synchronisation of a sweep
-bool fetch(vc_comparer* c, int m) {
-  c->in_flight = true;
-  if (hipGetLastError() != hipSuccess || hipMemcpyAsync(c->h_res, c->v.out, (size_t)m * 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-      hipStreamSynchronize(c->stream) != hipSuccess) return false;
-  c->in_flight = false;
-  return true;
-}
-bool grid_ok(int w, int h, int gx, int gy) { return gx >= 2 && gy >= 2 && gx <= w && gy <= h && (long long)gx * gy <= vc::kCmpMaxSamples; }
 
 }  // namespace
 
@@ -245,38 +161,27 @@ extern "C" {
 int vc_comparer_create(int device, int model_a, const double* params_a, int nparams_a, int model_b, const double* params_b, int nparams_b, int width, int height,
                        int grid_x, int grid_y, vc_comparer** out) {
   if (!out || !vc::undist_source_args_ok(model_a, params_a, nparams_a, width, height) || !vc::undist_source_args_ok(model_b, params_b, nparams_b, width, height) ||
-      !grid_ok(width, height, grid_x, grid_y)) return VC_ERR_BAD_ARG;
-  if (vch::open_device(device) != VC_OK) return VC_ERR_NO_DEVICE;
+      !vc::cvt_grid_ok(width, height, grid_x, grid_y)) return VC_ERR_BAD_ARG;
   vc_comparer* c = new vc_comparer;
-  c->device = device;
   std::memset(&c->v, 0, sizeof(c->v)); std::memset(&c->fit, 0, sizeof(c->fit));
-  CmpPlan& p = c->v.plan;
-  p.model_a = model_a; p.model_b = model_b; p.w = width; p.h = height; p.gx = grid_x; p.gy = grid_y; p.n = grid_x * grid_y;
-  for (int k = 0; k < nparams_a; ++k) p.Ka[k] = params_a[k];
-  for (int k = 0; k < nparams_b; ++k) p.Kb[k] = params_b[k];
-  vc::model_precompute(model_a, p.Ka, &p.pre_a); vc::model_precompute(model_b, p.Kb, &p.pre_b);
+  vc::cmp_plan_set(&c->v.plan, model_a, params_a, nparams_a, model_b, params_b, nparams_b, width, height, grid_x, grid_y);
   auto carve = [&](vch::Carver q) {
-    const size_t n = (size_t)p.n;
+    const size_t n = (size_t)c->v.plan.n;
     c->v.rays = q.take<double>(n * 3);
     c->v.diff = q.take<double2>(n);
     c->v.flags0 = q.take<unsigned char>(n);
     c->v.flags = q.take<unsigned char>(n);
     c->v.part = q.take<double>((size_t)c->n_wg() * kDiffDoubles);
-    c->v.out = q.take<double>(kDiffDoubles);
     return q.bytes();
   };
-  if (hipStreamCreate(&c->stream) != hipSuccess || hipMalloc((void**)&c->d_buf, carve(vch::Carver())) != hipSuccess ||
-      hipHostMalloc((void**)&c->h_res, kDiffDoubles * 8, hipHostMallocDefault) != hipSuccess) { vc_comparer_destroy(c); return VC_ERR_NO_DEVICE; }
+  if (!c->open(device, carve(vch::Carver()), kDiffDoubles)) { delete c; return VC_ERR_NO_DEVICE; }
   carve(vch::Carver(c->d_buf));
   *out = c;
   return VC_OK;
 }
 void vc_comparer_destroy(vc_comparer* c) {
   if (!c) return;
-  (void)hipSetDevice(c->device);
-  if (c->stream) { (void)hipStreamSynchronize(c->stream); (void)hipStreamDestroy(c->stream); }
-  (void)hipFree(c->d_buf);
-  if (c->h_res) (void)hipHostFree(c->h_res);
+  c->close();
   delete c;
 }
 
@@ -288,14 +193,13 @@ int vc_compare_run(vc_comparer* c, double fit_radius, int max_iters, const doubl
     if (!vc::is_rotation(R_ba)) return VC_ERR_BAD_ARG;
     std::memcpy(R0, R_ba, 72);
   }
-  if (hipSetDevice(c->device) != hipSuccess) return VC_ERR_NO_DEVICE;
-  if (c->in_flight) { (void)hipStreamSynchronize(c->stream); c->in_flight = false; }
+  if (!c->settle()) return VC_ERR_NO_DEVICE;
   c->have_run = false; c->rings_n = 0;
   if (!c->have_rays || (fitting && fit_radius != c->rays_radius)) {
     c->have_rays = false;
     const double radius = fitting ? fit_radius : 0.0;
     launch_rays(c, radius);
-    if (!fetch(c, kRayDoubles)) return VC_ERR_NO_DEVICE;
+    if (!c->fetch(kRayDoubles)) return VC_ERR_NO_DEVICE;
     std::memcpy(c->H, c->h_res, 72);
     c->n_fit = (long long)c->h_res[9];
     c->rays_radius = radius; c->have_rays = true;
@@ -307,7 +211,7 @@ int vc_compare_run(vc_comparer* c, double fit_radius, int max_iters, const doubl
     vc::rigid_rotation(c->H, R0);
     const int rc = vc::cmp_gauss_newton([&](const double* R, double* sums) -> int {
       launch_fit(c, R, fit_radius);
-      if (!fetch(c, vc::kCmpFitDoubles)) return (int)VC_ERR_NO_DEVICE;
+      if (!c->fetch(vc::kCmpFitDoubles)) return (int)VC_ERR_NO_DEVICE;
       std::memcpy(sums, c->h_res, vc::kCmpFitDoubles * 8);
       return 0;
     }, R0, max_iters, &f);
@@ -318,7 +222,7 @@ int vc_compare_run(vc_comparer* c, double fit_radius, int max_iters, const doubl
     std::memcpy(f.R, R0, 72);
   }
   launch_diff(c, f.R, vc::kCmpDefaultRings, 0);
-  if (!fetch(c, vc::kCmpSumDoubles + vc::kCmpRingDoubles * vc::kCmpDefaultRings)) return VC_ERR_NO_DEVICE;
+  if (!c->fetch(vc::kCmpSumDoubles + vc::kCmpRingDoubles * vc::kCmpDefaultRings)) return VC_ERR_NO_DEVICE;
   std::memcpy(c->summary, c->h_res, (vc::kCmpSumDoubles + vc::kCmpRingDoubles * vc::kCmpDefaultRings) * 8);
   c->fit_radius = fit_radius;
   c->have_run = true;
@@ -369,7 +273,7 @@ int vc_compare_rings(vc_comparer* c, int n_rings, long long* count, long long* i
       if (hipSetDevice(c->device) != hipSuccess) return VC_ERR_NO_DEVICE;
       c->rings_n = 0;
       launch_diff(c, c->fit.R, n_rings, 1);
-      if (!fetch(c, vc::kCmpSumDoubles + vc::kCmpRingDoubles * n_rings)) return VC_ERR_NO_DEVICE;
+      if (!c->fetch(vc::kCmpSumDoubles + vc::kCmpRingDoubles * n_rings)) return VC_ERR_NO_DEVICE;
       std::memcpy(c->rings, c->h_res + vc::kCmpSumDoubles, (size_t)vc::kCmpRingDoubles * n_rings * 8);
       c->rings_n = n_rings;
     }
@@ -399,8 +303,7 @@ int vc_compare_extrinsics(const double T_ck_a0[7], const double T_ck_ac[7], cons
 
 int vc_time_compare(vc_comparer* c, int reps, double out_ms[3]) {
   if (!c || reps < 1 || !out_ms || !c->have_run) return VC_ERR_BAD_ARG;
-  if (hipSetDevice(c->device) != hipSuccess) return VC_ERR_NO_DEVICE;
-  if (c->in_flight) { (void)hipStreamSynchronize(c->stream); c->in_flight = false; }
+  if (!c->settle()) return VC_ERR_NO_DEVICE;
   for (int what = 0; what < 3; ++what) {
     auto launch = [&]() {                                          // (each rewrites what the last run left: the same rays, the same map)
       if (what == 0) launch_rays(c, c->rays_radius);

@@ -26,6 +26,16 @@ struct CmpPlan {
   double Ka[10], Kb[10];
   ModelPre pre_a, pre_b;
 };
+// the one check of a lattice over a w x h image
+inline bool cvt_grid_ok(int w, int h, int gx, int gy) { return gx >= 2 && gy >= 2 && gx <= w && gy <= h && (long long)gx * gy <= kCmpMaxSamples; }
+// the plan of cameras A and B on a gx x gy lattice over their w x h image (a tool with one camera gives it as B too)
+inline void cmp_plan_set(CmpPlan* p, int model_a, const double* Ka, int nka, int model_b, const double* Kb, int nkb, int w, int h, int gx, int gy) {
+  *p = CmpPlan{};
+  p->model_a = model_a; p->model_b = model_b; p->w = w; p->h = h; p->gx = gx; p->gy = gy; p->n = gx * gy;
+  for (int k = 0; k < nka; ++k) p->Ka[k] = Ka[k];
+  for (int k = 0; k < nkb; ++k) p->Kb[k] = Kb[k];
+  model_precompute(model_a, p->Ka, &p->pre_a); model_precompute(model_b, p->Kb, &p->pre_b);
+}
 
 // x * x + y * y with both products rounded (no fused multiply-add): the same bits on the device, on the host and in numpy, so that a
 // maximum over |d|^2 can be compared exactly

@@ -8,12 +8,11 @@
 //                      run asks for another fit radius.
 //   k_cvt_fit<MODEL>   one linearisation at K_b: 1024 samples per 256-thread workgroup, a lane takes its four samples in index order and keeps
 //                      J^T J packed (nk (nk + 1) / 2), J^T d (nk), E and the two counts in registers -- nk and every index are compile-time
-//                      constants of the instantiation --; wave_allsum, then the four waves' sums in wave order through LDS -> one partial record
-//                      per workgroup.  One instantiation per target model, chosen at the launch through with_model.
+//                      constants of the instantiation.  One instantiation per target model, chosen at the launch through with_model.
 //   k_cvt_cost         the values-only sweep, one sample per thread in the shape of k_cmp_diff and through the comparer's cmp_diff_sample at the
 //                      identity rotation: E, the counts, and the largest |d|^2 (cmp_norm2) with its sample, the lowest sample on ties.
-//   k_cvt_reduce       one wavefront: lane c adds column c of the workgroup partials in workgroup order; the cost sweep's maximum keeps the
-//                      lower sample of equal ones.
+// The workgroup's record (lat_block_record), the fold of the records (k_lat_reduce) and the handle's device side (LatticeHandle) are the
+// lattice core's, vc_lattice.hpp, shared with the comparer and the uncertainty map.
 // No floating-point atomic anywhere; the workgroup decomposition depends on n alone: two runs, and two handles, give the same bits.
 // One host synchronisation per evaluation of the Levenberg-Marquardt loop and one for each of the two cost sweeps of the readout.  No CPU fallback:
 // vc_converter_create fails with VC_ERR_NO_DEVICE without a HIP device.
@@ -21,8 +20,7 @@
 #include <cmath>
 #include <cstring>
 #include "../../include/vicalib_amd.h"
-#include "vc_kutil.hpp"
-#include "vc_hostutil.hpp"
+#include "vc_lattice.hpp"
 #include "vc_convert.hpp"
 
 namespace {
@@ -30,20 +28,17 @@ namespace {
 using vc::CmpPlan;
 using vc::CvtCam;
 constexpr int kPerWg = 1024;                   // samples of a workgroup of the fit and cost sweeps
-enum { kReduceSums = 0, kReduceCost = 1 };
 
 struct CvtView {
   CmpPlan plan;                // A, the lattice, the target's model; Kb and pre_b are set per sweep from a CvtCam
   double* rays;                // n x 3: a
   unsigned char* flags;        // n
   double* part;                // workgroup partials of the kernel in flight
-  double* out;                 // the reduced record
 };
 
 __global__ __launch_bounds__(256) void k_cvt_rays(CvtView v, double fit_radius) {
-  __shared__ double s_w[4];
   const int s = blockIdx.x * 256 + threadIdx.x;
-  double nf = 0.0;
+  double nf[1] = {0.0};
   if (s < v.plan.n) {
     double qx, qy, rho, a[3];
     vc::cmp_sample(v.plan, s, &qx, &qy, &rho);
@@ -54,18 +49,14 @@ __global__ __launch_bounds__(256) void k_cvt_rays(CvtView v, double fit_radius) 
     double* dst = v.rays + 3 * (size_t)s;
     dst[0] = a[0]; dst[1] = a[1]; dst[2] = a[2];
     v.flags[s] = (unsigned char)fl;
-    if (fl == 0) nf = 1.0;
+    if (fl == 0) nf[0] = 1.0;
   }
-  nf = vc::wave_allsum(nf);
-  if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = nf;
-  __syncthreads();
-  if (threadIdx.x == 0) v.part[blockIdx.x] = ((s_w[0] + s_w[1]) + s_w[2]) + s_w[3];
+  vc::lat_block_record(v.part + blockIdx.x, nf);
 }
 
 template <int MODEL>
 __global__ __launch_bounds__(256) void k_cvt_fit(CvtView v, CvtCam cam) {
   constexpr int NS = vc::cvt_nsums(vc::cvt_nk(MODEL));
-  __shared__ double s_w[4][NS];
   double acc[NS - 2], used = 0.0, left = 0.0;
 #pragma unroll
   for (int k = 0; k < NS - 2; ++k) acc[k] = 0.0;
@@ -80,22 +71,16 @@ __global__ __launch_bounds__(256) void k_cvt_fit(CvtView v, CvtCam cam) {
     const double a[3] = {src[0], src[1], src[2]};
     if (vc::cvt_fit_sample<MODEL>(cam, a, qx, qy, acc)) used += 1.0; else left += 1.0;
   }
-  const int wave = threadIdx.x >> 6;
-  const bool first = (threadIdx.x & 63) == 0;
+  double sums[NS];
 #pragma unroll
-  for (int k = 0; k < NS; ++k) {
-    const double t = vc::wave_allsum(k < NS - 2 ? acc[k] : k == NS - 2 ? used : left);
-    if (first) s_w[wave][k] = t;
-  }
-  __syncthreads();
-  if (threadIdx.x < NS) v.part[(size_t)blockIdx.x * NS + threadIdx.x] = ((s_w[0][threadIdx.x] + s_w[1][threadIdx.x]) + s_w[2][threadIdx.x]) + s_w[3][threadIdx.x];
+  for (int k = 0; k < NS; ++k) sums[k] = k < NS - 2 ? acc[k] : k == NS - 2 ? used : left;
+  vc::lat_block_record(v.part + (size_t)blockIdx.x * NS, sums);
 }
 
 // (the shape of k_cmp_diff: one sample per thread, the target in the plan of the kernel argument, the rotation a kernel argument too, d through
 //  cmp_diff_sample -- the closest this sweep can come to the code the compiler makes of the comparer's, whose d it is meant to reproduce)
 struct CvtRot { double R[9]; };
 __global__ __launch_bounds__(256) void k_cvt_cost(CvtView v, CvtRot rot) {
-  __shared__ double s_w[4][vc::kCvtCostDoubles];
   const int s = blockIdx.x * 256 + threadIdx.x;
   bool in = s < v.plan.n && v.flags[s] == 0, valid = false;
   double d[2] = {0.0, 0.0};
@@ -108,54 +93,15 @@ __global__ __launch_bounds__(256) void k_cvt_cost(CvtView v, CvtRot rot) {
   }
   if (!valid) { d[0] = 0.0; d[1] = 0.0; }
   const double sq = vc::cmp_norm2(d[0], d[1]);
-  const double e = vc::wave_allsum(sq), used = vc::wave_allsum(valid ? 1.0 : 0.0), left = vc::wave_allsum(in && !valid ? 1.0 : 0.0);
-  double best = valid ? sq : -1.0;
-  int best_i = valid ? s : -1;
-  vc::wave_argmax_low(&best, &best_i);
-  if ((threadIdx.x & 63) == 0) {
-    double* w = s_w[threadIdx.x >> 6];
-    w[0] = e; w[1] = used; w[2] = left; w[3] = best; w[4] = (double)best_i;
-  }
-  __syncthreads();
-  double* rec = v.part + (size_t)blockIdx.x * vc::kCvtCostDoubles;
-  if (threadIdx.x < 3) rec[threadIdx.x] = ((s_w[0][threadIdx.x] + s_w[1][threadIdx.x]) + s_w[2][threadIdx.x]) + s_w[3][threadIdx.x];
-  if (threadIdx.x == 3) {                                          // waves hold ascending samples: a later wave wins only when larger
-    double b = s_w[0][3], bi = s_w[0][4];
-#pragma unroll
-    for (int w = 1; w < 4; ++w) if (s_w[w][3] > b) { b = s_w[w][3]; bi = s_w[w][4]; }
-    rec[3] = b; rec[4] = bi;
-  }
-}
-
-// columns of n_wg records of m doubles added in workgroup order.  kReduceCost: column 3 is a maximum that carries column 4 (its sample;
-// strictly larger wins: workgroups hold ascending samples).
-__global__ __launch_bounds__(64) void k_cvt_reduce(const double* __restrict__ part, int n_wg, int m, int kind, double* __restrict__ out) {
-  for (int c = threadIdx.x; c < m; c += 64) {
-    if (kind == kReduceCost && c == 4) continue;                   // (written with column 3)
-    if (kind == kReduceCost && c == 3) {
-      double b = -1.0, bi = -1.0;
-      for (int g = 0; g < n_wg; ++g) {
-        const double x = part[(size_t)g * m + 3];
-        if (x > b) { b = x; bi = part[(size_t)g * m + 4]; }
-      }
-      out[3] = b; out[4] = bi;
-    } else {
-      double t = 0.0;
-      for (int g = 0; g < n_wg; ++g) t += part[(size_t)g * m + c];
-      out[c] = t;
-    }
-  }
+  const double sums[3] = {sq, valid ? 1.0 : 0.0, in && !valid ? 1.0 : 0.0};                // E, used, left out
+  vc::lat_block_record<3, true>(v.part + (size_t)blockIdx.x * vc::kCvtCostDoubles, sums, valid ? sq : -1.0, valid ? s : -1);
 }
 
 }  // namespace
 
-struct vc_converter {
-  int device = 0;
+struct vc_converter : vc::LatticeHandle {     // d_buf: [rays | flags | part]
   CvtView v;
-  hipStream_t stream = nullptr;
-  unsigned char* d_buf = nullptr;      // [rays | flags | part | out]
-  double* h_res = nullptr;             // pinned: the reduced record of the sweep in flight
-  bool have_rays = false, have_run = false, in_flight = false;
+  bool have_rays = false, have_run = false;
   double rays_radius = 0.0;            // the fit radius the flags were set for
   long long n_fit = 0;
   vc::CvtFit fit;                      // the last run's
@@ -171,28 +117,21 @@ namespace {
 
 void launch_rays(vc_converter* c, double radius) {
   hipLaunchKernelGGL(k_cvt_rays, dim3(c->n_wg_rays()), dim3(256), 0, c->stream, c->v, radius);
-  hipLaunchKernelGGL(k_cvt_reduce, dim3(1), dim3(64), 0, c->stream, c->v.part, c->n_wg_rays(), 1, (int)kReduceSums, c->v.out);
+  c->reduce(c->v.part, c->n_wg_rays(), 1, 1);
 }
 void launch_fit(vc_converter* c, const CvtCam& cam) {
   vc::with_model(c->v.plan.model_b, [&](auto m) {
     hipLaunchKernelGGL(k_cvt_fit<decltype(m)::value>, dim3(c->n_wg()), dim3(256), 0, c->stream, c->v, cam);
   });
-  hipLaunchKernelGGL(k_cvt_reduce, dim3(1), dim3(64), 0, c->stream, c->v.part, c->n_wg(), vc::cvt_nsums(c->nk()), (int)kReduceSums, c->v.out);
+  const int ns = vc::cvt_nsums(c->nk());
+  c->reduce(c->v.part, c->n_wg(), ns, ns);
 }
 void launch_cost(vc_converter* c, const CvtCam& cam) {
   CvtView v = c->v;                                                // the target at this point of the fit goes into the plan, where the comparer has its B
   std::memcpy(v.plan.Kb, cam.K, sizeof(cam.K)); v.plan.pre_b = cam.pre;
   const CvtRot rot = {{1, 0, 0, 0, 1, 0, 0, 0, 1}};
   hipLaunchKernelGGL(k_cvt_cost, dim3(c->n_wg_rays()), dim3(256), 0, c->stream, v, rot);
-  hipLaunchKernelGGL(k_cvt_reduce, dim3(1), dim3(64), 0, c->stream, c->v.part, c->n_wg_rays(), (int)vc::kCvtCostDoubles, (int)kReduceCost, c->v.out);
-}
-// the reduced record of what was just enqueued, in h_res: the one synchronisation of a sweep
-bool fetch(vc_converter* c, int m) {
-  c->in_flight = true;
-  if (hipGetLastError() != hipSuccess || hipMemcpyAsync(c->h_res, c->v.out, (size_t)m * 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-      hipStreamSynchronize(c->stream) != hipSuccess) return false;
-  c->in_flight = false;
-  return true;
+  c->reduce(c->v.part, c->n_wg_rays(), vc::kCvtCostDoubles, vc::kCvtCostDoubles, vc::kCvtCostDoubles - 2);
 }
 
 }  // namespace
@@ -202,50 +141,39 @@ extern "C" {
 int vc_converter_create(int device, int model_a, const double* params_a, int nparams_a, int width, int height, int model_b, int grid_x, int grid_y, vc_converter** out) {
   if (!out || !vc::undist_source_args_ok(model_a, params_a, nparams_a, width, height) || !vc::cvt_model_ok(model_b) ||
       !vc::cvt_grid_ok(width, height, grid_x, grid_y)) return VC_ERR_BAD_ARG;
-  if (vch::open_device(device) != VC_OK) return VC_ERR_NO_DEVICE;
   vc_converter* c = new vc_converter;
-  c->device = device;
   std::memset(&c->v, 0, sizeof(c->v)); std::memset(&c->fit, 0, sizeof(c->fit));
-  CmpPlan& p = c->v.plan;
-  p.model_a = model_a; p.model_b = model_b; p.w = width; p.h = height; p.gx = grid_x; p.gy = grid_y; p.n = grid_x * grid_y;
   c->nk_a = nparams_a;
-  for (int k = 0; k < nparams_a; ++k) p.Ka[k] = params_a[k];
-  vc::model_precompute(model_a, p.Ka, &p.pre_a);
-  vc::cvt_default_start(model_b, p.Ka, p.Kb);                      // (the B of the plan outside a cost sweep: what k_cvt_rays' unused half inverts)
-  vc::model_precompute(model_b, p.Kb, &p.pre_b);
+  double K0[10];
+  vc::cvt_default_start(model_b, params_a, K0);                    // (the B of the plan outside a cost sweep: what k_cvt_rays' unused half inverts)
+  vc::cmp_plan_set(&c->v.plan, model_a, params_a, nparams_a, model_b, K0, 10, width, height, grid_x, grid_y);
   auto carve = [&](vch::Carver q) {
-    const size_t n = (size_t)p.n;
+    const size_t n = (size_t)c->v.plan.n;
     c->v.rays = q.take<double>(n * 3);
     c->v.flags = q.take<unsigned char>(n);
     const size_t fit_part = (size_t)c->n_wg() * vc::kCvtMaxSums, ray_part = (size_t)c->n_wg_rays() * vc::kCvtCostDoubles;      // (rays: 1 per workgroup, cost: 5)
     c->v.part = q.take<double>(fit_part > ray_part ? fit_part : ray_part);
-    c->v.out = q.take<double>(vc::kCvtMaxSums);
     return q.bytes();
   };
-  if (hipStreamCreate(&c->stream) != hipSuccess || hipMalloc((void**)&c->d_buf, carve(vch::Carver())) != hipSuccess ||
-      hipHostMalloc((void**)&c->h_res, vc::kCvtMaxSums * 8, hipHostMallocDefault) != hipSuccess) { vc_converter_destroy(c); return VC_ERR_NO_DEVICE; }
+  if (!c->open(device, carve(vch::Carver()), vc::kCvtMaxSums)) { delete c; return VC_ERR_NO_DEVICE; }
   carve(vch::Carver(c->d_buf));
   *out = c;
   return VC_OK;
 }
 void vc_converter_destroy(vc_converter* c) {
   if (!c) return;
-  (void)hipSetDevice(c->device);
-  if (c->stream) { (void)hipStreamSynchronize(c->stream); (void)hipStreamDestroy(c->stream); }
-  (void)hipFree(c->d_buf);
-  if (c->h_res) (void)hipHostFree(c->h_res);
+  c->close();
   delete c;
 }
 
 int vc_convert_run(vc_converter* c, double fit_radius, int max_iters, const double* start, unsigned free_mask) {
   if (!c || !vc::cvt_run_args_ok(c->v.plan.model_b, fit_radius, start, free_mask)) return VC_ERR_BAD_ARG;
-  if (hipSetDevice(c->device) != hipSuccess) return VC_ERR_NO_DEVICE;
-  if (c->in_flight) { (void)hipStreamSynchronize(c->stream); c->in_flight = false; }
+  if (!c->settle()) return VC_ERR_NO_DEVICE;
   c->have_run = false;
   if (!c->have_rays || fit_radius != c->rays_radius) {
     c->have_rays = false;
     launch_rays(c, fit_radius);
-    if (!fetch(c, 1)) return VC_ERR_NO_DEVICE;
+    if (!c->fetch(1)) return VC_ERR_NO_DEVICE;
     c->n_fit = (long long)c->h_res[0];
     c->rays_radius = fit_radius; c->have_rays = true;
   }
@@ -257,7 +185,7 @@ int vc_convert_run(vc_converter* c, double fit_radius, int max_iters, const doub
     CvtCam cam;
     vc::cvt_cam(model_b, K, &cam);
     launch_fit(c, cam);
-    if (!fetch(c, vc::cvt_nsums(nk))) return (int)VC_ERR_NO_DEVICE;
+    if (!c->fetch(vc::cvt_nsums(nk))) return (int)VC_ERR_NO_DEVICE;
     std::memcpy(sums, c->h_res, (size_t)vc::cvt_nsums(nk) * 8);
     return 0;
   }, nk, K0, free_mask, max_iters, c->n_fit, &c->fit);
@@ -271,7 +199,7 @@ int vc_convert_run(vc_converter* c, double fit_radius, int max_iters, const doub
     CvtCam cam;
     vc::cvt_cam(model_b, end ? c->fit.K : K0, &cam);
     launch_cost(c, cam);
-    if (!fetch(c, vc::kCvtCostDoubles)) return VC_ERR_NO_DEVICE;
+    if (!c->fetch(vc::kCvtCostDoubles)) return VC_ERR_NO_DEVICE;
     (end ? c->fit.cost : c->fit.cost0) = 0.5 * c->h_res[0];
     c->left_out = (long long)c->h_res[2];
     c->max_sq = c->h_res[3]; c->worst = (long long)c->h_res[4];
@@ -305,8 +233,7 @@ int vc_convert_comparer(vc_converter* c, vc_comparer** out) {
 
 int vc_time_convert(vc_converter* c, int reps, double out_ms[3]) {
   if (!c || reps < 1 || !out_ms || !c->have_run) return VC_ERR_BAD_ARG;
-  if (hipSetDevice(c->device) != hipSuccess) return VC_ERR_NO_DEVICE;
-  if (c->in_flight) { (void)hipStreamSynchronize(c->stream); c->in_flight = false; }
+  if (!c->settle()) return VC_ERR_NO_DEVICE;
   CvtCam cam;
   vc::cvt_cam(c->v.plan.model_b, c->fit.K, &cam);
   for (int what = 0; what < 3; ++what) {

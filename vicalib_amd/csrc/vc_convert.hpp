@@ -87,7 +87,6 @@ VC_HD bool cvt_cost_sample(const CmpPlan& p, const double* a, double qx, double 
 
 // ---- host side --------------------------------------------------------------------------------------------------------------------
 inline bool cvt_model_ok(int m) { return m >= 0 && m <= kRational6; }
-inline bool cvt_grid_ok(int w, int h, int gx, int gy) { return gx >= 2 && gy >= 2 && gx <= w && gy <= h && (long long)gx * gy <= kCmpMaxSamples; }
 // the arguments of a run: a radius above 0, a finite start (or none), no mask bit at or above nk
 inline bool cvt_run_args_ok(int model_b, double fit_radius, const double* start, unsigned free_mask) {
   const int nk = model_nk(model_b);

@@ -7,13 +7,13 @@
 //                       bit), the unit ray and the inversion flag stored.  Once per handle.
 //   k_unc_gram<MODEL>   the sums of the implied rotation per parameter: 1024 samples per 256-thread workgroup, a lane takes its four samples
 //                       in index order and keeps G (6 packed), C (3 nk) and the size of the fit set in registers -- nk and every index are
-//                       compile-time constants of the instantiation --; wave_allsum, then the four waves' sums in wave order through LDS ->
-//                       one partial record per workgroup.  Again only when a run asks for another fit radius.
+//                       compile-time constants of the instantiation.  Again only when a run asks for another fit radius.
 //   k_unc_map<MODEL>    one sample per thread, M (3 x nk) and the packed, pre-scaled covariance as kernel arguments: Sigma = J Cov J^T with
 //                       J = B + Jw M, the triple (s_uu, s_uv, s_vv) and the flags stored, then the workgroup's partial of the summary and of
 //                       the rings (unc_block_sums).
 //   k_unc_rings         the same partials at another ring count from the stored triples: no inversion, no projection.
-//   k_unc_reduce        one wavefront: lane c adds column c of the workgroup partials in workgroup order (maxima: the first of equal ones).
+// The workgroup's record (lat_block_record), the rings (lat_ring_walk), the fold of the records (k_lat_reduce) and the handle's device side
+// (LatticeHandle) are the lattice core's, vc_lattice.hpp, shared with the comparer and the converter.
 // One instantiation per model, chosen at the launch through with_model.  No floating-point atomic anywhere; the workgroup decomposition
 // depends on n alone: two runs, and two handles, give the same bits.  One host synchronisation per sweep.  No CPU fallback:
 // vc_uncertainty_create fails with VC_ERR_NO_DEVICE without a HIP device.
@@ -22,8 +22,7 @@
 #include <cstring>
 #include <vector>
 #include "../../include/vicalib_amd.h"
-#include "vc_kutil.hpp"
-#include "vc_hostutil.hpp"
+#include "vc_lattice.hpp"
 #include "vc_uncertainty.hpp"
 
 namespace {
@@ -33,7 +32,7 @@ using vc::UncCov;
 using vc::UncFit;
 constexpr int kPerWg = 1024;                                                          // samples of a workgroup of the Gram sweep
 constexpr int kMapDoubles = vc::kUncSumDoubles + vc::kUncRingDoubles * vc::kCmpMaxRings;   // a workgroup's record of the map sweep
-enum { kReduceSums = 0, kReduceMap = 1 };
+static_assert(vc::kUncRingDoubles == vc::kLatRingDoubles, "a ring's record is the lattice core's");
 
 struct UncView {
   CmpPlan plan;                // A and the lattice (B is A again: the half of cmp_rays that is dropped)
@@ -42,7 +41,6 @@ struct UncView {
   unsigned char* flags;        // n: the last map sweep's, bit 2 added
   double* sigma;               // n x 3: s_uu, s_uv, s_vv
   double* part;                // workgroup partials of the kernel in flight
-  double* out;                 // the reduced record
 };
 
 __global__ __launch_bounds__(256) void k_unc_rays(UncView v) {
@@ -59,7 +57,6 @@ __global__ __launch_bounds__(256) void k_unc_rays(UncView v) {
 template <int MODEL>
 __global__ __launch_bounds__(256) void k_unc_gram(UncView v, double fit_radius) {
   constexpr int NS = vc::unc_ngram(vc::cvt_nk(MODEL));
-  __shared__ double s_w[4][NS];
   double acc[NS - 1], nf = 0.0;
 #pragma unroll
   for (int k = 0; k < NS - 1; ++k) acc[k] = 0.0;
@@ -75,53 +72,24 @@ __global__ __launch_bounds__(256) void k_unc_gram(UncView v, double fit_radius) 
     const double a[3] = {src[0], src[1], src[2]};
     if (vc::unc_gram_sample<MODEL>(v.plan, a, acc)) nf += 1.0;
   }
-  const int wave = threadIdx.x >> 6;
-  const bool first = (threadIdx.x & 63) == 0;
+  double sums[NS];
 #pragma unroll
-  for (int k = 0; k < NS; ++k) {
-    const double t = vc::wave_allsum(k < NS - 1 ? acc[k] : nf);
-    if (first) s_w[wave][k] = t;
-  }
-  __syncthreads();
-  if (threadIdx.x < NS) v.part[(size_t)blockIdx.x * NS + threadIdx.x] = ((s_w[0][threadIdx.x] + s_w[1][threadIdx.x]) + s_w[2][threadIdx.x]) + s_w[3][threadIdx.x];
+  for (int k = 0; k < NS; ++k) sums[k] = k < NS - 1 ? acc[k] : nf;
+  vc::lat_block_record(v.part + (size_t)blockIdx.x * NS, sums);
 }
 
 // The workgroup's record of the map sweep from one sample per thread: `in` (the thread has a sample), `valid`, var and lam (0 unless valid),
-// ring (-1 without a sample).  Sums by the butterfly, the four waves in wave order; the maximum keeps the lower sample on ties; thread k owns
-// ring k and walks the workgroup's entries in thread order.  Reached by every thread of the workgroup.
+// ring (-1 without a sample): count, invalid, sum var, the largest lam and its sample, then the rings, where var is summed and lam is the
+// key.  Reached by every thread of the workgroup.
 __device__ __forceinline__ void unc_block_sums(double* rec, int s, bool in, bool valid, double var, double lam, int ring, int n_rings) {
-  __shared__ double s_w[4][6];
   __shared__ double s_var[256], s_lam[256];      // s_lam: -1 of an invalid sample
   __shared__ int s_ring[256];
   s_var[threadIdx.x] = var;
   s_lam[threadIdx.x] = valid ? lam : -1.0;
   s_ring[threadIdx.x] = ring;
-  const double cnt = vc::wave_allsum(valid ? 1.0 : 0.0), inv = vc::wave_allsum(in && !valid ? 1.0 : 0.0), sv = vc::wave_allsum(var);
-  double best = valid ? lam : -1.0;
-  int best_i = valid ? s : -1;
-  vc::wave_argmax_low(&best, &best_i);
-  if ((threadIdx.x & 63) == 0) {
-    double* w = s_w[threadIdx.x >> 6];
-    w[0] = cnt; w[1] = inv; w[2] = sv; w[3] = best; w[4] = (double)best_i;
-  }
-  __syncthreads();
-  if (threadIdx.x < 3) rec[threadIdx.x] = ((s_w[0][threadIdx.x] + s_w[1][threadIdx.x]) + s_w[2][threadIdx.x]) + s_w[3][threadIdx.x];
-  if (threadIdx.x == 3) {                                          // waves hold ascending samples: a later wave wins only when larger
-    double b = s_w[0][3], bi = s_w[0][4];
-#pragma unroll
-    for (int w = 1; w < 4; ++w) if (s_w[w][3] > b) { b = s_w[w][3]; bi = s_w[w][4]; }
-    rec[3] = b; rec[4] = bi;
-  }
-  if ((int)threadIdx.x < n_rings) {
-    double rc = 0.0, ri = 0.0, rs = 0.0, rm = -1.0;
-    for (int j = 0; j < 256; ++j) {
-      if (s_ring[j] != (int)threadIdx.x) continue;
-      const double l = s_lam[j];
-      if (l >= 0.0) { rc += 1.0; rs += s_var[j]; rm = l > rm ? l : rm; } else ri += 1.0;
-    }
-    double* r = rec + vc::kUncSumDoubles + vc::kUncRingDoubles * threadIdx.x;
-    r[0] = rc; r[1] = ri; r[2] = rs; r[3] = rm;
-  }
+  const double sums[3] = {valid ? 1.0 : 0.0, in && !valid ? 1.0 : 0.0, var};
+  vc::lat_block_record<3, true>(rec, sums, valid ? lam : -1.0, valid ? s : -1);
+  vc::lat_ring_walk(rec + vc::kUncSumDoubles, n_rings, s_ring, s_var, s_lam);
 }
 
 template <int MODEL>
@@ -166,41 +134,11 @@ __global__ __launch_bounds__(256) void k_unc_rings(UncView v, int n_rings) {
   unc_block_sums(v.part + (size_t)blockIdx.x * kMapDoubles, s, in, valid, vc::unc_var(sg), vc::unc_lam(sg), ring, n_rings);
 }
 
-// columns of n_wg records of `stride` doubles added in workgroup order.  kReduceMap: column 3 is a maximum that carries column 4 (its sample;
-// strictly larger wins: workgroups hold ascending samples), every fourth ring column is a maximum.
-__global__ __launch_bounds__(64) void k_unc_reduce(const double* __restrict__ part, int n_wg, int stride, int m, int kind, double* __restrict__ out) {
-  for (int c = threadIdx.x; c < m; c += 64) {
-    const bool is_worst = kind == kReduceMap && c == 3, is_idx = kind == kReduceMap && c == 4;
-    const bool is_max = kind == kReduceMap && c >= vc::kUncSumDoubles && ((c - vc::kUncSumDoubles) & 3) == 3;
-    if (is_idx) continue;                                          // (written with column 3)
-    if (is_worst) {
-      double b = -1.0, bi = -1.0;
-      for (int g = 0; g < n_wg; ++g) {
-        const double x = part[(size_t)g * stride + 3];
-        if (x > b) { b = x; bi = part[(size_t)g * stride + 4]; }
-      }
-      out[3] = b; out[4] = bi;
-    } else if (is_max) {
-      double b = -1.0;
-      for (int g = 0; g < n_wg; ++g) { const double x = part[(size_t)g * stride + c]; b = x > b ? x : b; }
-      out[c] = b;
-    } else {
-      double t = 0.0;
-      for (int g = 0; g < n_wg; ++g) t += part[(size_t)g * stride + c];
-      out[c] = t;
-    }
-  }
-}
-
 }  // namespace
 
-struct vc_uncertainty {
-  int device = 0;
+struct vc_uncertainty : vc::LatticeHandle {   // d_buf: [rays | sigma | flags0 | flags | part]
   UncView v;
-  hipStream_t stream = nullptr;
-  unsigned char* d_buf = nullptr;      // [rays | sigma | flags0 | flags | part | out]
-  double* h_res = nullptr;             // pinned: the reduced record of the sweep in flight
-  bool have_rays = false, have_gram = false, have_run = false, in_flight = false, have_cal_cov = false;
+  bool have_rays = false, have_gram = false, have_run = false, have_cal_cov = false;
   double gram_radius = 0.0;            // the fit radius G, C and M were made for
   UncFit gram_fit;                     // ... and their M, G and fit set
   double gram_G[9];
@@ -227,23 +165,14 @@ void launch_gram(vc_uncertainty* u, double radius) {
   vc::with_model(u->v.plan.model_a, [&](auto m) {
     hipLaunchKernelGGL(k_unc_gram<decltype(m)::value>, dim3(u->n_wg_gram()), dim3(256), 0, u->stream, u->v, radius);
   });
-  hipLaunchKernelGGL(k_unc_reduce, dim3(1), dim3(64), 0, u->stream, u->v.part, u->n_wg_gram(), ns, ns, (int)kReduceSums, u->v.out);
+  u->reduce(u->v.part, u->n_wg_gram(), ns, ns);
 }
 void launch_map(vc_uncertainty* u, const UncFit& fit, const UncCov& cov, int n_rings, bool rings_only) {
   if (rings_only) hipLaunchKernelGGL(k_unc_rings, dim3(u->n_wg()), dim3(256), 0, u->stream, u->v, n_rings);
   else vc::with_model(u->v.plan.model_a, [&](auto m) {
     hipLaunchKernelGGL(k_unc_map<decltype(m)::value>, dim3(u->n_wg()), dim3(256), 0, u->stream, u->v, fit, cov, n_rings);
   });
-  hipLaunchKernelGGL(k_unc_reduce, dim3(1), dim3(64), 0, u->stream, u->v.part, u->n_wg(), kMapDoubles, vc::kUncSumDoubles + vc::kUncRingDoubles * n_rings,
-                     (int)kReduceMap, u->v.out);
-}
-// the reduced record of what was just enqueued, in h_res: the one synchronisation of a sweep (m = 0: none to fetch)
-bool fetch(vc_uncertainty* u, int m) {
-  u->in_flight = true;
-  if (hipGetLastError() != hipSuccess || (m > 0 && hipMemcpyAsync(u->h_res, u->v.out, (size_t)m * 8, hipMemcpyDeviceToHost, u->stream) != hipSuccess) ||
-      hipStreamSynchronize(u->stream) != hipSuccess) return false;
-  u->in_flight = false;
-  return true;
+  u->reduce(u->v.part, u->n_wg(), kMapDoubles, vc::kUncSumDoubles + vc::kUncRingDoubles * n_rings, vc::kUncSumDoubles - 2, vc::kUncSumDoubles);
 }
 
 }  // namespace
@@ -258,38 +187,28 @@ extern "C" {
 
 int vc_uncertainty_create(int device, int model, const double* params, int nparams, int width, int height, int grid_x, int grid_y, vc_uncertainty** out) {
   if (!out || !vc::undist_source_args_ok(model, params, nparams, width, height) || !vc::cvt_grid_ok(width, height, grid_x, grid_y)) return VC_ERR_BAD_ARG;
-  if (vch::open_device(device) != VC_OK) return VC_ERR_NO_DEVICE;
   vc_uncertainty* u = new vc_uncertainty;
-  u->device = device;
   std::memset(&u->v, 0, sizeof(u->v)); std::memset(&u->fit, 0, sizeof(u->fit)); std::memset(&u->cov, 0, sizeof(u->cov));
   std::memset(&u->gram_fit, 0, sizeof(u->gram_fit));
-  CmpPlan& p = u->v.plan;
-  p.model_a = model; p.model_b = model; p.w = width; p.h = height; p.gx = grid_x; p.gy = grid_y; p.n = grid_x * grid_y;
-  for (int k = 0; k < nparams; ++k) { p.Ka[k] = params[k]; p.Kb[k] = params[k]; }
-  vc::model_precompute(model, p.Ka, &p.pre_a); p.pre_b = p.pre_a;
+  vc::cmp_plan_set(&u->v.plan, model, params, nparams, model, params, nparams, width, height, grid_x, grid_y);      // (B is A again)
   auto carve = [&](vch::Carver q) {
-    const size_t n = (size_t)p.n;
+    const size_t n = (size_t)u->v.plan.n;
     u->v.rays = q.take<double>(n * 3);
     u->v.sigma = q.take<double>(n * 3);
     u->v.flags0 = q.take<unsigned char>(n);
     u->v.flags = q.take<unsigned char>(n);
     const size_t gram_part = (size_t)u->n_wg_gram() * vc::kUncMaxGram, map_part = (size_t)u->n_wg() * kMapDoubles;
     u->v.part = q.take<double>(gram_part > map_part ? gram_part : map_part);
-    u->v.out = q.take<double>(kMapDoubles);
     return q.bytes();
   };
-  if (hipStreamCreate(&u->stream) != hipSuccess || hipMalloc((void**)&u->d_buf, carve(vch::Carver())) != hipSuccess ||
-      hipHostMalloc((void**)&u->h_res, kMapDoubles * 8, hipHostMallocDefault) != hipSuccess) { vc_uncertainty_destroy(u); return VC_ERR_NO_DEVICE; }
+  if (!u->open(device, carve(vch::Carver()), kMapDoubles)) { delete u; return VC_ERR_NO_DEVICE; }
   carve(vch::Carver(u->d_buf));
   *out = u;
   return VC_OK;
 }
 void vc_uncertainty_destroy(vc_uncertainty* u) {
   if (!u) return;
-  (void)hipSetDevice(u->device);
-  if (u->stream) { (void)hipStreamSynchronize(u->stream); (void)hipStreamDestroy(u->stream); }
-  (void)hipFree(u->d_buf);
-  if (u->h_res) (void)hipHostFree(u->h_res);
+  u->close();
   delete u;
 }
 
@@ -300,11 +219,10 @@ int vc_uncertainty_run(vc_uncertainty* u, const double* cov, double sigma_px, do
   const double* c = cov ? cov : u->cal_cov;
   const int nk = u->nk();
   if (!vc::unc_run_args_ok(c, nk, sigma_px, fit_radius)) return VC_ERR_BAD_ARG;
-  if (hipSetDevice(u->device) != hipSuccess) return VC_ERR_NO_DEVICE;
-  if (u->in_flight) { (void)hipStreamSynchronize(u->stream); u->in_flight = false; }
+  if (!u->settle()) return VC_ERR_NO_DEVICE;
   if (!u->have_rays) {
     launch_rays(u);
-    if (!fetch(u, 0)) return VC_ERR_NO_DEVICE;
+    if (!u->fetch(0)) return VC_ERR_NO_DEVICE;
     u->have_rays = true;
   }
   if (fit_radius > 0.0) {
@@ -312,7 +230,7 @@ int vc_uncertainty_run(vc_uncertainty* u, const double* cov, double sigma_px, do
       u->have_gram = false;
       const int ns = vc::unc_ngram(nk);
       launch_gram(u, fit_radius);
-      if (!fetch(u, ns)) return VC_ERR_NO_DEVICE;
+      if (!u->fetch(ns)) return VC_ERR_NO_DEVICE;
       if (!vc::unc_solve_fit(u->h_res, nk, &u->gram_fit, u->gram_G, &u->gram_n_fit)) return VC_ERR_NUMERIC;
       u->gram_radius = fit_radius; u->have_gram = true;
     }
@@ -325,7 +243,7 @@ int vc_uncertainty_run(vc_uncertainty* u, const double* cov, double sigma_px, do
   vc::unc_pack_cov(c, nk, sigma_px, &u->cov);
   launch_map(u, u->fit, u->cov, vc::kCmpDefaultRings, false);
   const int m = vc::kUncSumDoubles + vc::kUncRingDoubles * vc::kCmpDefaultRings;
-  if (!fetch(u, m)) return VC_ERR_NO_DEVICE;
+  if (!u->fetch(m)) return VC_ERR_NO_DEVICE;
   std::memcpy(u->summary, u->h_res, (size_t)m * 8);
   u->fit_radius = fit_radius;
   u->have_run = true;
@@ -369,7 +287,7 @@ int vc_uncertainty_rings(vc_uncertainty* u, int n_rings, long long* count, long 
       if (hipSetDevice(u->device) != hipSuccess) return VC_ERR_NO_DEVICE;
       u->rings_n = 0;
       launch_map(u, u->fit, u->cov, n_rings, true);
-      if (!fetch(u, vc::kUncSumDoubles + vc::kUncRingDoubles * n_rings)) return VC_ERR_NO_DEVICE;
+      if (!u->fetch(vc::kUncSumDoubles + vc::kUncRingDoubles * n_rings)) return VC_ERR_NO_DEVICE;
       std::memcpy(u->rings, u->h_res + vc::kUncSumDoubles, (size_t)vc::kUncRingDoubles * n_rings * 8);
       u->rings_n = n_rings;
     }
@@ -387,8 +305,7 @@ int vc_uncertainty_rings(vc_uncertainty* u, int n_rings, long long* count, long 
 
 int vc_time_uncertainty(vc_uncertainty* u, int reps, double out_ms[3]) {
   if (!u || reps < 1 || !out_ms || !u->have_run) return VC_ERR_BAD_ARG;
-  if (hipSetDevice(u->device) != hipSuccess) return VC_ERR_NO_DEVICE;
-  if (u->in_flight) { (void)hipStreamSynchronize(u->stream); u->in_flight = false; }
+  if (!u->settle()) return VC_ERR_NO_DEVICE;
   for (int what = 0; what < 3; ++what) {
     auto launch = [&]() {                                          // (each rewrites what the last run left: the same rays, the same map)
       if (what == 0) launch_rays(u);
