@@ -67,6 +67,22 @@ int vc_pnp_planar(int model, const double* params, int nparams, int n, const dou
 int vc_pnp_planar_ransac(int model, const double* params, int nparams, int n, const double* p_w, const double* p_c,
                          int iterations, double tol_px, double T_cw[7], double* rms_px, int* n_inliers, char* inlier);
 int vc_set_pnp_ransac(vc_calibrator* h, int iterations, double tol_px);
+/* Poses of many views of the planar target at once, on the device.  View v owns corners view_off[v] .. view_off[v+1]-1.
+   One wavefront per view runs what vc_pnp_planar_ransac runs (iterations = 0 or a view of fewer than 5 corners: vc_pnp_planar).
+   status[v]: 0 ok, 1 fewer than 4 corners, 2 not planar, 3 no pose (DLT / rotation / refinement failed), 4 no consensus (< 4 inliers).
+   T_cw, rms, n_inliers of a view with status != 0 are left untouched; inlier (may be NULL) gets 0 there.
+   VC_ERR_BAD_ARG before any device call (a null pointer, n_views < 0, offsets that decrease, an unknown model, iterations < 0,
+   a tol_px that is not >= 0); VC_ERR_NO_DEVICE without that device.  Two runs, and a view alone or among others, give the same bits. */
+int vc_pnp_planar_batch(int device, int n_views, const int* view_model, const double* view_K /* n_views x 10 */,
+                        const int* view_off /* n_views + 1 */, const double* p_w /* total x 3 */, const double* p_c /* total x 2 */,
+                        int iterations, double tol_px, double* T_cw /* n_views x 7 */, double* rms, int* n_inliers,
+                        char* inlier /* total, or NULL */, int* status);
+/* Mean time in ms of the batch's kernel alone on that input: `reps` launches back to back between two events, after one run that warms up. */
+int vc_time_pnp_planar_batch(int device, int n_views, const int* view_model, const double* view_K, const int* view_off, const double* p_w,
+                             const double* p_c, int iterations, double tol_px, int reps, double* kernel_ms);
+/* on: vc_init_frame_poses_pnp and the seeds of vc_holdout_compute(h, NULL, ...) come from one vc_pnp_planar_batch over every view of
+   >= 4 corners on the calibrator's device; the rule that picks a frame's camera stays on the host.  Default 0: the host routine. */
+int vc_set_pnp_device(vc_calibrator* h, int on);
 /* AddObservation(frame, cam, p_w, p_c, time) :385-468, in bulk: n corners of one (frame, camera) */
 int vc_add_observations(vc_calibrator* h, int frame, int camera, int n, const double* p_w /* n x 3 */,
                         const double* p_c /* n x 2 */);

@@ -72,6 +72,8 @@ class ViCalibrator {
   int AddImuMeasurements(int n, const double* gyro, const double* accel, const double* time) { return vc_add_imu(h_, n, gyro, accel, time); }
   // robust branch of calibu::PosePnPRansac (iterations = 0: the reference's own call, vicalib-task.cc:323-325)
   void SetPnPRansac(int iterations, double tol_px) { vc_checked(vc_set_pnp_ransac(h_, iterations, tol_px), "SetPnPRansac"); }
+  // the pose seeds (InitFramePosesPnP, HoldoutCompute without seeds) from the batched device PnP instead of the host routine
+  void SetPnPDevice(bool on) { vc_checked(vc_set_pnp_device(h_, on ? 1 : 0), "SetPnPDevice"); }
   int InitFramePosesPnP() { int n = 0; vc_checked(vc_init_frame_poses_pnp(h_, &n), "InitFramePosesPnP"); return n; }      // vicalib-task.cc:335-348
 
   void SetOptimizationFlags(bool bias_active, bool inertial_active, bool rotation_only, bool optimize_imu_time_offset) {   // :252

@@ -65,6 +65,7 @@ struct vc_calibrator {
        is_visual_active = true, rotation_only = true, optimize_time_offset = true, is_finished = false,
        gravity_initialized = false, outliers_removed = false;
   int pnp_its = 0; double pnp_tol = 0.0;     // PosePnPRansac(..., robust_3pt_its = 0, robust_3pt_tol = 0, ...) at vicalib-task.cc:323-325
+  bool pnp_device = false;                   // vc_set_pnp_device: the seeds come from the batched device PnP (vc_seed.hip)
   int max_iters = 200;                       // FLAGS_max_iters
   double function_tolerance = 1e-6;          // vicalibrator.h:149
   double gradient_tolerance = 1e-10, parameter_tolerance = 1e-8;   // Ceres defaults
@@ -189,6 +190,10 @@ struct vc_calibrator {
     ~Holdout() { if (stage) (void)hipHostFree(stage); }
   } hold;
   int holdout_compute(const double* seeds, int max_iters);
+  // T_cw (x 7) and status of views of this rig's cameras through the batched device PnP (vc_seed.hip) with pnp_its / pnp_tol, on `stream`:
+  // view v is seen by camera view_cam[v] and owns corners view_off[v] .. view_off[v+1]-1 of pw (x 3) / pc (x 2)
+  int pnp_batch(const std::vector<int>& view_cam, const std::vector<int>& view_off, const std::vector<double>& pw, const std::vector<double>& pc,
+                std::vector<double>* T_cw, std::vector<int>* status);
 
   ~vc_calibrator() {
     stop();

@@ -2,6 +2,7 @@
 // status codes; RCCL communicators; parity / timing hooks; solution covariance; results as text and cameras.xml.
 #include "vc_calibrator.hpp"
 #include "vc_uncertainty.hpp"
+#include "vc_seed.hpp"
 
 static int env_bit(const char* name) { const char* e = std::getenv(name); return (e && (e[0] == '0' || e[0] == '1')) ? e[0] - '0' : -1; }
 Switches Switches::read() {
@@ -20,6 +21,21 @@ Switches Switches::read() {
   w.chain.hadd_early = env_bit("VICALIB_AMD_HADD_EARLY") != 0; w.chain.defer_tail = env_bit("VICALIB_AMD_DEFER_TAIL") != 0;
   w.chain.odd_even = env_bit("VICALIB_AMD_CHAIN_ODD_EVEN") != 0;
   return w;
+}
+
+int vc_calibrator::pnp_batch(const std::vector<int>& view_cam, const std::vector<int>& view_off, const std::vector<double>& pw, const std::vector<double>& pc,
+                             std::vector<double>* T_cw, std::vector<int>* status) {
+  const size_t nv = view_cam.size();
+  std::vector<int> model(nv + 1, 0), n_in(nv + 1, 0);
+  std::vector<double> K((nv + 1) * 10, 0.0), rms(nv + 1, 0.0);
+  for (size_t v = 0; v < nv; ++v) {
+    const HostCam& cm = cams[view_cam[v]];
+    model[v] = cm.model;
+    std::memcpy(&K[10 * v], cm.K, (size_t)cm.nk * 8);
+  }
+  T_cw->assign((nv + 1) * 7, 0.0); status->assign(nv + 1, 0);
+  return vc::seed_batch_run(device, stream, (int)nv, model.data(), K.data(), view_off.data(), pw.data(), pc.data(), pnp_its, pnp_tol, T_cw->data(),
+                            rms.data(), n_in.data(), nullptr, status->data());
 }
 
 // =====================================================================================================
@@ -132,8 +148,59 @@ int vc_set_pnp_ransac(vc_calibrator* h, int iterations, double tol_px) {
   h->pnp_its = iterations; h->pnp_tol = tol_px;
   return VC_OK;
 }
+int vc_set_pnp_device(vc_calibrator* h, int on) {
+  NOT_RUNNING(h);
+  h->pnp_device = on != 0;
+  return VC_OK;
+}
+// vc_init_frame_poses_pnp with the switch of vc_set_pnp_device on: every view of >= 4 corners in one batch on the calibrator's device, then
+// the rule below on the host -- cameras in order, a camera other than 0 only while camera 0 has not succeeded, T_wk = T_cw^-1 * T_ck
+static int init_frame_poses_device(vc_calibrator* h, int* n_initialised) {
+  BIND_DEVICE(h);
+  const int N = (int)h->frames.size(), C = (int)h->cams.size();
+  std::vector<std::vector<int>> view((size_t)N * std::max(C, 1));
+  for (size_t i = 0; i < h->o_frame.size(); ++i) view[(size_t)h->o_frame[i] * C + h->o_cam[i]].push_back((int)i);
+  std::vector<int> v_frame, v_cam, v_off(1, 0);
+  std::vector<double> pw, pc;
+  for (int f = 0; f < N; ++f)
+    for (int c = 0; c < C; ++c) {
+      const std::vector<int>& ids = view[(size_t)f * C + c];
+      if (ids.size() < 4) continue;
+      for (int i : ids) {
+        pw.insert(pw.end(), &h->pts.xyz[3 * (size_t)h->o_pid[i]], &h->pts.xyz[3 * (size_t)h->o_pid[i]] + 3);
+        pc.insert(pc.end(), &h->o_pc[2 * (size_t)i], &h->o_pc[2 * (size_t)i] + 2);
+      }
+      v_frame.push_back(f); v_cam.push_back(c); v_off.push_back((int)(pc.size() / 2));
+    }
+  std::vector<double> T_cw;
+  std::vector<int> status;
+  const int rc = h->pnp_batch(v_cam, v_off, pw, pc, &T_cw, &status);
+  if (rc != VC_OK) return rc;
+  std::vector<char> cam0_good((size_t)std::max(N, 1), 0), any((size_t)std::max(N, 1), 0);
+  int done = 0;
+  for (size_t v = 0; v < v_cam.size(); ++v) {                     // (ordered by frame, then camera)
+    const int f = v_frame[v], c = v_cam[v];
+    if ((c != 0 && cam0_good[f]) || status[v] != 0) continue;
+    const HostCam& cm = h->cams[c];
+    const double* Tc = &T_cw[7 * v];
+    const double qi[4] = {-Tc[0], -Tc[1], -Tc[2], Tc[3]};
+    double ti[3], tr[3], T[7];
+    const double nt[3] = {-Tc[4], -Tc[5], -Tc[6]};
+    quat_rotate(qi, nt, ti);
+    quat_mul(qi, cm.T_ck, T);
+    quat_rotate(qi, cm.T_ck + 4, tr);
+    for (int k = 0; k < 3; ++k) T[4 + k] = ti[k] + tr[k];
+    std::memcpy(h->frames[f].T, T, 56);
+    if (!any[f]) { any[f] = 1; ++done; }
+    if (c == 0) cam0_good[f] = 1;
+  }
+  if (n_initialised) *n_initialised = done;
+  h->device_dirty = true;
+  return VC_OK;
+}
 int vc_init_frame_poses_pnp(vc_calibrator* h, int* n_initialised) {
   NOT_RUNNING(h);
+  if (h->pnp_device) return init_frame_poses_device(h, n_initialised);
   const int N = (int)h->frames.size(), C = (int)h->cams.size();
   // group the observation indices per (frame, camera)
   std::vector<std::vector<int>> view((size_t)N * std::max(C, 1));

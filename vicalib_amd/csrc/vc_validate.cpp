@@ -35,6 +35,46 @@ static void holdout_pnp_seeds(const vc_calibrator* h, const vc_calibrator::Holdo
   }
 }
 
+// The same seeds with the switch of vc_set_pnp_device on: every tile of >= 4 corners in one batch on the calibrator's device, the rule above
+// applied to the statuses on the host.
+static int holdout_pnp_seeds_device(vc_calibrator* h, const vc_calibrator::Holdout& ho, const std::vector<int>& order, const std::vector<int>& tile_frame,
+                                    const std::vector<int>& tile_cam, const std::vector<int>& tile_off, std::vector<double>* seeds, std::vector<int>* ok) {
+  std::vector<int> v_tile, v_cam, v_off(1, 0);
+  std::vector<double> pw, pc;
+  for (size_t t = 0; t < tile_frame.size(); ++t) {
+    const int n = tile_off[t + 1] - tile_off[t];
+    if (n < 4) continue;
+    for (int k = 0; k < n; ++k) {
+      const size_t i = (size_t)order[tile_off[t] + k];
+      pw.insert(pw.end(), &ho.pts.xyz[3 * (size_t)ho.o_pid[i]], &ho.pts.xyz[3 * (size_t)ho.o_pid[i]] + 3);
+      pc.insert(pc.end(), &ho.o_pc[2 * i], &ho.o_pc[2 * i] + 2);
+    }
+    v_tile.push_back((int)t); v_cam.push_back(tile_cam[t]); v_off.push_back((int)(pc.size() / 2));
+  }
+  std::vector<double> T_all;
+  std::vector<int> status;
+  const int rc = h->pnp_batch(v_cam, v_off, pw, pc, &T_all, &status);
+  if (rc != VC_OK) return rc;
+  std::vector<char> cam0_good((size_t)std::max(ho.n_frames, 1), 0);
+  for (size_t v = 0; v < v_tile.size(); ++v) {                  // (ordered by frame, then camera)
+    const int f = tile_frame[v_tile[v]], c = v_cam[v];
+    if ((c != 0 && cam0_good[f]) || status[v] != 0) continue;
+    const HostCam& cm = h->cams[c];
+    const double* T_cw = &T_all[7 * v];
+    const double qi[4] = {-T_cw[0], -T_cw[1], -T_cw[2], T_cw[3]};
+    const double nt[3] = {-T_cw[4], -T_cw[5], -T_cw[6]};
+    double ti[3], tr[3];
+    double* T = seeds->data() + (size_t)f * kPoseStride;
+    quat_rotate(qi, nt, ti);
+    quat_mul(qi, cm.T_ck, T);
+    quat_rotate(qi, cm.T_ck + 4, tr);
+    for (int k = 0; k < 3; ++k) T[4 + k] = ti[k] + tr[k];
+    (*ok)[f] = 1;
+    if (c == 0) cam0_good[f] = 1;
+  }
+  return VC_OK;
+}
+
 int vc_calibrator::holdout_compute(const double* seeds_in, int iters) {
   HIP_OK(hipSetDevice(device));
   Holdout& ho = hold;
@@ -67,6 +107,9 @@ int vc_calibrator::holdout_compute(const double* seeds_in, int iters) {
   for (int f = 0; f < F; ++f) seeds[(size_t)f * kPoseStride + 3] = 1.0;
   if (seeds_in) {
     for (int f = 0; f < F; ++f) { std::memcpy(&seeds[(size_t)f * kPoseStride], seeds_in + 7 * (size_t)f, 56); seed_ok[f] = 1; }
+  } else if (pnp_device) {
+    const int rc = holdout_pnp_seeds_device(this, ho, order, tile_frame, tile_cam, tile_off, &seeds, &seed_ok);
+    if (rc != VC_OK) return rc;
   } else {
     holdout_pnp_seeds(this, ho, order, tile_frame, tile_cam, tile_off, &seeds, &seed_ok);
   }

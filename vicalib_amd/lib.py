@@ -29,7 +29,7 @@ SYMBOLS = [
     "vc_get_biases", "vc_get_scale_factor", "vc_get_gravity", "vc_time_offset", "vc_mean_squared_error", "vc_get_camera_proj_rmse",
     "vc_get_num_iterations", "vc_num_imu_measurements", "vc_get_imu_measurements", "vc_get_integration_poses", "vc_print_results", "vc_write_camera_models", "vc_trace_len", "vc_get_trace", "vc_set_shard", "vc_get_stream", "vc_prepare",
     "vc_linearize", "vc_step_hold", "vc_shared_dim", "vc_run_iterations", "vc_download_state", "vc_evaluate", "vc_time_kernels", "vc_time_stages", "vc_get_imu_blocks", "vc_get_debug_stamps", "vc_num_observations", "vc_num_tiles",
-    "vc_init_frame_poses_pnp", "vc_pnp_planar", "vc_pnp_planar_ransac", "vc_set_pnp_ransac", "vc_rccl_unique_id", "vc_set_shard_rccl", "vc_shard_comm_create", "vc_set_shard_comm", "vc_shard_comm_destroy", "vc_allreduce_calls", "vc_shard_info", "vc_pass_paths", "vc_chain_order", "vc_last_error", "vc_get_imu_weights",
+    "vc_init_frame_poses_pnp", "vc_pnp_planar", "vc_pnp_planar_ransac", "vc_set_pnp_ransac", "vc_pnp_planar_batch", "vc_time_pnp_planar_batch", "vc_set_pnp_device", "vc_rccl_unique_id", "vc_set_shard_rccl", "vc_shard_comm_create", "vc_set_shard_comm", "vc_shard_comm_destroy", "vc_allreduce_calls", "vc_shard_info", "vc_pass_paths", "vc_chain_order", "vc_last_error", "vc_get_imu_weights",
     "vc_solution_covariance_dim", "vc_get_solution_covariance", "vc_get_solution_covariance_names",
     "vc_target_make_pattern", "vc_target_find",
     "vc_report_compute", "vc_report_num_corners", "vc_report_corners", "vc_report_num_views", "vc_report_views", "vc_report_error_map", "vc_report_num_imu_blocks", "vc_report_imu", "vc_time_report_sweeps",
@@ -99,6 +99,44 @@ def pnp_planar_ransac(model, params, p_w, p_c, iterations=64, tol_px=2.0):
     _check(L.vc_pnp_planar_ransac(m, _d(params), len(params), len(p_w), _d(p_w), _d(p_c), int(iterations), C.c_double(tol_px), _d(T),
                                   C.byref(rms), C.byref(n_in), flags.ctypes.data_as(C.c_void_p)), "pnp_planar_ransac")
     return T, rms.value, flags.astype(bool)
+
+
+def _pnp_batch_arrays(models, params, view_off, p_w, p_c):
+    from .synth import MODEL_IDS
+    n = len(models)
+    m = np.array([MODEL_IDS[x] if isinstance(x, str) else int(x) for x in models], dtype=np.int32)
+    K = np.zeros((n, 10))
+    for v in range(n):
+        K[v, :len(params[v])] = params[v]
+    off = np.ascontiguousarray(view_off, dtype=np.int32)
+    p_w = np.ascontiguousarray(p_w, dtype=np.float64).reshape(-1, 3); p_c = np.ascontiguousarray(p_c, dtype=np.float64).reshape(-1, 2)
+    return n, m, K, off, p_w, p_c
+
+
+def time_pnp_planar_batch(models, params, view_off, p_w, p_c, iterations=0, tol_px=0.0, device=0, reps=10):
+    """mean time in ms of the kernel of pnp_planar_batch alone on that input (vc_time_pnp_planar_batch: HIP events, launches back to back)"""
+    n, m, K, off, p_w, p_c = _pnp_batch_arrays(models, params, view_off, p_w, p_c)
+    ms = C.c_double(0)
+    _check(load().vc_time_pnp_planar_batch(int(device), n, m.ctypes.data_as(C.c_void_p), _d(K), off.ctypes.data_as(C.c_void_p), _d(p_w), _d(p_c), int(iterations),
+                                           C.c_double(tol_px), int(reps), C.byref(ms)), "time_pnp_planar_batch")
+    return ms.value
+
+
+def pnp_planar_batch(models, params, view_off, p_w, p_c, iterations=0, tol_px=0.0, device=0, out=None):
+    """Poses of many views at once on the device (vc_pnp_planar_batch).  models: per view (names or ids); params: per view, up to 10 each;
+    view v owns corners view_off[v] .. view_off[v+1]-1 of p_w / p_c.  Returns T_cw [n, 7], rms, n_inliers, inlier (bool per corner), status;
+    `out` may hold pre-filled T_cw / rms / n_inliers arrays: a view with status != 0 leaves its rows as they were."""
+    L = load()
+    n, m, K, off, p_w, p_c = _pnp_batch_arrays(models, params, view_off, p_w, p_c)
+    out = dict(out or {})
+    T = out.get("T_cw", np.zeros((n, 7))); rms = out.get("rms", np.zeros(n)); n_in = out.get("n_inliers", np.zeros(n, dtype=np.int32))
+    assert T.dtype == np.float64 and rms.dtype == np.float64 and n_in.dtype == np.int32 and T.flags.c_contiguous
+    flags = np.zeros(max(len(p_w), 1), dtype=np.int8); status = np.full(max(n, 1), -1, dtype=np.int32)
+    pad3, pad2 = (p_w if len(p_w) else np.zeros((1, 3))), (p_c if len(p_c) else np.zeros((1, 2)))
+    _check(L.vc_pnp_planar_batch(int(device), n, m.ctypes.data_as(C.c_void_p), _d(K), off.ctypes.data_as(C.c_void_p), _d(pad3), _d(pad2), int(iterations),
+                                 C.c_double(tol_px), T.ctypes.data_as(C.c_void_p), rms.ctypes.data_as(C.c_void_p), n_in.ctypes.data_as(C.c_void_p),
+                                 flags.ctypes.data_as(C.c_void_p), status.ctypes.data_as(C.c_void_p)), "pnp_planar_batch")
+    return dict(T_cw=T, rms=rms, n_inliers=n_in, inlier=flags[:len(p_w)].astype(bool), status=status[:n])
 
 
 def load():
@@ -207,6 +245,10 @@ class ViCalibrator:
         return n.value
 
     def SetPnPRansac(self, iterations, tol_px): _check(self.L.vc_set_pnp_ransac(self.h, int(iterations), C.c_double(tol_px)), "SetPnPRansac")
+
+    def SetPnPDevice(self, on):
+        """the seeds of InitFramePosesPnP and of HoldoutCompute(None) from the batched device PnP (vc_set_pnp_device); default off: the host routine"""
+        _check(self.L.vc_set_pnp_device(self.h, int(bool(on))), "SetPnPDevice")
 
     def AddObservations(self, frame, camera, p_w, p_c):
         p_w = np.ascontiguousarray(p_w, dtype=np.float64); p_c = np.ascontiguousarray(p_c, dtype=np.float64)
