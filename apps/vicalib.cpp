@@ -79,6 +79,9 @@ static void DefineFlags() {
   Define("pnp_ransac_its", "int32", "0", "Minimal-sample iterations of the robust pose seed (0: plain PnP, as the reference calls PosePnPRansac).");
   Define("pnp_ransac_tol", "double", "2.0", "Inlier threshold of the robust pose seed, pixels.");
   Define("pnp_device", "bool", "false", "Seed the frame poses with the batched PnP on the GPU instead of the host routine (same seeds to 1e-6).");
+  Define("seed_focal", "bool", "false", "Without -model_files: start every camera at the focal length its views of the target give (homographies, on the GPU) instead of 300.");
+  Define("seed_focal_radius", "double", "0.5", "Corners used by -seed_focal lie within this fraction of the half diagonal of the image centre (<= 0: the whole image).");
+  Define("seed_focal_fit_px", "double", "0", "Views whose homography fits worse than this many pixels rms are left out of -seed_focal (0: off).");
   Define("gyro_sigma", "double", "5.3088444e-5", "Sigma of gyroscope measurements.");
   Define("accel_sigma", "double", "0.001883649", "Sigma of accel measurements.");
   Define("remove_outliers", "bool", "false", "Remove outliers and re-optimise.");
@@ -1508,6 +1511,10 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "ERROR: illegal value '%s' specified for flag 'holdout_every': expected 0 (off) or N >= 2 (N = 1 would leave no frame to calibrate from)\n", FlagString("holdout_every").c_str());
     return 1;
   }
+  if (FlagBool("seed_focal")) {
+    if (!FlagString("model_files").empty()) { std::fprintf(stderr, "ERROR: -seed_focal and -model_files exclude each other: a model file brings its own focal length\n"); return 1; }
+    if (!(FlagDouble("seed_focal_fit_px") >= 0.0)) { std::fprintf(stderr, "ERROR: illegal value for flag 'seed_focal_fit_px': expected at least 0\n"); return 1; }
+  }
   UncertaintyOptions uncertainty;
   if (!UncertaintyFlags(&uncertainty, &err)) { std::fprintf(stderr, "ERROR: %s\n", err.c_str()); return 1; }
   SelectOptions select;
@@ -1709,6 +1716,49 @@ int main(int argc, char** argv) {
     std::vector<long> fit;
     for (size_t i = 0; i < frame_ids.size(); ++i) (vc::holdout_is_held((long long)i, holdout_every) ? held_ids : fit).push_back(frame_ids[i]);
     frame_ids.swap(fit);
+  }
+
+  // ---- -seed_focal: fx = fy of every camera from the homographies of its views in the frames that will be calibrated (held-out frames are
+  // not among them), one batch on -device; the one result serves every rank
+  if (FlagBool("seed_focal")) {
+    const std::set<long> fit_ids(frame_ids.begin(), frame_ids.end());
+    std::vector<int> view_cam, view_off(1, 0);
+    std::vector<double> pp, radius, pw, pc;
+    const double frac = FlagDouble("seed_focal_radius");
+    for (size_t c = 0; c < n_cam; ++c) {
+      const double w = input_cameras[c].width, h = input_cameras[c].height;
+      pp.insert(pp.end(), {w / 2.0, h / 2.0});
+      radius.push_back(frac > 0.0 ? frac * 0.5 * std::sqrt(w * w + h * h) : 0.0);
+      std::map<long, std::vector<const Detection*>> per_frame;
+      for (const Detection& d : channels[c].det)
+        if (fit_ids.count(d.frame) && d.dot < grid_w * grid_h) per_frame[d.frame].push_back(&d);
+      for (const auto& kv : per_frame) {
+        for (const Detection* d : kv.second) { pw.insert(pw.end(), {d->X, d->Y, d->Z}); pc.insert(pc.end(), {d->u, d->v}); }
+        view_cam.push_back((int)c); view_off.push_back((int)(pc.size() / 2));
+      }
+    }
+    vic::SeedFocalResult sf;
+    try { sf = vic::SeedFocalBatch((int)FlagInt("device"), view_cam, pp, radius, view_off, pw, pc, 4, FlagDouble("seed_focal_fit_px")); }
+    catch (const std::exception& e) { std::fprintf(stderr, "F -seed_focal: %s (device %d)\n", e.what(), (int)FlagInt("device")); return 3; }
+    for (size_t c = 0; c < n_cam; ++c) {
+      int total = 0;
+      std::vector<double> fv;
+      for (size_t v = 0; v < view_cam.size(); ++v) {
+        if (view_cam[v] != (int)c) continue;
+        ++total;
+        if (sf.view_status[v] == 0 && std::isfinite(sf.view_f[v])) fv.push_back(sf.view_f[v]);
+      }
+      if (sf.cam_status[c] == 0) {
+        input_cameras[c].params[0] = input_cameras[c].params[1] = sf.cam_f[c];
+        std::sort(fv.begin(), fv.end());
+        if (fv.empty()) std::fprintf(stderr, "I camera %zu: focal length seed %.2f px from %d of %d views\n", c, sf.cam_f[c], sf.cam_views[c], total);
+        else std::fprintf(stderr, "I camera %zu: focal length seed %.2f px from %d of %d views (single views: %.2f .. %.2f px, median %.2f, %zu of them tilted enough)\n",
+                          c, sf.cam_f[c], sf.cam_views[c], total, fv.front(), fv.back(), fv[fv.size() / 2], fv.size());
+      } else {
+        const char* why = sf.cam_status[c] == 1 ? "no usable view" : sf.cam_status[c] == 2 ? "the target was never tilted against the image plane" : "the views give no positive focal length";
+        std::fprintf(stderr, "W camera %zu: no focal length seed (%s, %d of %d views usable); keeping fx = fy = %g\n", c, why, sf.cam_views[c], total, input_cameras[c].params[0]);
+      }
+    }
   }
 
   // ---- one calibrator per GPU; frames sharded contiguously, the library's own RCCL communicator does the per-iteration

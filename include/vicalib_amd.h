@@ -83,6 +83,35 @@ int vc_time_pnp_planar_batch(int device, int n_views, const int* view_model, con
 /* on: vc_init_frame_poses_pnp and the seeds of vc_holdout_compute(h, NULL, ...) come from one vc_pnp_planar_batch over every view of
    >= 4 corners on the calibrator's device; the rule that picks a frame's camera stays on the host.  Default 0: the host routine. */
 int vc_set_pnp_device(vc_calibrator* h, int on);
+/* The focal length of every camera from its views of the planar target, on the device, before anything is solved: a start value for
+   fx = fy where no model file gives one.  View v belongs to camera view_cam[v] and owns corners view_off[v] .. view_off[v+1]-1.
+   A corner is used when both coordinates are finite and it lies within cam_radius pixels of the camera's assumed principal point
+   cam_pp (radius <= 0: every finite corner).  Per view: H, the DLT homography from target (X, Y) to pixel - principal point, scaled
+   to h1x^2 + h1y^2 + h2x^2 + h2y^2 = 2 (h1, h2: its first two columns); view_rows = c1 d1 c2 d2 with c1 = h1x h2x + h1y h2y,
+   d1 = -h1z h2z, c2 = (h1x^2 + h1y^2) - (h2x^2 + h2y^2), d2 = h2z^2 - h1z^2, so that c1 / f^2 = d1 and c2 / f^2 = d2;
+   view_f = the focal length of that view alone (NaN when the view is tilted by less than min_tilt_deg or gives none; diagnosis only);
+   view_fit_px = the rms transfer error of H over the used corners.
+   view_status: 0 ok, 1 fewer than max(min_corners, 4) used corners, 2 used target points not on one plane z, 3 no homography,
+   4 view_fit_px above max_fit_px (max_fit_px = 0: not tested).  The outputs of a view with status != 0 are left untouched.
+   Per camera, over its status-0 views in view order: Scc = sum(c1^2 + c2^2), Scd = sum(c1 d1 + c2 d2), cam_f = sqrt(Scc / Scd);
+   cam_views = the number of those views.  cam_status: 0 ok, 1 no usable view, 2 Scc < sin^4(min_tilt_deg) (the target was never
+   tilted), 3 Scd / Scc not positive or not finite.  cam_f of a camera with status != 0 is left untouched.
+   VC_ERR_BAD_ARG before any device call (a null pointer other than view_H, n_views < 0, n_cams < 1, a view_cam outside
+   0 .. n_cams-1, offsets that decrease, a principal point that is not finite, max_fit_px < 0, min_tilt_deg outside (0, 90));
+   VC_ERR_NO_DEVICE without that device: there is no host fallback.  Two runs give the same bits, a view gives the same bits alone
+   or among others, and a camera's result does not depend on the views of other cameras in the batch. */
+int vc_seed_focal_batch(int device, int n_views, const int* view_cam, int n_cams,
+                        const double* cam_pp /* n_cams x 2 */, const double* cam_radius /* n_cams */,
+                        const int* view_off /* n_views + 1 */, const double* p_w /* total x 3 */,
+                        const double* p_c /* total x 2 */, int min_corners, double max_fit_px, double min_tilt_deg,
+                        double* view_H /* n_views x 9, may be NULL */,
+                        double* view_rows /* n_views x 4: c1 d1 c2 d2 */,
+                        double* view_f, double* view_fit_px, int* view_used, int* view_status,
+                        double* cam_f, int* cam_views, int* cam_status);
+/* Mean time in ms of the batch's two kernels alone on that input: `reps` runs back to back between two events, after one that warms up. */
+int vc_time_seed_focal_batch(int device, int n_views, const int* view_cam, int n_cams, const double* cam_pp, const double* cam_radius,
+                             const int* view_off, const double* p_w, const double* p_c, int min_corners, double max_fit_px,
+                             double min_tilt_deg, int reps, double* kernel_ms);
 /* AddObservation(frame, cam, p_w, p_c, time) :385-468, in bulk: n corners of one (frame, camera) */
 int vc_add_observations(vc_calibrator* h, int frame, int camera, int n, const double* p_w /* n x 3 */,
                         const double* p_c /* n x 2 */);

@@ -9,6 +9,7 @@
 
 #include <algorithm>
 #include <array>
+#include <cmath>
 #include <stdexcept>
 #include <cstring>
 #include <string>
@@ -40,6 +41,32 @@ struct VicalibFrame {          // vicalibrator.h:76-97
 inline int vc_checked(int rc, const char* what) {
   if (rc < 0) throw std::runtime_error(std::string("vicalib_amd: ") + what + " failed (status " + std::to_string(rc) + ")");
   return rc;
+}
+
+// The focal-length seed of every camera from its views of the planar target (vc_seed_focal_batch; on the device, no handle).
+struct SeedFocalResult {
+  std::vector<double> view_H, view_rows, view_f, view_fit_px;      // x 9, x 4 (c1 d1 c2 d2), x 1, x 1 per view; NaN where the view was refused
+  std::vector<int> view_used, view_status;
+  std::vector<double> cam_f;                                       // NaN where the camera was refused
+  std::vector<int> cam_views, cam_status;
+};
+inline SeedFocalResult SeedFocalBatch(int device, const std::vector<int>& view_cam, const std::vector<double>& cam_pp, const std::vector<double>& cam_radius,
+                                      const std::vector<int>& view_off, const std::vector<double>& p_w, const std::vector<double>& p_c, int min_corners = 4,
+                                      double max_fit_px = 0.0, double min_tilt_deg = 5.0) {
+  const size_t nv = view_cam.size(), nc = cam_radius.size();
+  if (view_off.size() != nv + 1 || cam_pp.size() != 2 * nc) throw std::runtime_error("vicalib_amd: SeedFocalBatch: array sizes disagree");
+  const double nan = std::nan("");
+  SeedFocalResult r;
+  r.view_H.assign(9 * nv + 1, nan); r.view_rows.assign(4 * nv + 1, nan); r.view_f.assign(nv + 1, nan); r.view_fit_px.assign(nv + 1, nan);
+  r.view_used.assign(nv + 1, 0); r.view_status.assign(nv + 1, -1); r.cam_f.assign(nc + 1, nan); r.cam_views.assign(nc + 1, 0); r.cam_status.assign(nc + 1, -1);
+  const double none[3] = {0, 0, 0};
+  vc_checked(vc_seed_focal_batch(device, (int)nv, nv ? view_cam.data() : r.view_used.data(), (int)nc, cam_pp.data(), cam_radius.data(), view_off.data(),
+                                 p_w.empty() ? none : p_w.data(), p_c.empty() ? none : p_c.data(), min_corners, max_fit_px, min_tilt_deg, r.view_H.data(),
+                                 r.view_rows.data(), r.view_f.data(), r.view_fit_px.data(), r.view_used.data(), r.view_status.data(), r.cam_f.data(),
+                                 r.cam_views.data(), r.cam_status.data()), "SeedFocalBatch");
+  r.view_H.resize(9 * nv); r.view_rows.resize(4 * nv); r.view_f.resize(nv); r.view_fit_px.resize(nv); r.view_used.resize(nv); r.view_status.resize(nv);
+  r.cam_f.resize(nc); r.cam_views.resize(nc); r.cam_status.resize(nc);
+  return r;
 }
 
 class ViCalibrator {

@@ -245,23 +245,26 @@ VC_HD void seed_eig9(const W& w, const double* acc, double* Hn) {
 
 VC_HD bool seed_used(const char* use, size_t i) { return !use || use[i]; }
 
-// rough pose of the used corners: normalised DLT  s [x y 1]^T = H [X Y 1]^T, then seed_pose_from_H
-template <class W>
-VC_HD bool seed_dlt_pose(const W& w, const SeedView& s, const char* use, double* T) {
+// H (row-major, up to scale) of the used points by the normalised DLT  s [x y 1]^T = H [X Y 1]^T: Hartley normalisation (5 + 2 sums), the 45 sums
+// of the upper triangle of A^T A, seed_eig9, de-normalisation.  pt(i, &X, &Y, &x, &y) gives point i of n and whether it is used; every lane gets
+// the same H.  *m_used (nullable) gets the number of used points.  false: fewer than 4 used points, or all of them on one spot.
+template <class W, class P>
+VC_HD bool seed_dlt_H(const W& w, int n, const P& pt, double* H, int* m_used = nullptr) {
   int m = 0;
   double mX = 0, mY = 0, mx = 0, my = 0;
-  for (int i = w.lane; i < s.n; i += W::kLanes) {
-    const double x = s.xy[2 * (size_t)i], y = s.xy[2 * (size_t)i + 1];
-    if (seed_used(use, i) && x == x) { ++m; mX += s.pw[3 * (size_t)i]; mY += s.pw[3 * (size_t)i + 1]; mx += x; my += y; }
+  for (int i = w.lane; i < n; i += W::kLanes) {
+    double X, Y, x, y;
+    if (pt(i, &X, &Y, &x, &y)) { ++m; mX += X; mY += Y; mx += x; my += y; }
   }
   m = w.allsum(m);
+  if (m_used) *m_used = m;
   if (m < 4) return false;
   mX = w.allsum(mX) / m; mY = w.allsum(mY) / m; mx = w.allsum(mx) / m; my = w.allsum(my) / m;
   double dW = 0, dI = 0;
-  for (int i = w.lane; i < s.n; i += W::kLanes) {
-    const double x = s.xy[2 * (size_t)i], y = s.xy[2 * (size_t)i + 1];
-    if (seed_used(use, i) && x == x) {
-      const double a = s.pw[3 * (size_t)i] - mX, b = s.pw[3 * (size_t)i + 1] - mY, c = x - mx, d = y - my;
+  for (int i = w.lane; i < n; i += W::kLanes) {
+    double X, Y, x, y;
+    if (pt(i, &X, &Y, &x, &y)) {
+      const double a = X - mX, b = Y - mY, c = x - mx, d = y - my;
       dW += sqrt(a * a + b * b); dI += sqrt(c * c + d * d);
     }
   }
@@ -271,10 +274,10 @@ VC_HD bool seed_dlt_pose(const W& w, const SeedView& s, const char* use, double*
   double acc[45];
   VC_SEED_UNROLL
   for (int k = 0; k < 45; ++k) acc[k] = 0.0;
-  for (int i = w.lane; i < s.n; i += W::kLanes) {
-    const double xi = s.xy[2 * (size_t)i], yi = s.xy[2 * (size_t)i + 1];
-    if (!(seed_used(use, i) && xi == xi)) continue;
-    const double X = (s.pw[3 * (size_t)i] - mX) * sW, Y = (s.pw[3 * (size_t)i + 1] - mY) * sW, x = (xi - mx) * sI, y = (yi - my) * sI;
+  for (int i = w.lane; i < n; i += W::kLanes) {
+    double Xi, Yi, xi, yi;
+    if (!pt(i, &Xi, &Yi, &xi, &yi)) continue;
+    const double X = (Xi - mX) * sW, Y = (Yi - mY) * sW, x = (xi - mx) * sI, y = (yi - my) * sI;
     const double r1[9] = {-X, -Y, -1, 0, 0, 0, x * X, x * Y, x}, r2[9] = {0, 0, 0, -X, -Y, -1, y * X, y * Y, y};
     int k = 0;
   VC_SEED_UNROLL
@@ -287,13 +290,29 @@ VC_HD bool seed_dlt_pose(const W& w, const SeedView& s, const char* use, double*
   double Hn[9];
   seed_eig9(w, acc, Hn);                          // the eigenvector of the smallest eigenvalue
   // de-normalise: H = Ti^-1 Hn Tw with Tw = [sW 0 -sW mX; 0 sW -sW mY; 0 0 1], Ti likewise
-  double H[9];
-  {
-    const double Tw[9] = {sW, 0, -sW * mX, 0, sW, -sW * mY, 0, 0, 1}, TiInv[9] = {1 / sI, 0, mx, 0, 1 / sI, my, 0, 0, 1};
-    double tmp[9];
-    for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) { tmp[3 * i + j] = 0; for (int k = 0; k < 3; ++k) tmp[3 * i + j] += Hn[3 * i + k] * Tw[3 * k + j]; }
-    for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) { H[3 * i + j] = 0; for (int k = 0; k < 3; ++k) H[3 * i + j] += TiInv[3 * i + k] * tmp[3 * k + j]; }
+  const double Tw[9] = {sW, 0, -sW * mX, 0, sW, -sW * mY, 0, 0, 1}, TiInv[9] = {1 / sI, 0, mx, 0, 1 / sI, my, 0, 0, 1};
+  double tmp[9];
+  for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) { tmp[3 * i + j] = 0; for (int k = 0; k < 3; ++k) tmp[3 * i + j] += Hn[3 * i + k] * Tw[3 * k + j]; }
+  for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) { H[3 * i + j] = 0; for (int k = 0; k < 3; ++k) H[3 * i + j] += TiInv[3 * i + k] * tmp[3 * k + j]; }
+  return true;
+}
+
+// the used corners of a view for seed_dlt_H: target (X, Y) against the ideal pinhole coordinates kept in s.xy
+struct SeedPosePoints {
+  const SeedView& s;
+  const char* use;
+  VC_HD bool operator()(int i, double* X, double* Y, double* x, double* y) const {
+    *x = s.xy[2 * (size_t)i]; *y = s.xy[2 * (size_t)i + 1];
+    *X = s.pw[3 * (size_t)i]; *Y = s.pw[3 * (size_t)i + 1];
+    return seed_used(use, i) && *x == *x;
   }
+};
+
+// rough pose of the used corners: seed_dlt_H, then seed_pose_from_H
+template <class W>
+VC_HD bool seed_dlt_pose(const W& w, const SeedView& s, const char* use, double* T) {
+  double H[9];
+  if (!seed_dlt_H(w, s.n, SeedPosePoints{s, use}, H)) return false;
   return seed_pose_from_H(H, s.z0, T);
 }
 
@@ -493,6 +512,7 @@ struct SeedSerial {
   int lane = 0;
   double allsum(double x) const { return x; }
   int allsum(int x) const { return x; }
+  int allmin(int x) const { return x; }
   double bcast(double x, int) const { return x; }
   int bcast(int x, int) const { return x; }
 };

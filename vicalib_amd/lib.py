@@ -29,7 +29,7 @@ SYMBOLS = [
     "vc_get_biases", "vc_get_scale_factor", "vc_get_gravity", "vc_time_offset", "vc_mean_squared_error", "vc_get_camera_proj_rmse",
     "vc_get_num_iterations", "vc_num_imu_measurements", "vc_get_imu_measurements", "vc_get_integration_poses", "vc_print_results", "vc_write_camera_models", "vc_trace_len", "vc_get_trace", "vc_set_shard", "vc_get_stream", "vc_prepare",
     "vc_linearize", "vc_step_hold", "vc_shared_dim", "vc_run_iterations", "vc_download_state", "vc_evaluate", "vc_time_kernels", "vc_time_stages", "vc_get_imu_blocks", "vc_get_debug_stamps", "vc_num_observations", "vc_num_tiles",
-    "vc_init_frame_poses_pnp", "vc_pnp_planar", "vc_pnp_planar_ransac", "vc_set_pnp_ransac", "vc_pnp_planar_batch", "vc_time_pnp_planar_batch", "vc_set_pnp_device", "vc_rccl_unique_id", "vc_set_shard_rccl", "vc_shard_comm_create", "vc_set_shard_comm", "vc_shard_comm_destroy", "vc_allreduce_calls", "vc_shard_info", "vc_pass_paths", "vc_chain_order", "vc_last_error", "vc_get_imu_weights",
+    "vc_init_frame_poses_pnp", "vc_pnp_planar", "vc_pnp_planar_ransac", "vc_set_pnp_ransac", "vc_pnp_planar_batch", "vc_time_pnp_planar_batch", "vc_set_pnp_device", "vc_seed_focal_batch", "vc_time_seed_focal_batch","vc_rccl_unique_id", "vc_set_shard_rccl", "vc_shard_comm_create", "vc_set_shard_comm", "vc_shard_comm_destroy", "vc_allreduce_calls", "vc_shard_info", "vc_pass_paths", "vc_chain_order", "vc_last_error", "vc_get_imu_weights",
     "vc_solution_covariance_dim", "vc_get_solution_covariance", "vc_get_solution_covariance_names",
     "vc_target_make_pattern", "vc_target_find",
     "vc_report_compute", "vc_report_num_corners", "vc_report_corners", "vc_report_num_views", "vc_report_views", "vc_report_error_map", "vc_report_num_imu_blocks", "vc_report_imu", "vc_time_report_sweeps",
@@ -137,6 +137,53 @@ def pnp_planar_batch(models, params, view_off, p_w, p_c, iterations=0, tol_px=0.
                                  C.c_double(tol_px), T.ctypes.data_as(C.c_void_p), rms.ctypes.data_as(C.c_void_p), n_in.ctypes.data_as(C.c_void_p),
                                  flags.ctypes.data_as(C.c_void_p), status.ctypes.data_as(C.c_void_p)), "pnp_planar_batch")
     return dict(T_cw=T, rms=rms, n_inliers=n_in, inlier=flags[:len(p_w)].astype(bool), status=status[:n])
+
+
+def _focal_batch_arrays(view_cam, cam_pp, cam_radius, view_off, p_w, p_c):
+    cam = np.ascontiguousarray(view_cam, dtype=np.int32).reshape(-1)
+    pp = np.ascontiguousarray(cam_pp, dtype=np.float64).reshape(-1, 2)
+    rad = np.ascontiguousarray(cam_radius, dtype=np.float64).reshape(-1)
+    off = np.ascontiguousarray(view_off, dtype=np.int32).reshape(-1)
+    p_w = np.ascontiguousarray(p_w, dtype=np.float64).reshape(-1, 3); p_c = np.ascontiguousarray(p_c, dtype=np.float64).reshape(-1, 2)
+    if len(off) != len(cam) + 1 or len(rad) != len(pp):
+        raise VicalibError("seed_focal_batch: view_off needs one entry more than view_cam, cam_radius one per row of cam_pp")
+    pad = lambda a, shape, dt: a if len(a) else np.zeros(shape, dtype=dt)
+    return cam, pp, rad, off, pad(p_w, (1, 3), np.float64), pad(p_c, (1, 2), np.float64), pad(cam, 1, np.int32)
+
+
+def seed_focal_batch(view_cam, cam_pp, cam_radius, view_off, p_w, p_c, min_corners=4, max_fit_px=0.0, min_tilt_deg=5.0, device=0, out=None):
+    """The focal length of every camera from its views of the planar target, on the device (vc_seed_focal_batch).  view_cam: the camera of
+    every view; cam_pp [n_cams, 2]: the assumed principal points; cam_radius [n_cams]: the corners used lie within that many pixels of it
+    (<= 0: all); view v owns corners view_off[v] .. view_off[v+1]-1 of p_w / p_c.  Returns view_H [n, 3, 3], view_rows [n, 4] (c1 d1 c2 d2),
+    view_f, view_fit_px, view_used, view_status, cam_f, cam_views, cam_status.  `out` may hold pre-filled view_H / view_rows / view_f /
+    view_fit_px / view_used / cam_f arrays: a refused view or camera leaves its rows as they were (the default fill is NaN, 0 for view_used)."""
+    L = load()
+    cam, pp, rad, off, p_w, p_c, cam_arg = _focal_batch_arrays(view_cam, cam_pp, cam_radius, view_off, p_w, p_c)
+    n, nc = len(cam), len(rad)
+    out = dict(out or {})
+    H = out.get("view_H", np.full((n, 3, 3), np.nan)); rows = out.get("view_rows", np.full((n, 4), np.nan)); f = out.get("view_f", np.full(n, np.nan))
+    fit = out.get("view_fit_px", np.full(n, np.nan)); used = out.get("view_used", np.zeros(n, dtype=np.int32)); cam_f = out.get("cam_f", np.full(nc, np.nan))
+    for a in (H, rows, f, fit, cam_f):
+        assert a.dtype == np.float64 and a.flags.c_contiguous
+    assert used.dtype == np.int32
+    status = np.full(max(n, 1), -1, dtype=np.int32); cam_views = np.zeros(max(nc, 1), dtype=np.int32); cam_status = np.full(max(nc, 1), -1, dtype=np.int32)
+    keep = [np.zeros(1) if a.size == 0 else a for a in (H, rows, f, fit, cam_f)] + [np.zeros(1, dtype=np.int32) if used.size == 0 else used]
+    ip = lambda a: a.ctypes.data_as(C.c_void_p)
+    _check(L.vc_seed_focal_batch(int(device), n, ip(cam_arg), nc, _d(pp), _d(rad), ip(off), _d(p_w), _d(p_c), int(min_corners), C.c_double(max_fit_px),
+                                 C.c_double(min_tilt_deg), _d(keep[0]), _d(keep[1]), _d(keep[2]), _d(keep[3]), ip(keep[5]), ip(status), _d(keep[4]), ip(cam_views),
+                                 ip(cam_status)), "seed_focal_batch")
+    return dict(view_H=H, view_rows=rows, view_f=f, view_fit_px=fit, view_used=used, view_status=status[:n], cam_f=cam_f, cam_views=cam_views[:nc],
+                cam_status=cam_status[:nc])
+
+
+def time_seed_focal_batch(view_cam, cam_pp, cam_radius, view_off, p_w, p_c, min_corners=4, max_fit_px=0.0, min_tilt_deg=5.0, device=0, reps=10):
+    """mean time in ms of the two kernels of seed_focal_batch alone on that input (vc_time_seed_focal_batch: HIP events, runs back to back)"""
+    cam, pp, rad, off, p_w, p_c, cam_arg = _focal_batch_arrays(view_cam, cam_pp, cam_radius, view_off, p_w, p_c)
+    ms = C.c_double(0)
+    ip = lambda a: a.ctypes.data_as(C.c_void_p)
+    _check(load().vc_time_seed_focal_batch(int(device), len(cam), ip(cam_arg), len(rad), _d(pp), _d(rad), ip(off), _d(p_w), _d(p_c), int(min_corners),
+                                           C.c_double(max_fit_px), C.c_double(min_tilt_deg), int(reps), C.byref(ms)), "time_seed_focal_batch")
+    return ms.value
 
 
 def load():
