@@ -159,6 +159,13 @@ static void DefineFlags() {
   Define("uncertainty_fit_radius", "double", "0.5", "The absorbed rotation is fitted over the samples within this fraction of the half-diagonal of the image centre (<= 0: no rotation is removed).");
   Define("uncertainty_rings", "int32", "8", "Rings of equal width in normalised radius in uncertainty_summary.csv, 1 ... 64.");
   Define("uncertainty_noise", "double", "0", "Detection noise in px per coordinate that scales the covariance; 0 = the camera's own reprojection RMSE.");
+  Define("stereo_uncertainty_dir", "string", "", "Directory for stereo_uncertainty.csv (depth, x, y, sigma_dv, sigma_d, sigma_Z, flags per lattice sample of the rectified image of the "
+         "first camera and depth: what the covariance of the calibration implies for the row misalignment and the disparity in px and for the depth in m) and "
+         "stereo_uncertainty_summary.csv, written behind a calibration.  The rectified camera is the one -rectify_dir uses: fitted at -rectify_alpha, of the first camera's size.");
+  Define("stereo_uncertainty_cams", "string", "0,1", "The two cameras of -stereo_uncertainty_dir: a,b.");
+  Define("stereo_uncertainty_depths", "string", "0.5,1,2,5", "Depths in m of the map, 1 ... 8 of them, each above 0.");
+  Define("stereo_uncertainty_grid", "string", "64x48", "Lattice of the stereo uncertainty map, GXxGY: 2 ... image width by 2 ... image height, at most 2^22 samples.");
+  Define("stereo_uncertainty_noise", "double", "0", "Detection noise in px per coordinate that scales the covariance; 0 = the mean of the two cameras' reprojection RMSE.");
   Define("select_views", "string", "", "Behind a calibration, select this many of the calibrated frames by greedy D-optimal view selection (the log-determinant of the "
          "information on the shared vision parameters, every frame's pose marginalised) with the result's cameras and poses; needs -select_dir and -gpus 1.");
   Define("select_dir", "string", "", "Directory for selected_views.csv (rank, frame, gain, cum, share), select_frames.csv (frame, status, corners, behind, first-round gain) and, with "
@@ -1385,6 +1392,121 @@ static bool UncertaintyOutputs(const std::vector<vic::CameraAndPose>& cams, cons
   return ok;
 }
 
+// ---- -stereo_uncertainty_dir: the row and depth uncertainty of two cameras just calibrated, mapped over the rectified image (vc_stereo_uncertainty*)
+struct StereoUncertaintyOptions { std::string dir; int a = 0, b = 1, gx = 64, gy = 48; std::vector<double> depths; double noise = 0.0, alpha = 0.0; };
+static bool StereoUncertaintyFlags(StereoUncertaintyOptions* o, std::string* err) {
+  o->dir = FlagString("stereo_uncertainty_dir");
+  if (!ParseCompareGrid(FlagString("stereo_uncertainty_grid"), &o->gx, &o->gy)) { *err = "illegal value '" + FlagString("stereo_uncertainty_grid") + "' specified for flag 'stereo_uncertainty_grid': expected GXxGY, both at least 2, at most 2^22 samples"; return false; }
+  char tail = 0;
+  if (std::sscanf(FlagString("stereo_uncertainty_cams").c_str(), "%d,%d%c", &o->a, &o->b, &tail) != 2 || o->a < 0 || o->b < 0 || o->a == o->b) {
+    *err = "illegal value '" + FlagString("stereo_uncertainty_cams") + "' specified for flag 'stereo_uncertainty_cams': expected a,b, two different cameras";
+    return false;
+  }
+  std::stringstream ss(FlagString("stereo_uncertainty_depths"));
+  std::string item;
+  while (std::getline(ss, item, ',')) {
+    char* end = nullptr;
+    const double z = std::strtod(item.c_str(), &end);
+    if (item.empty() || end != item.c_str() + item.size() || !(z > 0.0) || !(z <= 1e300)) { o->depths.clear(); break; }
+    o->depths.push_back(z);
+  }
+  if (o->depths.empty() || o->depths.size() > 8) { *err = "illegal value '" + FlagString("stereo_uncertainty_depths") + "' specified for flag 'stereo_uncertainty_depths': expected 1 ... 8 depths above 0, separated by commas"; return false; }
+  o->noise = FlagDouble("stereo_uncertainty_noise");
+  if (!(o->noise >= 0.0 && o->noise <= 1e6)) { *err = "illegal value for flag 'stereo_uncertainty_noise': expected 0 (the two cameras' mean RMSE) or a noise in px above 0"; return false; }
+  o->alpha = FlagDouble("rectify_alpha");
+  if (!o->dir.empty() && !(o->alpha >= 0.0 && o->alpha <= 1.0)) { *err = "illegal value for flag 'rectify_alpha': expected 0 ... 1"; return false; }
+  return true;
+}
+// cov: the solution covariance (dim x dim, blocks q_ck (4), p_ck (3), params (nk) per camera); cams: model, params, size and pose of every camera;
+// rmse: the cameras' reprojection RMSE per coordinate.  Writes the files of -stereo_uncertainty_dir and prints one line per depth.
+static bool StereoUncertaintyOutputs(const std::vector<vic::CameraAndPose>& cams, const std::vector<double>& cov, int dim, const std::vector<double>& rmse,
+                                     const StereoUncertaintyOptions& o, int device, std::string* err) {
+  const vic::CameraAndPose& A = cams[o.a];
+  const vic::CameraAndPose& B = cams[o.b];
+  std::vector<int> idx;
+  for (int s = 0; s < 2; ++s) {
+    const int c = s ? o.b : o.a;
+    int first = 0;
+    for (int k = 0; k < c; ++k) first += 7 + (int)cams[k].params.size();
+    for (int k = 0; k < 7 + (int)cams[c].params.size(); ++k) idx.push_back(first + k);
+    if (first + 7 + (int)cams[c].params.size() > dim) { *err = "the solution covariance has no blocks for camera " + std::to_string(c); return false; }
+  }
+  const size_t m = idx.size();
+  std::vector<double> block(m * m);
+  for (size_t r = 0; r < m; ++r) for (size_t q = 0; q < m; ++q) block[r * m + q] = cov[(size_t)idx[r] * dim + idx[q]];
+  const double noise = o.noise > 0.0 ? o.noise : 0.5 * (rmse[o.a] + rmse[o.b]);
+  const int nd = (int)o.depths.size();
+  const size_t n = (size_t)o.gx * o.gy;
+  std::vector<double> var(3 * n * nd);
+  std::vector<unsigned char> fl(n * nd);
+  std::vector<vic::StereoUncertaintySummary> sum((size_t)nd);
+  double dl[4] = {0, 0, 0, 0}, baseline = 0.0, pose_var[7] = {0, 0, 0, 0, 0, 0, 0};
+  vc_stereo_uncertainty* h = nullptr;
+  int q = vc_stereo_uncertainty_create(device, A.model, A.params.data(), (int)A.params.size(), A.width, A.height, A.T_ck.data(), B.model, B.params.data(), (int)B.params.size(),
+                                       B.width, B.height, B.T_ck.data(), nullptr, A.width, A.height, o.alpha, o.gx, o.gy, &h);
+  if (q == VC_OK) q = vc_stereo_uncertainty_run(h, block.data(), noise, o.depths.data(), nd);
+  if (q == VC_OK) q = vc_stereo_uncertainty_get_map(h, var.data(), fl.data());
+  for (int k = 0; k < nd && q == VC_OK; ++k)
+    q = vc_stereo_uncertainty_summary(h, k, &sum[k].count, &sum[k].invalid, &sum[k].sum_var_dv, &sum[k].sum_var_d, &sum[k].sum_var_z, &sum[k].max_var_dv, &sum[k].worst);
+  if (q == VC_OK) q = vc_stereo_uncertainty_get_pose_sigma(h, pose_var);
+  if (q == VC_OK) q = vc_stereo_uncertainty_get(h, nullptr, nullptr, dl, &baseline, nullptr);
+  vc_stereo_uncertainty_destroy(h);
+  if (q != VC_OK) {
+    *err = q == VC_ERR_NUMERIC ? "the two cameras' centres coincide, or no destination camera can be fitted"
+         : q == VC_ERR_UNSUPPORTED ? "the baseline is vertical: column rectification is not supported"
+         : q == VC_ERR_BAD_ARG && !(noise > 0.0) ? "the noise is 0 (a reprojection RMSE of 0: give -stereo_uncertainty_noise)"
+         : "the stereo uncertainty map failed (status " + std::to_string(q) + ")";
+    return false;
+  }
+  struct stat st;
+  if (mkdir(o.dir.c_str(), 0777) != 0 && !(stat(o.dir.c_str(), &st) == 0 && S_ISDIR(st.st_mode))) { *err = "cannot create the directory " + o.dir; return false; }      // (one level)
+  FILE* fm = std::fopen((o.dir + "/stereo_uncertainty.csv").c_str(), "w");
+  FILE* fs = fm ? std::fopen((o.dir + "/stereo_uncertainty_summary.csv").c_str(), "w") : nullptr;
+  if (!fs) { if (fm) std::fclose(fm); *err = "cannot write into " + o.dir; return false; }
+  auto sigma = [](double v) { return std::sqrt(v > 0.0 ? v : v == v ? 0.0 : v); };          // (a rounding below zero is zero; NaN stays)
+  auto at_x = [&](long long s) { return (double)((s % o.gx) * (A.width - 1)) / (o.gx - 1); };
+  auto at_y = [&](long long s) { return (double)((s / o.gx) * (A.height - 1)) / (o.gy - 1); };
+  std::fprintf(fm, "depth,x,y,sigma_dv,sigma_d,sigma_Z,flags\n");
+  for (int k = 0; k < nd; ++k)
+    for (size_t s = 0; s < n; ++s) {
+      const double* t = &var[3 * (k * n + s)];
+      std::fprintf(fm, "%.17g,%.17g,%.17g,%.17g,%.17g,%.17g,%d\n", o.depths[k], at_x((long long)s), at_y((long long)s), sigma(t[0]), sigma(t[1]), sigma(t[2]), (int)fl[k * n + s]);
+    }
+  std::fclose(fm);
+  std::fprintf(fs, "depth,count,invalid,rms_sigma_dv,max_sigma_dv,worst_x,worst_y,rms_sigma_d,rms_sigma_z_over_z\n");
+  for (int k = 0; k < nd; ++k) {
+    const vic::StereoUncertaintySummary& s = sum[k];
+    const double c = s.count > 0 ? (double)s.count : 1.0;
+    std::fprintf(fs, "%.17g,%lld,%lld,%.17g,%.17g,%.17g,%.17g,%.17g,%.17g\n", o.depths[k], s.count, s.invalid, sigma(s.sum_var_dv / c), sigma(s.max_var_dv),
+                 s.worst >= 0 ? at_x(s.worst) : -1.0, s.worst >= 0 ? at_y(s.worst) : -1.0, sigma(s.sum_var_d / c), sigma(s.sum_var_z / c) / o.depths[k]);
+    if (s.worst >= 0)
+      std::printf("cameras %d,%d at %.4g m: row misalignment sigma %.4g px rms, worst %.4g px at (%.1f, %.1f); disparity sigma %.4g px rms; depth sigma %.4g %% rms over %lld samples\n",
+                  o.a, o.b, o.depths[k], sigma(s.sum_var_dv / c), sigma(s.max_var_dv), at_x(s.worst), at_y(s.worst), sigma(s.sum_var_d / c), 100.0 * sigma(s.sum_var_z / c) / o.depths[k], s.count);
+    else std::printf("cameras %d,%d at %.4g m: stereo uncertainty: no valid sample\n", o.a, o.b, o.depths[k]);
+  }
+  // the second table: the pair's geometry and the noise; the third: the two cameras that were mapped; the fourth: their covariance, row by row
+  // (q_a p_a K_a q_b p_b K_b)
+  std::fprintf(fs, "baseline,sigma_baseline,noise_px,fu,fv,u0,v0,width,height\n");
+  std::fprintf(fs, "%.17g,%.17g,%.17g,%.17g,%.17g,%.17g,%.17g,%d,%d\n", baseline, sigma(pose_var[6]), noise, dl[0], dl[1], dl[2], dl[3], A.width, A.height);
+  std::fprintf(fs, "camera,qx,qy,qz,qw,tx,ty,tz,params\n");
+  for (int s = 0; s < 2; ++s) {
+    const vic::CameraAndPose& cm = s ? B : A;
+    std::fprintf(fs, "%d", s ? o.b : o.a);
+    for (int k = 0; k < 7; ++k) std::fprintf(fs, ",%.17g", cm.T_ck.data()[k]);
+    for (double p : cm.params) std::fprintf(fs, ",%.17g", p);
+    std::fprintf(fs, "\n");
+  }
+  std::fprintf(fs, "row,covariance\n");
+  for (size_t r = 0; r < m; ++r) {
+    std::fprintf(fs, "%zu", r);
+    for (size_t c = 0; c < m; ++c) std::fprintf(fs, ",%.17g", block[r * m + c]);
+    std::fprintf(fs, "\n");
+  }
+  std::fclose(fs);
+  std::printf("cameras %d,%d: baseline %.6g m, sigma %.3g m, noise %.4g px\n", o.a, o.b, baseline, sigma(pose_var[6]), noise);
+  return true;
+}
+
 // ---- -select_views K -select_dir DIR: the most informative of the calibrated frames (vc_selector*) -----------------------------------------
 struct SelectOptions { int k = 0; std::string dir; double prior = 1e-6; std::vector<long> start; };
 static bool SelectFlags(SelectOptions* o, std::string* err) {
@@ -1517,6 +1639,8 @@ int main(int argc, char** argv) {
   }
   UncertaintyOptions uncertainty;
   if (!UncertaintyFlags(&uncertainty, &err)) { std::fprintf(stderr, "ERROR: %s\n", err.c_str()); return 1; }
+  StereoUncertaintyOptions stereo_uncertainty;
+  if (!StereoUncertaintyFlags(&stereo_uncertainty, &err)) { std::fprintf(stderr, "ERROR: %s\n", err.c_str()); return 1; }
   SelectOptions select;
   if (!SelectFlags(&select, &err)) { std::fprintf(stderr, "ERROR: %s\n", err.c_str()); return 1; }
   // ---- -compare_models a.xml,b.xml: file against file, nothing is calibrated; -compare_to b.xml: read now, compared behind the results
@@ -1688,6 +1812,12 @@ int main(int argc, char** argv) {
     if (!FlagBool("calibrate_intrinsics")) { std::fprintf(stderr, "F -uncertainty_dir needs -calibrate_intrinsics: fixed intrinsics have no covariance\n"); return 1; }
     for (size_t c = 0; c < input_cameras.size(); ++c)
       if (uncertainty.gx > input_cameras[c].width || uncertainty.gy > input_cameras[c].height) { std::fprintf(stderr, "F camera %zu: -uncertainty_grid exceeds the image\n", c); return 1; }
+  }
+  if (!stereo_uncertainty.dir.empty()) {
+    const StereoUncertaintyOptions& su = stereo_uncertainty;
+    if ((size_t)su.a >= n_cam || (size_t)su.b >= n_cam) { std::fprintf(stderr, "E illegal value '%s' specified for flag 'stereo_uncertainty_cams': expected two cameras below %zu\n", FlagString("stereo_uncertainty_cams").c_str(), n_cam); return 1; }
+    if (!FlagBool("calibrate_intrinsics")) { std::fprintf(stderr, "F -stereo_uncertainty_dir needs -calibrate_intrinsics: fixed intrinsics have no covariance\n"); return 1; }
+    if (su.gx > input_cameras[su.a].width || su.gy > input_cameras[su.a].height) { std::fprintf(stderr, "F -stereo_uncertainty_grid exceeds the image of camera %d\n", su.a); return 1; }
   }
   if (!compare_b.empty() && !ComparableRigs(input_cameras, compare_b, compare, &err)) { std::fprintf(stderr, "F -compare_to: %s\n", err.c_str()); return 1; }      // before any solve
 
@@ -2109,8 +2239,24 @@ int main(int argc, char** argv) {
     if (covs[0].empty()) { std::fprintf(stderr, "E uncertainty map failed: the solution covariance cannot be computed\n"); uncertainty_failed = true; }
     else if (!UncertaintyOutputs(a, covs[0], dims[0], rmse, uncertainty, (int)FlagInt("device"), &err)) { std::fprintf(stderr, "E uncertainty map failed: %s\n", err.c_str()); uncertainty_failed = true; }
   }
+  bool stereo_uncertainty_failed = false;
+  if (!stereo_uncertainty.dir.empty()) {                 // -stereo_uncertainty_dir: the covariance at the result (collective when the frames are sharded), mapped for the pair
+    std::vector<std::vector<double>> covs((size_t)n_gpus);
+    std::vector<int> dims((size_t)n_gpus, 0);
+    std::vector<std::thread> th;
+    for (int r = 0; r < n_gpus; ++r) th.emplace_back([&, r] { covs[r] = cals[r]->GetSolutionCovariance(&dims[r]); });
+    for (auto& t : th) t.join();
+    std::vector<vic::CameraAndPose> a;
+    for (size_t c = 0; c < n_cam; ++c) {
+      vic::CameraAndPose now = cal.GetCamera(c);
+      now.model = input_cameras[c].model; now.width = input_cameras[c].width; now.height = input_cameras[c].height;
+      a.push_back(now);
+    }
+    if (covs[0].empty()) { std::fprintf(stderr, "E stereo uncertainty map failed: the solution covariance cannot be computed\n"); stereo_uncertainty_failed = true; }
+    else if (!StereoUncertaintyOutputs(a, covs[0], dims[0], rmse, stereo_uncertainty, (int)FlagInt("device"), &err)) { std::fprintf(stderr, "E stereo uncertainty map failed: %s\n", err.c_str()); stereo_uncertainty_failed = true; }
+  }
   bool select_failed = false;
-  if (select.k > 0) {                                    // -select_views: the most informative of the calibrated frames, at the result
+  if (select.k > 0) {                                  // -select_views: the most informative of the calibrated frames, at the result
     try {
       if (!SelectOutputs(cal, frame_ids, held_ids, select_held, select, &err)) { std::fprintf(stderr, "E view selection failed: %s\n", err.c_str()); select_failed = true; }
     } catch (const std::exception& e) { std::fprintf(stderr, "E view selection failed: %s\n", e.what()); select_failed = true; }
@@ -2177,8 +2323,9 @@ int main(int argc, char** argv) {
   if (compare_failed) std::fprintf(stderr, "E -compare_to: the comparison's files are incomplete (exit status %d)\n", success ? 1 : 2);
   if (convert_failed) std::fprintf(stderr, "E -convert_to: the converted rig is incomplete (exit status %d)\n", success ? 1 : 2);
   if (uncertainty_failed) std::fprintf(stderr, "E -uncertainty_dir: the uncertainty map's files are incomplete (exit status %d)\n", success ? 1 : 2);
+  if (stereo_uncertainty_failed) std::fprintf(stderr, "E -stereo_uncertainty_dir: the stereo uncertainty map's files are incomplete (exit status %d)\n", success ? 1 : 2);
   if (select_failed) std::fprintf(stderr, "E -select_views: the selection's files are incomplete (exit status %d)\n", success ? 1 : 2);
   if (register_failed) std::fprintf(stderr, "E -register_depth: the registered images are incomplete (exit status %d)\n", success ? 1 : 2);
   if (depthcal_failed) std::fprintf(stderr, "E -depthcal_depth: the depth correction is incomplete (exit status %d)\n", success ? 1 : 2);
-  return success ? ((undistort_failed || rectify_failed || compare_failed || convert_failed || uncertainty_failed || select_failed || register_failed || depthcal_failed) ? 1 : 0) : 2;
+  return success ? ((undistort_failed || rectify_failed || compare_failed || convert_failed || uncertainty_failed || stereo_uncertainty_failed || select_failed || register_failed || depthcal_failed) ? 1 : 0) : 2;
 }

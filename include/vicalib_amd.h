@@ -657,6 +657,57 @@ int vc_uncertainty_rings(vc_uncertainty* u, int n_rings, long long* count, long 
  * and C, [2] the map sweep, each with its reduction. */
 int vc_time_uncertainty(vc_uncertainty* u, int reps, double out_ms[3]);
 
+/* ---- mapping the row and depth uncertainty of a calibrated stereo pair ---------------------------------------------------------------
+ * By how many pixels will the rows of the rectified images disagree, and where?  How wrong is a depth of 2 m?  Cameras A and B (model,
+ * intrinsics, size, T_ck), the rectified frames of vc_stereo_rectify_rotations and a destination pinhole dst_linear of dst_w x dst_h that
+ * is held FIXED (NULL = vc_stereo_fit_linear at alpha, as vc_rectifier_create).  A sample is a point (x, y) of the comparer's lattice of
+ * grid_x x grid_y points over the rectified image of A together with a depth Z > 0: the point ((x - u0) Z / fu, (y - v0) Z / fv, Z) of A's
+ * rectified frame, seen by the two cameras at pixels p_a and p_b.  A user who holds a slightly different calibration pushes those pixels
+ * through the rectifier's arithmetic (vc_rectify_check) and gets the row misalignment dv, the disparity d and the depth Z off by a shift that
+ * is linear in the calibration's error; with the covariance of the calibration that shift has the variances (var_dv, var_d, var_Z) in
+ * px^2, px^2 and m^2, which is what the map stores per sample and depth.  cov is the joint covariance of the pair in the layout a
+ * two-camera rig's vc_get_solution_covariance has -- q_a (4) p_a (3) K_a q_b (4) p_b (3) K_b, n = 14 + nk_a + nk_b, row-major --, multiplied
+ * by sigma_px^2 before it enters the sweep: doubling sigma_px quadruples every output bit for bit.  The pose part goes through W, the 7 x 12
+ * derivative of (w_a, w_b, baseline) -- R_ds moving as exp([w]x) R_ds -- with respect to (w_ck_a, dp_a, w_ck_b, dp_b), the poses moving as
+ * q <- q * exp(w_ck), p <- p + dp (vc_stereo_pose_jacobian; host code, the statuses of vc_stereo_rectify_rotations).
+ * flags: bit 0 the point is not seen by A (behind the camera unless kb4, or its pixel outside [0, w - 1] x [0, h - 1]), bit 1 the same for
+ * B, bit 2 the sample is INVALID -- either of the two, or a variance that is not finite --: its triple is NaN and it enters no sum.
+ * What the map does NOT say: dst_linear is held fixed (a user who refits it moves every pixel by more), the two images' noise and the
+ * matching error are not in it, and like any covariance it assumes the noise model of the solve.
+ * A run takes 1 to 8 depths, each > 0 and finite; the planes are swept one after the other on the handle's stream with one
+ * synchronisation per run, and a plane's bits do not depend on the planes beside it.  A handle is single-threaded with a stream of its
+ * own; nothing is launched before the first run; no CPU fallback.  Argument errors are VC_ERR_BAD_ARG; they, the rotations' and the fit's
+ * statuses come before the device is looked for (VC_ERR_NO_DEVICE).  Every sum is formed in a fixed order that depends on the lattice
+ * alone: two runs, and two handles, give the same bits.  Any output pointer may be NULL. */
+typedef struct vc_stereo_uncertainty vc_stereo_uncertainty;
+int vc_stereo_pose_jacobian(const double T_ck_a[7], const double T_ck_b[7], double W[84]);
+int vc_stereo_uncertainty_create(int device, int model_a, const double* params_a, int nparams_a, int w_a, int h_a, const double T_ck_a[7], int model_b,
+                                 const double* params_b, int nparams_b, int w_b, int h_b, const double T_ck_b[7], const double dst_linear[4], int dst_w, int dst_h,
+                                 double alpha, int grid_x, int grid_y, vc_stereo_uncertainty** out);
+/* the same for cameras cam_a and cam_b of a calibrator as vc_get_camera returns them, on the calibrator's device, with the pair's rows and
+ * columns of vc_get_solution_covariance at the current state kept as the handle's covariance: collective on a sharded calibrator like that
+ * call, whose status is handed on (VC_ERR_NUMERIC included).  VC_ERR_BAD_ARG with fixed intrinsics: no intrinsics blocks then. */
+int vc_stereo_uncertainty_create_for_cameras(vc_calibrator* h, int cam_a, int cam_b, const double dst_linear[4], int dst_w, int dst_h, double alpha, int grid_x,
+                                             int grid_y, vc_stereo_uncertainty** out);
+void vc_stereo_uncertainty_destroy(vc_stereo_uncertainty* u);
+/* the handle's geometry: the rectifying rotations, the destination pinhole, the signed baseline and W */
+int vc_stereo_uncertainty_get(vc_stereo_uncertainty* u, double R_ds_a[9], double R_ds_b[9], double dst_linear[4], double* baseline, double W[84]);
+/* cov: n x n, NULL = the calibrator's (VC_ERR_BAD_ARG on a handle without one).  VC_ERR_BAD_ARG: an entry of cov that is not finite, cov
+ * not symmetric to 1e-12 max |diag|, a negative diagonal entry, sigma_px not > 0 and finite, n_depths outside [1, 8], a depth that is not
+ * > 0 and finite.  A refused run leaves nothing to read. */
+int vc_stereo_uncertainty_run(vc_stereo_uncertainty* u, const double* cov, double sigma_px, const double* depths, int n_depths);
+/* The readers below return VC_ERR_BAD_ARG before a successful run. */
+int vc_stereo_uncertainty_get_map(vc_stereo_uncertainty* u, double* var /* n_depths x grid_y x grid_x x 3 */, unsigned char* flags /* n_depths x grid_y x grid_x */);
+/* of depth plane `plane` of the last run, over its valid samples: the three sums of variances and the largest var_dv with its sample -- the
+ * lowest among equal ones, -1 (and max_var_dv 0) without a valid sample */
+int vc_stereo_uncertainty_summary(vc_stereo_uncertainty* u, int plane, long long* count, long long* invalid, double* sum_var_dv, double* sum_var_d, double* sum_var_z,
+                                  double* max_var_dv, long long* worst);
+/* sigma_px^2 W Cov W^T of the last run, its diagonal: the variances of w_a (3, rad^2), of w_b (3) and of the baseline (m^2) */
+int vc_stereo_uncertainty_get_pose_sigma(vc_stereo_uncertainty* u, double var[7]);
+/* HIP events on the handle's stream like vc_time_compare, after a run: average ms of `reps` launches of [0] the two side sweeps of one depth
+ * plane, [1] the map sweep with its reduction. */
+int vc_time_stereo_uncertainty(vc_stereo_uncertainty* u, int reps, double out_ms[2]);
+
 /* ---- view selection: which frames carry the information? -----------------------------------------------------------------------------
  * Greedy D-optimal selection over candidate frames of a rig of up to 8 cameras.  Inputs are where the target was seen, not what was
  * measured: per camera a model, intrinsics, T_ck and the solver's flags (1 rotation free, 2 translation free, 4 intrinsics free); per

@@ -510,6 +510,66 @@ class Uncertainty {
   int nk_ = 0, gx_ = 0, gy_ = 0;
 };
 
+// The row and depth uncertainty of a calibrated stereo pair mapped over its rectified image (vc_stereo_uncertainty*): per lattice sample and
+// depth the variances of the row misalignment (px^2), the disparity (px^2) and the depth (m^2) that the joint covariance of the pair implies
+// for pixels pushed through the rectifier's arithmetic.  The destination pinhole is held fixed.
+struct StereoUncertaintySummary { long long count = 0, invalid = 0, worst = -1; double sum_var_dv = 0, sum_var_d = 0, sum_var_z = 0, max_var_dv = 0; };
+class StereoUncertainty {
+ public:
+  // dst.fu_fv_u0_v0 all zero: fitted at alpha (vc_stereo_fit_linear); dst.width / height are the destination size.  Run needs a covariance.
+  StereoUncertainty(const CameraAndPose& a, const CameraAndPose& b, const LinearCamera& dst, int grid_x, int grid_y, double alpha = 0.0, int device = 0)
+      : gx_(grid_x), gy_(grid_y) {
+    vc_checked(vc_stereo_uncertainty_create(device, a.model, a.params.data(), (int)a.params.size(), a.width, a.height, a.T_ck.data(), b.model, b.params.data(),
+                                            (int)b.params.size(), b.width, b.height, b.T_ck.data(), Given(dst), dst.width, dst.height, alpha, grid_x, grid_y, &u_),
+               "StereoUncertainty");
+  }
+  // the calibrator's cameras with the pair's rows and columns of the solution covariance at the current state
+  StereoUncertainty(ViCalibrator& cal, int cam_a, int cam_b, const LinearCamera& dst, int grid_x, int grid_y, double alpha = 0.0) : gx_(grid_x), gy_(grid_y) {
+    vc_checked(vc_stereo_uncertainty_create_for_cameras(cal.handle(), cam_a, cam_b, Given(dst), dst.width, dst.height, alpha, grid_x, grid_y, &u_), "StereoUncertainty");
+  }
+  ~StereoUncertainty() { vc_stereo_uncertainty_destroy(u_); }
+  StereoUncertainty(const StereoUncertainty&) = delete;
+  StereoUncertainty& operator=(const StereoUncertainty&) = delete;
+  // host code, no device: W (7 x 12, row-major) = d(w_a, w_b, baseline) / d(w_ck_a, dp_a, w_ck_b, dp_b)
+  static std::array<double, 84> PoseJacobian(const Se3& T_ck_a, const Se3& T_ck_b) {
+    std::array<double, 84> W{};
+    vc_checked(vc_stereo_pose_jacobian(T_ck_a.data(), T_ck_b.data(), W.data()), "PoseJacobian");
+    return W;
+  }
+  // cov: n x n row-major in the layout q_a p_a K_a q_b p_b K_b, nullptr = the calibrator's; 1 to 8 depths
+  void Run(const double* cov, double sigma_px, const std::vector<double>& depths) {
+    n_depths_ = 0;
+    vc_checked(vc_stereo_uncertainty_run(u_, cov, sigma_px, depths.data(), (int)depths.size()), "Run");
+    n_depths_ = (int)depths.size();
+  }
+  // var: n_depths x gy x gx x 3 = (var_dv, var_d, var_Z), NaN at an invalid sample; flags: n_depths x gy x gx
+  void Map(std::vector<double>* var, std::vector<unsigned char>* flags) {
+    const size_t n = (size_t)gx_ * gy_ * (n_depths_ > 0 ? n_depths_ : 1);
+    var->resize(3 * n); flags->resize(n);
+    vc_checked(vc_stereo_uncertainty_get_map(u_, var->data(), flags->data()), "Map");
+  }
+  StereoUncertaintySummary Summary(int plane) {
+    StereoUncertaintySummary s;
+    vc_checked(vc_stereo_uncertainty_summary(u_, plane, &s.count, &s.invalid, &s.sum_var_dv, &s.sum_var_d, &s.sum_var_z, &s.max_var_dv, &s.worst), "Summary");
+    return s;
+  }
+  // the variances of w_a (3), w_b (3) and of the baseline at the last run's covariance and sigma_px
+  std::array<double, 7> PoseSigma() { std::array<double, 7> v{}; vc_checked(vc_stereo_uncertainty_get_pose_sigma(u_, v.data()), "PoseSigma"); return v; }
+  double Baseline() { double b = 0.0; vc_checked(vc_stereo_uncertainty_get(u_, nullptr, nullptr, nullptr, &b, nullptr), "Baseline"); return b; }
+  LinearCamera Destination(int dst_width, int dst_height) {
+    LinearCamera d; d.width = dst_width; d.height = dst_height;
+    vc_checked(vc_stereo_uncertainty_get(u_, nullptr, nullptr, d.fu_fv_u0_v0.data(), nullptr, nullptr), "Destination");
+    return d;
+  }
+  std::array<double, 2> Time(int reps = 20) { std::array<double, 2> ms{{0, 0}}; vc_checked(vc_time_stereo_uncertainty(u_, reps, ms.data()), "Time"); return ms; }
+  vc_stereo_uncertainty* handle() { return u_; }
+
+ private:
+  static const double* Given(const LinearCamera& d) { return (d.fu_fv_u0_v0[0] == 0.0 && d.fu_fv_u0_v0[1] == 0.0) ? nullptr : d.fu_fv_u0_v0.data(); }
+  vc_stereo_uncertainty* u_ = nullptr;
+  int gx_ = 0, gy_ = 0, n_depths_ = 0;
+};
+
 // Greedy D-optimal selection of the most informative views (vc_selector*): which candidate frames carry the information on the shared
 // vision parameters, every frame's pose marginalised.  At most 64 shared columns.
 struct Selection { std::vector<int> order; std::vector<double> gain, cum; double total = 0; };      // cum[k] / total: the share of the first k + 1 views

@@ -2,6 +2,7 @@
 // status codes; RCCL communicators; parity / timing hooks; solution covariance; results as text and cameras.xml.
 #include "vc_calibrator.hpp"
 #include "vc_uncertainty.hpp"
+#include "vc_stereo_uncertainty.hpp"
 #include "vc_seed.hpp"
 
 static int env_bit(const char* name) { const char* e = std::getenv(name); return (e && (e[0] == '0' || e[0] == '1')) ? e[0] - '0' : -1; }
@@ -455,6 +456,37 @@ int vc_uncertainty_create_for_camera(vc_calibrator* h, int c, int grid_x, int gr
   const int st = vc_uncertainty_create(h->device, cm.model, cm.K, cm.nk, cm.width, cm.height, grid_x, grid_y, &u);
   if (st != VC_OK) return st;
   vc::unc_attach_cov(u, block.data());
+  *out = u;
+  return VC_OK;
+}
+// a stereo uncertainty map (vc_stereo_uncertainty.hip) of cameras a and b as vc_get_camera returns them, on the calibrator's device, with the
+// pair's rows and columns of vc_get_solution_covariance at the current state in a two-camera rig's layout: q_a p_a K_a q_b p_b K_b
+int vc_stereo_uncertainty_create_for_cameras(vc_calibrator* h, int a, int b, const double dst_linear[4], int dst_w, int dst_h, double alpha, int grid_x, int grid_y,
+                                             vc_stereo_uncertainty** out) {
+  if (!h || !out || a < 0 || b < 0 || a == b || a >= (int)h->cams.size() || b >= (int)h->cams.size() || h->fix_intrinsics) return VC_ERR_BAD_ARG;
+  HostCam cm[2];
+  int first[2] = {0, 0};
+  {
+    std::lock_guard<std::mutex> lk(h->result_mutex);
+    cm[0] = h->cams[a]; cm[1] = h->cams[b];
+    for (int k = 0; k < a; ++k) first[0] += 7 + h->cams[k].nk;
+    for (int k = 0; k < b; ++k) first[1] += 7 + h->cams[k].nk;
+  }
+  const int n = vc_solution_covariance_dim(h);
+  if (n < first[0] + 7 + cm[0].nk || n < first[1] + 7 + cm[1].nk) return VC_ERR_BAD_ARG;
+  std::vector<int> idx;
+  for (int s = 0; s < 2; ++s) for (int k = 0; k < 7 + cm[s].nk; ++k) idx.push_back(first[s] + k);
+  std::vector<double> cov((size_t)n * n), block(idx.size() * idx.size());
+  int m = 0;
+  const int rc = vc_get_solution_covariance(h, cov.data(), n, &m);                  // (collective: before anything that can fail on one rank alone)
+  if (rc != VC_OK) return rc;
+  for (size_t r = 0; r < idx.size(); ++r)
+    for (size_t s = 0; s < idx.size(); ++s) block[r * idx.size() + s] = cov[(size_t)idx[r] * n + idx[s]];
+  vc_stereo_uncertainty* u = nullptr;
+  const int st = vc_stereo_uncertainty_create(h->device, cm[0].model, cm[0].K, cm[0].nk, cm[0].width, cm[0].height, cm[0].T_ck, cm[1].model, cm[1].K, cm[1].nk,
+                                              cm[1].width, cm[1].height, cm[1].T_ck, dst_linear, dst_w, dst_h, alpha, grid_x, grid_y, &u);
+  if (st != VC_OK) return st;
+  vc::su_attach_cov(u, block.data());
   *out = u;
   return VC_OK;
 }

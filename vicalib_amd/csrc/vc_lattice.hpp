@@ -1,5 +1,6 @@
-// vc_lattice.hpp -- the one lattice-sweep core under the comparer (vc_compare.hip), the converter (vc_convert.hip) and the uncertainty map
-// (vc_uncertainty.hip); included by those three files only.  All three put a gx * gy lattice over a camera (CmpPlan, cmp_sample,
+// vc_lattice.hpp -- the one lattice-sweep core under the comparer (vc_compare.hip), the converter (vc_convert.hip), the uncertainty map
+// (vc_uncertainty.hip) and the stereo uncertainty map (vc_stereo_uncertainty.hip, which folds one record per depth plane and launches
+// k_lat_reduce itself); included by those four files only.  All of them put a gx * gy lattice over a camera (CmpPlan, cmp_sample,
 // vc_compare.hpp), sweep it with 256-thread workgroups that leave one partial record per workgroup, fold the partials with a one-wavefront
 // kernel and fetch the folded record with one synchronisation.  What that takes is here once:
 //   lat_block_record  a workgroup's record: sums by wave_allsum, the four waves in wave order; optionally the largest value with its sample

@@ -67,6 +67,60 @@ VC_HD int rectify_rotations(const double* T_ck_a, const double* T_ck_b, double* 
   return kRectOk;
 }
 
+// W = d(w_a, w_b, baseline) / d(w_ck_a, dp_a, w_ck_b, dp_b), 7 x 12 row-major, in closed form (host): how rectify_rotations' outputs move
+// with the two poses.  The poses move as vc_get_solution_covariance's do, q <- q * exp(w_ck) and p <- p + dp; the outputs as
+// R_ds <- exp([w]x) R_ds.  With phi = R_ak (w_ck_b - w_ck_a), so that R <- R exp([phi]x), and g = R^T t_bk:
+//   dc = -g x phi + dp_a - R^T dp_b,  de1 = (I - e1 e1^T) s dc / |c| (s: the sign flip),  d baseline = e1 . dc,
+//   d zm = (R^T z) x phi,  u = zm x e1,  de2 = (I - e2 e2^T)(d zm x e1 + zm x de1) / |u|,  de3 = de1 x e2 + e1 x de2,
+//   w_a = (de3 . e2, de1 . e3, de2 . e1),  w_b = w_a - R_ds_a phi.
+// The sign flip and the error statuses are rectify_rotations' at the nominal poses, and its status is returned (W untouched on an error).
+inline int rect_pose_jacobian(const double* T_ck_a, const double* T_ck_b, double* W) {
+  double Rda[9], Rdb[9], b;
+  const int rc = rectify_rotations(T_ck_a, T_ck_b, Rda, Rdb, &b);
+  if (rc != kRectOk) return rc;
+  double Ra[9], Rb[9], R[9];
+  quat_to_R(T_ck_a, Ra); quat_to_R(T_ck_b, Rb);
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) R[3 * i + j] = Rb[3 * i] * Ra[3 * j] + Rb[3 * i + 1] * Ra[3 * j + 1] + Rb[3 * i + 2] * Ra[3 * j + 2];
+  const double* tb = T_ck_b + 4;
+  double g[3];
+  for (int i = 0; i < 3; ++i) g[i] = R[i] * tb[0] + R[3 + i] * tb[1] + R[6 + i] * tb[2];
+  const double* e1 = Rda; const double* e2 = Rda + 3; const double* e3 = Rda + 6;
+  const double nc = std::fabs(b);                                   // |c|: the baseline is s |c|
+  const double s = b < 0.0 ? -1.0 : 1.0;
+  const double zb[3] = {R[6], R[7], R[8]}, zm[3] = {R[6], R[7], 1.0 + R[8]};
+  const double u[3] = {zm[1] * e1[2] - zm[2] * e1[1], zm[2] * e1[0] - zm[0] * e1[2], zm[0] * e1[1] - zm[1] * e1[0]};
+  const double n2 = std::sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]);
+  auto cross = [](const double* x, const double* y, double* o) { o[0] = x[1] * y[2] - x[2] * y[1]; o[1] = x[2] * y[0] - x[0] * y[2]; o[2] = x[0] * y[1] - x[1] * y[0]; };
+  auto dot = [](const double* x, const double* y) { return x[0] * y[0] + x[1] * y[1] + x[2] * y[2]; };
+  for (int col = 0; col < 12; ++col) {
+    double d[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    d[col] = 1.0;
+    const double dw[3] = {d[6] - d[0], d[7] - d[1], d[8] - d[2]};
+    double phi[3], dc[3], gxp[3];
+    for (int i = 0; i < 3; ++i) phi[i] = Ra[3 * i] * dw[0] + Ra[3 * i + 1] * dw[1] + Ra[3 * i + 2] * dw[2];
+    cross(g, phi, gxp);
+    for (int i = 0; i < 3; ++i) dc[i] = -gxp[i] + d[3 + i] - (R[i] * d[9] + R[3 + i] * d[10] + R[6 + i] * d[11]);
+    const double along = dot(e1, dc);
+    double de1[3], dzm[3], t0[3], t1[3], du[3], de2[3], de3[3];
+    for (int i = 0; i < 3; ++i) de1[i] = s * (dc[i] - e1[i] * along) / nc;
+    cross(zb, phi, dzm);
+    cross(dzm, e1, t0); cross(zm, de1, t1);
+    for (int i = 0; i < 3; ++i) du[i] = t0[i] + t1[i];
+    const double a2 = dot(e2, du);
+    for (int i = 0; i < 3; ++i) de2[i] = (du[i] - e2[i] * a2) / n2;
+    cross(de1, e2, t0); cross(e1, de2, t1);
+    for (int i = 0; i < 3; ++i) de3[i] = t0[i] + t1[i];
+    const double wa[3] = {dot(de3, e2), dot(de1, e3), dot(de2, e1)};
+    for (int i = 0; i < 3; ++i) {
+      W[i * 12 + col] = wa[i];
+      W[(3 + i) * 12 + col] = wa[i] - (Rda[3 * i] * phi[0] + Rda[3 * i + 1] * phi[1] + Rda[3 * i + 2] * phi[2]);
+    }
+    W[6 * 12 + col] = along;
+  }
+  return kRectOk;
+}
+
 // One matched pair of distorted pixels of the same target point.  out = dv = va - vb, d = ua - ub, P = the point in the rectified frame
 // of a (Z = fu b / d, X from ua, Y from the mean row), v = (va + vb) / 2.  false (out untouched): an inversion fails (undist_point) or the
 // disparity does not have the baseline's sign (d b <= 0: a point behind the pair, or sides swapped).

@@ -45,6 +45,8 @@ SYMBOLS = [
     "vc_converter_create", "vc_converter_create_for_camera", "vc_converter_destroy", "vc_convert_run", "vc_convert_get", "vc_convert_comparer", "vc_time_convert",
     "vc_uncertainty_create", "vc_uncertainty_create_for_camera", "vc_uncertainty_destroy", "vc_uncertainty_run", "vc_uncertainty_get_fit", "vc_uncertainty_get_map",
     "vc_uncertainty_summary", "vc_uncertainty_rings", "vc_time_uncertainty",
+    "vc_stereo_pose_jacobian", "vc_stereo_uncertainty_create", "vc_stereo_uncertainty_create_for_cameras", "vc_stereo_uncertainty_destroy", "vc_stereo_uncertainty_get",
+    "vc_stereo_uncertainty_run", "vc_stereo_uncertainty_get_map", "vc_stereo_uncertainty_summary", "vc_stereo_uncertainty_get_pose_sigma", "vc_time_stereo_uncertainty",
     "vc_selector_create", "vc_selector_create_for_calibrator", "vc_selector_destroy", "vc_select_add_tiles", "vc_select_set_poses", "vc_select_run", "vc_select_get",
     "vc_select_frames", "vc_select_frame_information", "vc_select_last_gains", "vc_select_dim", "vc_time_select",
     "vc_registrar_create", "vc_registrar_create_for_cameras", "vc_registrar_destroy", "vc_register_get", "vc_register_depth", "vc_register_depth_device",
@@ -205,7 +207,7 @@ def load():
         L.vc_allreduce_calls.restype = C.c_longlong
         L.vc_last_error.restype = C.c_char_p
         for name in ("vc_destroy", "vc_detector_destroy", "vc_shard_comm_destroy", "vc_undistorter_destroy", "vc_rectifier_destroy", "vc_comparer_destroy", "vc_converter_destroy",
-                     "vc_uncertainty_destroy", "vc_selector_destroy", "vc_registrar_destroy", "vc_depthcal_destroy"):
+                     "vc_uncertainty_destroy", "vc_stereo_uncertainty_destroy", "vc_selector_destroy", "vc_registrar_destroy", "vc_depthcal_destroy"):
             getattr(L, name).restype = None
         _lib = L
     return _lib
@@ -1201,6 +1203,105 @@ class Uncertainty:
     def time(self, reps=20):
         out = np.zeros(3)
         _check(self.L.vc_time_uncertainty(self.h, int(reps), _d(out)), "time_uncertainty")
+        return out
+
+
+class StereoUncertainty:
+    """The row and depth uncertainty of a calibrated stereo pair mapped over its rectified image (include/vicalib_amd.h:
+    vc_stereo_uncertainty*): cameras a and b -- (model, params) of image size_a / size_b at T_ck_a / T_ck_b --, a destination pinhole
+    dst_linear of dst_size held fixed (None: fitted at alpha) and a lattice `grid` = (gx, gy) over the rectified image of a.
+    run(cov, sigma_px, depths) takes the joint covariance of the pair in the layout of a two-camera rig's GetSolutionCovariance() (None: the
+    calibrator's, on a handle made by for_cameras) and maps (var_dv, var_d, var_Z) per sample and depth; map(), summary(), pose_sigma() and
+    geometry() read the handle; time(reps) -> ms per launch of the two side sweeps and of the map sweep.  pose_jacobian is host code."""
+
+    def __init__(self, cam_a, cam_b, size_a, size_b, T_ck_a, T_ck_b, dst_size=None, dst_linear=None, alpha=0.0, grid=(64, 48), device=0, _cameras_of=None):
+        self.L = load()
+        self.h = C.c_void_p()
+        dl = None if dst_linear is None else _d(np.ascontiguousarray(dst_linear, dtype=np.float64).reshape(4))
+        dst_size = size_a if dst_size is None else dst_size
+        if _cameras_of is not None:
+            cal, a, b = _cameras_of
+            _check(self.L.vc_stereo_uncertainty_create_for_cameras(cal.h, int(a), int(b), dl, int(dst_size[0]), int(dst_size[1]), C.c_double(alpha), int(grid[0]),
+                                                                   int(grid[1]), C.byref(self.h)), "stereo_uncertainty_create_for_cameras")
+            self.n_cov = 14 + len(cal.GetCamera(a)[0]) + len(cal.GetCamera(b)[0])
+        else:
+            (ma, Ka), (mb, Kb) = cam_a, cam_b
+            Ka = np.ascontiguousarray(Ka, dtype=np.float64); Kb = np.ascontiguousarray(Kb, dtype=np.float64)
+            _check(self.L.vc_stereo_uncertainty_create(int(device), _model_id(ma), _d(Ka), len(Ka), int(size_a[0]), int(size_a[1]), _d(T_ck_a), _model_id(mb), _d(Kb),
+                                                       len(Kb), int(size_b[0]), int(size_b[1]), _d(T_ck_b), dl, int(dst_size[0]), int(dst_size[1]), C.c_double(alpha),
+                                                       int(grid[0]), int(grid[1]), C.byref(self.h)), "stereo_uncertainty_create")
+            self.n_cov = 14 + len(Ka) + len(Kb)
+        self.grid = (int(grid[0]), int(grid[1]))
+        self.n_depths = 0
+
+    @classmethod
+    def for_cameras(cls, cal, cam_a, cam_b, size_a, dst_size=None, dst_linear=None, alpha=0.0, grid=(64, 48)):
+        """For two cameras of a ViCalibrator as GetCamera returns them (size_a: the size camera a was added with), with the pair's rows and
+        columns of GetSolutionCovariance() at the current state as the handle's covariance."""
+        return cls(None, None, size_a, None, None, None, dst_size, dst_linear, alpha, grid, _cameras_of=(cal, cam_a, cam_b))
+
+    @staticmethod
+    def pose_jacobian(T_ck_a, T_ck_b):
+        """-> W [7, 12] = d(w_a, w_b, baseline) / d(w_ck_a, dp_a, w_ck_b, dp_b) (vc_stereo_pose_jacobian)"""
+        W = np.zeros((7, 12))
+        _check(load().vc_stereo_pose_jacobian(_d(T_ck_a), _d(T_ck_b), W.ctypes.data_as(C.c_void_p)), "stereo_pose_jacobian")
+        return W
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.vc_stereo_uncertainty_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+    def geometry(self):
+        Ra, Rb, dl, W, b = np.zeros((3, 3)), np.zeros((3, 3)), np.zeros(4), np.zeros((7, 12)), C.c_double(0)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)      # noqa: E731
+        _check(self.L.vc_stereo_uncertainty_get(self.h, p(Ra), p(Rb), p(dl), C.byref(b), p(W)), "stereo_uncertainty_get")
+        return dict(R_ds_a=Ra, R_ds_b=Rb, dst_linear=dl, baseline=b.value, W=W)
+
+    def run(self, cov=None, sigma_px=1.0, depths=(1.0,)):
+        cp = None
+        if cov is not None:
+            cov = np.ascontiguousarray(cov, dtype=np.float64)
+            if cov.shape != (self.n_cov, self.n_cov):
+                raise VicalibError("stereo_uncertainty_run failed: VC_ERR_BAD_ARG (cov is not n x n, n = 14 + nk_a + nk_b)")
+            cp = _d(cov)
+        depths = np.ascontiguousarray(depths, dtype=np.float64).reshape(-1)
+        self.n_depths = 0
+        _check(self.L.vc_stereo_uncertainty_run(self.h, cp, C.c_double(sigma_px), _d(depths) if len(depths) else None, len(depths)), "stereo_uncertainty_run")
+        self.n_depths = len(depths)
+        return self
+
+    def map(self):
+        """-> (var [n_depths, gy, gx, 3] = (var_dv, var_d, var_Z), a NaN triple at an invalid sample; flags [n_depths, gy, gx] uint8)"""
+        gx, gy = self.grid
+        nd = max(self.n_depths, 1)
+        v = np.zeros((nd, gy, gx, 3)); f = np.zeros((nd, gy, gx), dtype=np.uint8)
+        _check(self.L.vc_stereo_uncertainty_get_map(self.h, v.ctypes.data_as(C.c_void_p), f.ctypes.data_as(C.c_void_p)), "stereo_uncertainty_get_map")
+        return v, f
+
+    def summary(self, plane=None):
+        """one depth plane's summary, or the list of all of them"""
+        if plane is None:
+            _check(self.L.vc_stereo_uncertainty_summary(self.h, 0, None, None, None, None, None, None, None), "stereo_uncertainty_summary")
+            return [self.summary(k) for k in range(self.n_depths)]
+        n, bad, w = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
+        s0, s1, s2, mx = C.c_double(0), C.c_double(0), C.c_double(0), C.c_double(0)
+        _check(self.L.vc_stereo_uncertainty_summary(self.h, int(plane), C.byref(n), C.byref(bad), C.byref(s0), C.byref(s1), C.byref(s2), C.byref(mx), C.byref(w)),
+               "stereo_uncertainty_summary")
+        return dict(count=n.value, invalid=bad.value, sum_var_dv=s0.value, sum_var_d=s1.value, sum_var_z=s2.value, max_var_dv=mx.value, worst=w.value)
+
+    def pose_sigma(self):
+        """-> [7]: the variances of w_a (3), w_b (3) and of the baseline at the last run's covariance and sigma_px"""
+        out = np.zeros(7)
+        _check(self.L.vc_stereo_uncertainty_get_pose_sigma(self.h, out.ctypes.data_as(C.c_void_p)), "stereo_uncertainty_get_pose_sigma")
+        return out
+
+    def time(self, reps=20):
+        out = np.zeros(2)
+        _check(self.L.vc_time_stereo_uncertainty(self.h, int(reps), out.ctypes.data_as(C.c_void_p)), "time_stereo_uncertainty")
         return out
 
 
