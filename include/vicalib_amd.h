@@ -394,6 +394,13 @@ int vc_detector_create(int device, int width, int height, vc_detector** out);
 void vc_detector_destroy(vc_detector* d);
 int vc_detector_set_params(vc_detector* d, int black_on_white, double at_threshold, double at_window_ratio, double conic_min_area,
                            double conic_min_density, double conic_min_aspect);
+/* The threshold window has half-width rad = (int)(width / at_window_ratio) and is clamped to the image.  The integral image is kept
+ * modulo 2^32, which is exact only while a window's sum fits 32 bits: vc_detector_find / vc_detector_find_conics return
+ * VC_ERR_UNSUPPORTED, before anything is uploaded, when  min(2 rad + 1, width) * min(2 rad + 1, height) * 255  does not (only
+ * possible above 16.8 MP with a small at_window_ratio); the handle stays usable, set other parameters and call again.
+ * A candidate whose conic fit is singular because no pixel of its box has a gradient (squared central difference >= 1) is not a dot:
+ * it is neither returned nor counted in *n_found.  The limit of 4096 candidates per image (more: VC_ERR_UNSUPPORTED) is on the
+ * candidates before that rule.  Fits that are rank-deficient with a non-zero matrix are not detected. */
 /* centres: 2 x max_conics doubles; *n_found is the number of dots found (may exceed max_conics: the first max_conics are written).
  * A detector handle is single-threaded: one image at a time (its staging buffers and stream belong to the call in progress); use one
  * handle per thread. */

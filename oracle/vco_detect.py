@@ -77,9 +77,11 @@ def label4(fg):
 
 
 def fit_dual_conic(gx, gy, x0, y0, x1, y1, full=False):
-    """Centre of the ellipse whose edge runs through the box [x0, x1) x [y0, y1).  Coordinates relative to the box centre."""
+    """Centre of the ellipse whose edge runs through the box [x0, x1) x [y0, y1).  Coordinates relative to the box centre.
+    None for a box in which no pixel reaches MIN_GRAD2 (the normal equations are all zero).  A fit that is rank-deficient with a
+    non-zero matrix (fewer than five independent tangent lines) is NOT handled: numpy raises, the device's answer is undefined."""
     cx, cy = 0.5 * (x0 + x1 - 1), 0.5 * (y0 + y1 - 1)
-    M = np.zeros((5, 5)); rhs = np.zeros(5)
+    M = np.zeros((5, 5)); rhs = np.zeros(5); used = 0
     for y in range(y0, y1):
         for x in range(x0, x1):
             a, b = gx[y, x], gy[y, x]
@@ -88,7 +90,9 @@ def fit_dual_conic(gx, gy, x0, y0, x1, y1, full=False):
                 continue
             c = -(a * (x - cx) + b * (y - cy))
             K = np.array([a * a, a * b, b * b, a * c, b * c])
-            M += w2 * np.outer(K, K); rhs += w2 * K * (-(c * c))
+            M += w2 * np.outer(K, K); rhs += w2 * K * (-(c * c)); used += 1
+    if used == 0:
+        return None                           # no pixel of the box has a gradient: M = 0, nothing to fit -- not a dot
     th = np.linalg.solve(M, rhs)
     if not full:
         return cx + 0.5 * th[3], cy + 0.5 * th[4]
@@ -122,11 +126,14 @@ def find_conics(img, at_threshold=0.9, at_window_ratio=30.0, min_area=4.0, min_d
             continue
         if x0 - GROW < 1 or y0 - GROW < 1 or x1 + GROW > w - 1 or y1 + GROW > h - 1:
             continue
+        fit = fit_dual_conic(gx, gy, x0 - GROW, y0 - GROW, x1 + GROW, y1 + GROW, full=full)
+        if fit is None:
+            continue                          # a component without any gradient in its box is not a dot
         if full:
-            c, Cm = fit_dual_conic(gx, gy, x0 - GROW, y0 - GROW, x1 + GROW, y1 + GROW, full=True)
+            c, Cm = fit
             out.append(c); conics.append(Cm); boxes.append((x0, y0, x1 - 1, y1 - 1))
         else:
-            out.append(fit_dual_conic(gx, gy, x0 - GROW, y0 - GROW, x1 + GROW, y1 + GROW))
+            out.append(fit)
     if full:
         return np.array(out).reshape(-1, 2), np.array(conics).reshape(-1, 3, 3), np.array(boxes, dtype=np.int64).reshape(-1, 4)
     return np.array(out).reshape(-1, 2)

@@ -47,6 +47,7 @@ constexpr int kHeadBytes = 16;         // the candidate count, in front of the r
 constexpr int kFastRecs = 512;         // records that travel with the count in the first copy
 constexpr int kTW = 32, kTH = 32;      // labelling tile
 constexpr int kMaxCand = 4096;         // candidates per image (more: VC_ERR_UNSUPPORTED)
+constexpr int kNoDot = -1;             // DetRec::box[0] of a candidate whose fit was singular
 
 struct DetView {
   int w, h, pitch;
@@ -63,7 +64,9 @@ struct DetView {
 
 // integral image, rows: one wavefront per row, eight consecutive pixels per lane and round, exclusive scan of the lane sums.
 // The sums are kept modulo 2^32 (images above 16.8 MP would overflow a 32-bit total): every use takes the four-corner difference in
-// unsigned arithmetic, which is exact as long as the WINDOW's sum fits -- it does, a window has at most (2 rad + 1)^2 pixels
+// unsigned arithmetic, which is exact as long as the WINDOW's sum fits 32 bits.  The clamped window has at most
+// min(2 rad + 1, w) * min(2 rad + 1, h) pixels of at most 255 each; rad = w / at_window_ratio is the caller's to choose, so
+// vc_detector_find_conics refuses (VC_ERR_UNSUPPORTED) a window whose largest possible sum does not fit (det_window_fits)
 __global__ __launch_bounds__(64) void k_det_rows(DetView v) {
   const int y = blockIdx.x, lane = threadIdx.x;
   unsigned carry = 0;
@@ -289,7 +292,9 @@ __global__ __launch_bounds__(64) void k_det_fit(DetView v) {
     DetRec& rec = v.recs[ci];
     rec.cx = ok ? cx + 0.5 * th[3] : -1.0;
     rec.cy = ok ? cy + 0.5 * th[4] : -1.0;
-    rec.box[0] = v.x0[r]; rec.box[1] = v.y0[r]; rec.box[2] = v.x1[r] - 1; rec.box[3] = v.y1[r] - 1;
+    // a singular fit (no pixel of the box reached kMinGrad2: M = 0) is no dot: box[0] = kNoDot tells the host to leave the record out
+    // (the border test of k_det_select keeps a candidate's x0 at 3 or more)
+    rec.box[0] = ok ? v.x0[r] : kNoDot; rec.box[1] = v.y0[r]; rec.box[2] = v.x1[r] - 1; rec.box[3] = v.y1[r] - 1;
     {
       // the fitted dual conic [[A, B/2, D/2], [B/2, C, E/2], [D/2, E/2, 1]] lives in box-centred coordinates: moved to image
       // coordinates (T Q T^T, T = translation by the box centre), inverted (adjugate: the scale of a conic is free) and scaled
@@ -306,6 +311,12 @@ __global__ __launch_bounds__(64) void k_det_fit(DetView v) {
     }
   }
   }
+}
+
+// does the largest sum a clamped threshold window can hold fit the 32 bits of the integral image's differences?
+bool det_window_fits(int w, int h, int rad) {
+  const long long side = 2 * (long long)rad + 1;
+  return std::min(side, (long long)w) * std::min(side, (long long)h) * 255 <= 0xffffffffLL;
 }
 
 }  // namespace
@@ -366,6 +377,8 @@ int vc_detector_find_conics(vc_detector* d, const unsigned char* image, int pitc
   if (!d || !image || pitch < d->w || !n_found || max_conics < 0 || (max_conics > 0 && !centres)) return VC_ERR_BAD_ARG;
   if (hipSetDevice(d->device) != hipSuccess) return VC_ERR_NO_DEVICE;
   const int w = d->w, h = d->h, np = w * h;
+  const int rad = (int)((double)w / d->at_window_ratio);
+  if (!det_window_fits(w, h, rad)) return VC_ERR_UNSUPPORTED;      // (nothing uploaded, nothing queued)
   // A detector is SINGLE-THREADED: one image at a time per handle (the staging buffers and the stream belong to the call in progress) --
   // one handle per thread.  A clean call has synchronised on its download, the staging buffers are free; a call that left through an
   // error path may have copies in flight that still read them: it leaves the handle marked and this call drains the stream first
@@ -380,7 +393,7 @@ int vc_detector_find_conics(vc_detector* d, const unsigned char* image, int pitc
   v.w = w; v.h = h; v.pitch = w; v.img = d->d_img; v.S = d->d_S; v.lab = d->d_lab;
   v.area = d->d_stats; v.x0 = d->d_stats + np; v.x1 = d->d_stats + 2 * (size_t)np; v.y0 = d->d_stats + 3 * (size_t)np; v.y1 = d->d_stats + 4 * (size_t)np;
   v.cand = d->d_cand; v.cand_sorted = d->d_cand_sorted; v.n_cand = reinterpret_cast<int*>(d->d_out); v.max_cand = d->max_cand;
-  v.thr = d->at_threshold; v.rad = (int)((double)w / d->at_window_ratio);
+  v.thr = d->at_threshold; v.rad = rad;
   v.min_area = d->conic_min_area; v.min_density = d->conic_min_density; v.min_aspect = d->conic_min_aspect;
   v.black_on_white = d->black_on_white; v.recs = reinterpret_cast<DetRec*>(d->d_out + kHeadBytes);
   const int gb = (np + 255) / 256, tiles = ((w + kTW - 1) / kTW) * ((h + kTH - 1) / kTH);
@@ -397,19 +410,23 @@ int vc_detector_find_conics(vc_detector* d, const unsigned char* image, int pitc
   if (hipMemcpyAsync(d->h_out, d->d_out, fast_bytes, hipMemcpyDeviceToHost, d->stream) != hipSuccess || hipStreamSynchronize(d->stream) != hipSuccess) return VC_ERR_NO_DEVICE;
   const int n = *reinterpret_cast<const int*>(d->h_out);
   if (n > d->max_cand) { d->in_flight = false; return VC_ERR_UNSUPPORTED; }      // (synchronised: nothing pending)
-  *n_found = n;
-  const int nout = std::min(n, max_conics);
-  if (nout > kFastRecs) {
-    if (hipMemcpyAsync(d->h_out + fast_bytes, d->d_out + fast_bytes, (size_t)(nout - kFastRecs) * sizeof(DetRec), hipMemcpyDeviceToHost, d->stream) != hipSuccess ||
+  if (n > kFastRecs) {                           // (all n records: the count of dots needs every candidate's verdict)
+    if (hipMemcpyAsync(d->h_out + fast_bytes, d->d_out + fast_bytes, (size_t)(n - kFastRecs) * sizeof(DetRec), hipMemcpyDeviceToHost, d->stream) != hipSuccess ||
         hipStreamSynchronize(d->stream) != hipSuccess) return VC_ERR_NO_DEVICE;
   }
   d->in_flight = false;                          // (everything this call queued has completed)
   const DetRec* recs = reinterpret_cast<const DetRec*>(d->h_out + kHeadBytes);
-  for (int i = 0; i < nout; ++i) {
-    centres[2 * i] = recs[i].cx; centres[2 * i + 1] = recs[i].cy;
-    if (conics) std::memcpy(conics + 9 * (size_t)i, recs[i].conic, 72);
-    if (boxes) std::memcpy(boxes + 4 * (size_t)i, recs[i].box, 16);
+  int kept = 0;                                  // candidates whose fit was singular are no dots: neither counted nor copied out
+  for (int i = 0; i < n; ++i) {
+    if (recs[i].box[0] == kNoDot) continue;
+    if (kept < max_conics) {
+      centres[2 * kept] = recs[i].cx; centres[2 * kept + 1] = recs[i].cy;
+      if (conics) std::memcpy(conics + 9 * (size_t)kept, recs[i].conic, 72);
+      if (boxes) std::memcpy(boxes + 4 * (size_t)kept, recs[i].box, 16);
+    }
+    ++kept;
   }
+  *n_found = kept;
   return VC_OK;
 }
 int vc_detector_find(vc_detector* d, const unsigned char* image, int pitch, double* centres, int max_conics, int* n_found) {
