@@ -21,6 +21,7 @@
 // 30 ms polling loop (vicalib-engine.cc:376-431), WriteCalibration (:353-372), success test (vicalib-task.cc:831-856).
 #include <vicalib_amd.hpp>
 #include "../vicalib_amd/csrc/vc_holdout_select.hpp"      // which frames -holdout_every keeps out (host arithmetic, no device code)
+#include "../vicalib_amd/csrc/vc_allan.hpp"               // the noise model of -allan_imu evaluated at an averaging time (host arithmetic, no device code)
 
 #include <algorithm>
 #include <chrono>
@@ -204,6 +205,13 @@ static void DefineFlags() {
   Define("depthcal_min_count", "int32", "50", "A cell with fewer pixels gets no term of its own (>= 1).");
   Define("depthcal_min_spread", "double", "0.02", "A cell whose values spread less than this (standard deviation of (v - vref) / vref) gets an offset only (>= 0).");
   Define("depthcal_margin", "double", "0", "The board rectangle is the dot lattice [0, (grid_width - 1) spacing] x [0, (grid_height - 1) spacing] grown by this (m).");
+  Define("allan_imu", "string", "", "csv://directory of an IMU log recorded at rest: its Allan deviation, noise terms and the sigmas to calibrate with go into -allan_dir; needs no -cam, nothing is calibrated.");
+  Define("allan_dir", "string", "", "Directory for allan.csv and allan_summary.csv of -allan_imu.");
+  Define("allan_per_decade", "int32", "20", "Averaging times per decade of the Allan deviation (1 ... 1000).");
+  Define("allan_max_fraction", "double", "0.1111111111111111", "The longest averaging time as a fraction of the samples used (in (0, 0.5]; at 1/9 the standard error of a point is 25 %).");
+  Define("allan_static_window_s", "double", "1", "Window of the quiet test in seconds (> 0).");
+  Define("allan_static_gyro", "double", "0", "The mean angular velocity may change by less than this from one window to the next for a window to count as quiet (<= 0: not tested).");
+  Define("allan_static_accel", "double", "0", "The same for the mean acceleration (<= 0: not tested; both off: the whole log is used).");
   Define("convert_grid", "string", "64x48", "Lattice of the conversion, GXxGY: 2 ... image width by 2 ... image height, at most 2^22 samples.");
   Define("convert_fit_radius", "double", "1", "The target model is fitted over the samples within this fraction of the half-diagonal of the image centre (> 0; 1 = the whole image).");
 }
@@ -1207,6 +1215,116 @@ static int DepthCalApply(const DepthCalCli& o, int device, std::string* err) {
 }
 
 // ---- -convert_models / -convert_to: calibrated cameras converted to other camera models (vc_convert*) ------------------------------------
+// ---- -allan_imu: the noise of an IMU from a log recorded at rest (vc_allan*) -----------------------------------------------------------
+struct AllanCli { bool on = false; std::string imu, dir; int per_decade = 20; double max_fraction = 1.0 / 9.0, window_s = 1.0, gyro_thr = 0.0, accel_thr = 0.0; };
+static bool AllanFlags(AllanCli* o, std::string* err) {
+  o->imu = FlagString("allan_imu"); o->dir = FlagString("allan_dir");
+  o->on = !o->imu.empty();
+  if (!o->on && o->dir.empty()) return true;
+  if (o->imu.empty() || o->dir.empty()) { *err = "-allan_imu and -allan_dir need each other"; return false; }
+  o->per_decade = (int)FlagInt("allan_per_decade"); o->max_fraction = FlagDouble("allan_max_fraction"); o->window_s = FlagDouble("allan_static_window_s");
+  o->gyro_thr = FlagDouble("allan_static_gyro"); o->accel_thr = FlagDouble("allan_static_accel");
+  if (o->per_decade < 1 || o->per_decade > 1000) { *err = "illegal value for flag 'allan_per_decade': expected 1 ... 1000"; return false; }
+  if (!(o->max_fraction > 0.0 && o->max_fraction <= 0.5)) { *err = "illegal value for flag 'allan_max_fraction': expected a fraction in (0, 0.5]"; return false; }
+  if (!(o->window_s > 0.0) || !std::isfinite(o->window_s)) { *err = "illegal value for flag 'allan_static_window_s': expected a positive number of seconds"; return false; }
+  if (std::isnan(o->gyro_thr) || std::isnan(o->accel_thr)) { *err = "illegal value for flag 'allan_static_gyro' / 'allan_static_accel': not a number"; return false; }
+  return true;
+}
+// Exit status: 0, 1 (an error said in *err) or 3 (no device).
+static int AllanImu(const AllanCli& o, int device, std::string* err) {
+  static const char* kAxis[6] = {"gx", "gy", "gz", "ax", "ay", "az"};
+  ImuData imu;
+  if (!ReadImu(StripScheme(o.imu), FlagBool("use_system_time"), &imu, err)) return 1;
+  const size_t n = imu.time.size();
+  if (n < 2) { *err = "the log " + o.imu + " holds fewer than two samples"; return 1; }
+  if (n > (size_t)vc::kAllanMaxN) { *err = "the log holds more than 2^24 samples"; return 1; }
+  if (!MakeDir(o.dir, err)) return 1;
+  vc_allan* raw = nullptr;
+  const int st_create = vc_allan_create(device, (int)n, imu.gyro.data(), imu.accel.data(), imu.time.data(), &raw);
+  if (st_create == VC_ERR_NO_DEVICE) { *err = "no HIP device (there is no CPU fallback)"; return 3; }
+  if (st_create != VC_OK) { *err = "the log was refused: a sample or a time stamp is not finite (status " + std::to_string(st_create) + ")"; return 1; }
+  std::unique_ptr<vc_allan, void (*)(vc_allan*)> a(raw, vc_allan_destroy);
+  double tau0 = 0.0, dt_min = 0.0, dt_max = 0.0, means[6];
+  long long irregular = 0;
+  int range[2] = {0, (int)n};
+  vc_allan_get(a.get(), nullptr, &tau0, &dt_min, &dt_max, means, &irregular, range);
+  if (o.gyro_thr > 0.0 || o.accel_thr > 0.0) {
+    const long window = std::max(1L, std::lround(o.window_s / tau0));
+    if (2 * window >= (long)n) { *err = "-allan_static_window_s: two windows of " + std::to_string(window) + " samples do not fit into the log"; return 1; }
+    int n_quiet = 0;
+    const int q = vc_allan_static(a.get(), (int)window, o.gyro_thr, o.accel_thr, range, &n_quiet);
+    if (q == 1) { *err = "no window of " + std::to_string(window) + " samples is quiet under -allan_static_gyro / -allan_static_accel"; return 1; }
+    if (q != VC_OK) { *err = "the quiet test failed (status " + std::to_string(q) + ")"; return q == VC_ERR_NO_DEVICE ? 3 : 1; }
+    std::fprintf(stderr, "I static stretch: samples %d ... %d of %zu (%.1f s), %d quiet window starts of %ld samples\n", range[0], range[0] + range[1] - 1, n,
+                 range[1] * tau0, n_quiet, window);
+  }
+  vic::AllanFactors f;
+  vic::AllanCurve curve;
+  try { f = vic::AllanFactorList(range[1], o.per_decade, o.max_fraction); }
+  catch (const std::exception& e) { *err = e.what(); return 1; }
+  const size_t n_m = f.m.size();
+  curve.avar.resize(6 * n_m); curve.terms.resize(n_m);
+  const int q = vc_allan_run(a.get(), (int)n_m, f.m.data(), curve.avar.data(), curve.terms.data());
+  if (q != VC_OK) { *err = "the sweep failed (status " + std::to_string(q) + ")"; return q == VC_ERR_NO_DEVICE ? 3 : 1; }
+  std::vector<double> tau(n_m);
+  for (size_t j = 0; j < n_m; ++j) tau[j] = f.m[j] * tau0;
+  vic::AllanFitResult fit[6];
+  for (int c = 0; c < 6; ++c) fit[c] = vic::AllanFit(tau, curve.avar.data() + c * n_m, f.rel_err);
+  // ---- allan.csv: one line per averaging time
+  {
+    std::ofstream out(o.dir + "/allan.csv");
+    if (!out) { *err = "cannot write " + o.dir + "/allan.csv"; return 1; }
+    out << "tau,m,terms,rel_err";
+    for (int c = 0; c < 6; ++c) out << ",adev_" << kAxis[c];
+    for (int c = 0; c < 6; ++c) out << ",model_" << kAxis[c];
+    out << "\n";
+    char buf[64];
+    for (size_t j = 0; j < n_m; ++j) {
+      std::snprintf(buf, sizeof(buf), "%.10e,%d,%d,%.10e", tau[j], f.m[j], curve.terms[j], f.rel_err[j]); out << buf;
+      for (int c = 0; c < 6; ++c) { std::snprintf(buf, sizeof(buf), ",%.10e", std::sqrt(curve.avar[c * n_m + j])); out << buf; }
+      for (int c = 0; c < 6; ++c) {
+        const double md = fit[c].status == 0 ? std::sqrt(vc::allan_model(fit[c].N, fit[c].B, fit[c].K, tau[j])) : std::nan("");
+        std::snprintf(buf, sizeof(buf), ",%.10e", md); out << buf;
+      }
+      out << "\n";
+    }
+  }
+  // ---- allan_summary.csv: one line per axis; sigma = N / sqrt(tau0), the per-sample standard deviation at the log's own rate
+  const double sqrt_tau0 = std::sqrt(tau0);
+  {
+    std::ofstream out(o.dir + "/allan_summary.csv");
+    if (!out) { *err = "cannot write " + o.dir + "/allan_summary.csv"; return 1; }
+    out << "axis,mean,adev_tau0,N,B,K,active_terms,fit_rms_log,fit_status,sigma,n,first,count,tau0,irregular_intervals\n";
+    char buf[400];
+    for (int c = 0; c < 6; ++c) {
+      std::snprintf(buf, sizeof(buf), "%s,%.10e,%.10e,%.10e,%.10e,%.10e,%s%s%s,%.6e,%d,%.10e,%zu,%d,%d,%.10e,%lld\n", kAxis[c], means[c], std::sqrt(curve.avar[c * n_m]),
+                    fit[c].N, fit[c].B, fit[c].K, (fit[c].mask & 1) ? "N" : "", (fit[c].mask & 2) ? "B" : "", (fit[c].mask & 4) ? "K" : "", fit[c].rms_log,
+                    fit[c].status, fit[c].N / sqrt_tau0, n, range[0], range[1], tau0, irregular);
+      out << buf;
+    }
+  }
+  // ---- what the user reads
+  double sigma[2] = {0.0, 0.0};
+  bool have[2] = {false, false};
+  for (int s = 0; s < 2; ++s) {
+    double q2 = 0.0; int used = 0;
+    for (int c = 3 * s; c < 3 * s + 3; ++c) {
+      if (fit[c].status != 0) { std::fprintf(stderr, "W the fit of axis %s failed (status %d): it is left out of its sensor's sigma\n", kAxis[c], fit[c].status); continue; }
+      q2 += fit[c].N * fit[c].N; ++used;
+    }
+    if (used > 0) { sigma[s] = std::sqrt(q2 / used) / sqrt_tau0; have[s] = true; }
+    std::fprintf(stderr, "I %s white noise N = %.6e %.6e %.6e %s/sqrt(Hz) (x y z)\n", s == 0 ? "gyro" : "accel", fit[3 * s].N, fit[3 * s + 1].N, fit[3 * s + 2].N,
+                 s == 0 ? "rad/s" : "m/s^2");
+  }
+  if ((double)irregular > 0.01 * (double)(n - 1))
+    std::fprintf(stderr, "W %lld of %zu intervals lie outside [0.5, 1.5] tau0 (tau0 = %.6g s, %.6g ... %.6g s): the log is not resampled\n", irregular, n - 1, tau0, dt_min, dt_max);
+  if (range[1] * tau0 < 100.0) std::fprintf(stderr, "W the range used is %.1f s long: under 100 s the long averaging times carry little\n", range[1] * tau0);
+  if (have[0] && have[1]) std::printf("-gyro_sigma %.8e -accel_sigma %.8e\n", sigma[0], sigma[1]);
+  else std::fprintf(stderr, "W no sigma for a sensor without a fitted axis: nothing to paste\n");
+  std::fprintf(stderr, "I wrote %s/allan.csv (%zu averaging times) and %s/allan_summary.csv\n", o.dir.c_str(), n_m, o.dir.c_str());
+  return 0;
+}
+
 static const char* ModelXmlType(int id) {
   static const char* n[] = {"calibu_fu_fv_u0_v0_w", "calibu_fu_fv_u0_v0_k1_k2", "calibu_fu_fv_u0_v0_k1_k2_k3", "calibu_fu_fv_u0_v0_kb4", "calibu_fu_fv_u0_v0", "calibu_fu_fv_u0_v0_rational6"};
   return (id >= 0 && id < 6) ? n[id] : "?";
@@ -1672,6 +1790,14 @@ int main(int argc, char** argv) {
   if (!DepthCalFlags(&depthcal, &err)) { std::fprintf(stderr, "ERROR: %s\n", err.c_str()); return 1; }
   if (depthcal.on && (!FlagString("compare_models").empty() || !FlagString("convert_models").empty() || !FlagString("register_models").empty())) {
     std::fprintf(stderr, "ERROR: -depthcal_models / -depthcal_depth / -depthcal_apply and -compare_models / -convert_models / -register_models exclude each other\n"); return 1;
+  }
+  // ---- -allan_imu csv://log -allan_dir dir: the IMU's noise from a static log, nothing is calibrated
+  AllanCli allan;
+  if (!AllanFlags(&allan, &err)) { std::fprintf(stderr, "ERROR: %s\n", err.c_str()); return 1; }
+  if (allan.on) {
+    const int rc = AllanImu(allan, (int)FlagInt("device"), &err);
+    if (rc != 0) std::fprintf(stderr, "%s %s\n", rc == 3 ? "F" : "E IMU noise characterisation failed:", err.c_str());
+    return rc;
   }
   if (depthcal.apply) {
     const int rc = DepthCalApply(depthcal, (int)FlagInt("device"), &err);

@@ -911,6 +911,49 @@ int vc_depthcal_apply(vc_depthcal* d, int n, const unsigned short* src, int src_
  * images (into sums of the timer's own), [2] the apply. */
 int vc_time_depthcal(vc_depthcal* d, int n_images, int reps, double out_ms[3]);
 
+/* ---- the noise of an IMU from a log recorded at rest -----------------------------------------------------------------------------------
+ * vc_set_sigmas takes two numbers that belong to the sensor, not to the calibration.  The overlapping Allan variance of a static log
+ * gives them.  A handle holds one log of n samples (2 <= n <= 2^24; more is VC_ERR_UNSUPPORTED, before anything is read) on six channels
+ * gx gy gz ax ay az: on the device, per channel, the mean and S_0 = 0, S_k = sum_{i<k} (y_i - mean).  For an averaging factor m over the
+ * samples [first, first + count) in use
+ *   avar(m) = sum_{k=first}^{first+count-2m} (S_{k+2m} - 2 S_{k+m} + S_k)^2 / (2 m^2 terms),   terms = count - 2m + 1,
+ * at the averaging time tau = m tau0, tau0 = (t_{n-1} - t_0) / (n - 1).  Everything is fp64; no sum's order depends on anything but n, the
+ * range and m: two runs give the same bits, and a channel's bits do not depend on the other five.
+ * VC_ERR_BAD_ARG comes before any device call: a null pointer, n < 2, a time that is not finite or not strictly increasing, a sample
+ * that is not finite.  VC_ERR_NO_DEVICE without a device: there is no host fallback.  A handle is single-threaded. */
+typedef struct vc_allan vc_allan;
+int vc_allan_create(int device, int n, const double* gyro /* n x 3 */, const double* accel /* n x 3 */, const double* time /* n */, vc_allan** out);
+void vc_allan_destroy(vc_allan* a);
+/* n, tau0, the smallest and largest interval, the six means, the number of intervals outside [0.5, 1.5] tau0 (reported, not refused), the
+ * range in use (first, count); any pointer may be NULL */
+int vc_allan_get(vc_allan* a, int* n, double* tau0, double* dt_min, double* dt_max, double means[6], long long* irregular, int range[2]);
+/* The part of the log that is a static log.  Window start k (0 <= k <= n - 2 window) is quiet when the mean over `window` samples changes
+ * by less than the threshold to the next window on both sensors: the norm over the sensor's three axes of
+ * (S_{k+2W} - 2 S_{k+W} + S_k) / W.  The longest run of consecutive quiet starts k0 .. k1, the earliest among equals, becomes the range:
+ * samples [k0, k1 + 2 window).  A threshold <= 0 switches that sensor's test off; both off: the whole log.  range_out (nullable): first,
+ * count; n_quiet (nullable): quiet starts in the log.  Returns 1, the range unchanged, when no start is quiet.  VC_ERR_BAD_ARG:
+ * window < 1, 2 window >= n, a threshold that is NaN. */
+int vc_allan_static(vc_allan* a, int window, double gyro_thr, double accel_thr, int range_out[2], int* n_quiet);
+/* VC_ERR_BAD_ARG: a range outside the log or shorter than 2 */
+int vc_allan_set_range(vc_allan* a, int first, int count);
+/* avar[c * n_m + j] of channel c at factor m[j] over the range in use; terms (nullable): n_m.  VC_ERR_BAD_ARG: n_m outside 1 .. 65535, a
+ * factor with m < 1 or 2 m > count. */
+int vc_allan_run(vc_allan* a, int n_m, const int* m, double* avar /* 6 x n_m */, int* terms /* n_m, nullable */);
+/* HIP events on the handle's stream, `reps` launches back to back each: out_ms[0] the means and prefix sums, [1] the sweep of vc_allan_run
+ * over the range in use.  The same input: the same bits are written again. */
+int vc_time_allan(vc_allan* a, int n_m, const int* m, int reps, double out_ms[2]);
+/* Host only, no device, no handle.  The averaging factors round(10^(j / per_decade)), j = 0, 1, ..., made strictly increasing, up to
+ * max(1, floor(n_used max_fraction)); rel_err (nullable): IEEE Std 952's relative standard error of adev, 1 / sqrt(2 (n_used / m - 1)).
+ * *n_m is the count; with m == NULL nothing else is written.  VC_ERR_BAD_ARG: n_used < 2, per_decade < 1, max_fraction outside
+ * (0, 0.5], a count above cap. */
+int vc_allan_factors(int n_used, int per_decade, double max_fraction, int cap, int* m, double* rel_err, int* n_m);
+/* Host only.  avar(tau) = N^2 / tau + (2 ln 2 / pi) B^2 + K^2 tau / 3 fitted to n points with weights 1 / (avar^2 rel_err^2), N, B, K >= 0:
+ * the seven non-empty subsets of the terms by their normal equations; of the non-negative solutions the smallest weighted residual.
+ * out[5] = N (white noise, unit / sqrt(Hz)), B (bias instability), K (rate random walk), the rms of log(model / measured), the number of
+ * points used (a point whose tau, avar or rel_err is not positive and finite is left out); mask: bit 0 N, bit 1 B, bit 2 K active.
+ * Returns 0, 1 (fewer than three points, the model's terms: nothing fitted) or 2 (no feasible subset); VC_ERR_BAD_ARG: a null pointer, n < 1. */
+int vc_allan_fit(int n, const double* tau, const double* avar, const double* rel_err, double out[5], int* mask);
+
 #ifdef __cplusplus
 }
 #endif

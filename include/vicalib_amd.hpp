@@ -737,4 +737,60 @@ class DepthCalibrator {
   int cells_ = 0;
 };
 
+// The noise of an IMU from a log recorded at rest (vc_allan*): the overlapping Allan variance of six channels on the device, the averaging
+// factors and the fit of white noise N, bias instability B and rate random walk K on the host.
+struct AllanInfo { int n = 0, first = 0, count = 0; double tau0 = 0, dt_min = 0, dt_max = 0, means[6] = {0, 0, 0, 0, 0, 0}; long long irregular = 0; };
+struct AllanFactors { std::vector<int> m; std::vector<double> rel_err; };
+struct AllanCurve { std::vector<double> avar; std::vector<int> terms; };      // avar: 6 x n_m, channel-major (gx gy gz ax ay az)
+struct AllanFitResult { double N = 0, B = 0, K = 0, rms_log = 0; int n_points = 0, mask = 0, status = 0; };
+inline AllanFactors AllanFactorList(int n_used, int per_decade = 20, double max_fraction = 1.0 / 9.0) {
+  int n_m = 0;
+  vc_checked(vc_allan_factors(n_used, per_decade, max_fraction, 0, nullptr, nullptr, &n_m), "AllanFactorList");
+  AllanFactors f; f.m.resize(n_m); f.rel_err.resize(n_m);
+  vc_checked(vc_allan_factors(n_used, per_decade, max_fraction, n_m, f.m.data(), f.rel_err.data(), &n_m), "AllanFactorList");
+  return f;
+}
+inline AllanFitResult AllanFit(const std::vector<double>& tau, const double* avar, const std::vector<double>& rel_err) {
+  if (tau.empty() || tau.size() != rel_err.size()) throw std::runtime_error("vicalib_amd: AllanFit: array sizes disagree");
+  double out[5]; AllanFitResult r;
+  r.status = vc_checked(vc_allan_fit((int)tau.size(), tau.data(), avar, rel_err.data(), out, &r.mask), "AllanFit");
+  r.N = out[0]; r.B = out[1]; r.K = out[2]; r.rms_log = out[3]; r.n_points = (int)out[4];
+  return r;
+}
+class AllanAnalyzer {
+ public:
+  // gyro, accel: n x 3; time: n, strictly increasing
+  AllanAnalyzer(int n, const double* gyro, const double* accel, const double* time, int device = 0) {
+    vc_checked(vc_allan_create(device, n, gyro, accel, time, &a_), "AllanAnalyzer");
+  }
+  ~AllanAnalyzer() { vc_allan_destroy(a_); }
+  AllanAnalyzer(const AllanAnalyzer&) = delete;
+  AllanAnalyzer& operator=(const AllanAnalyzer&) = delete;
+  AllanInfo Get() {
+    AllanInfo i; int range[2] = {0, 0};
+    vc_checked(vc_allan_get(a_, &i.n, &i.tau0, &i.dt_min, &i.dt_max, i.means, &i.irregular, range), "Get");
+    i.first = range[0]; i.count = range[1];
+    return i;
+  }
+  void SetRange(int first, int count) { vc_checked(vc_allan_set_range(a_, first, count), "SetRange"); }
+  // the longest quiet stretch becomes the range; false (the range stays) when no window start is quiet
+  bool Static(int window, double gyro_thr, double accel_thr, int* n_quiet = nullptr) {
+    return vc_checked(vc_allan_static(a_, window, gyro_thr, accel_thr, nullptr, n_quiet), "Static") == 0;
+  }
+  AllanCurve Run(const std::vector<int>& m) {
+    AllanCurve c; c.avar.resize(6 * m.size()); c.terms.resize(m.size());
+    vc_checked(vc_allan_run(a_, (int)m.size(), m.data(), c.avar.data(), c.terms.data()), "Run");
+    return c;
+  }
+  std::array<double, 2> Time(const std::vector<int>& m, int reps = 10) {
+    std::array<double, 2> ms{{0, 0}};
+    vc_checked(vc_time_allan(a_, (int)m.size(), m.data(), reps, ms.data()), "Time");
+    return ms;
+  }
+  vc_allan* handle() { return a_; }
+
+ private:
+  vc_allan* a_ = nullptr;
+};
+
 }  // namespace visual_inertial_calibration

@@ -4,6 +4,7 @@
 #include "vc_uncertainty.hpp"
 #include "vc_stereo_uncertainty.hpp"
 #include "vc_seed.hpp"
+#include "vc_allan.hpp"
 
 static int env_bit(const char* name) { const char* e = std::getenv(name); return (e && (e[0] == '0' || e[0] == '1')) ? e[0] - '0' : -1; }
 Switches Switches::read() {
@@ -1118,5 +1119,19 @@ int vc_get_debug_stamps(vc_calibrator* h, long long* out) {
 }
 long long vc_num_observations(vc_calibrator* h) { return h ? h->dv.n_obs : 0; }
 int vc_num_tiles(vc_calibrator* h) { return h ? h->dv.n_tiles : 0; }
+
+// the host-only half of the IMU noise characterisation (vc_allan.hpp; the handle and the kernels: vc_allan.hip)
+int vc_allan_factors(int n_used, int per_decade, double max_fraction, int cap, int* m, double* rel_err, int* n_m) {
+  if (!n_m || n_used < 2 || per_decade < 1 || !(max_fraction > 0.0 && max_fraction <= 0.5) || (m && cap < 1)) return VC_ERR_BAD_ARG;
+  *n_m = vc::allan_factors(n_used, per_decade, max_fraction, m ? cap : 0, m, m ? rel_err : nullptr);
+  return (m && *n_m > cap) ? VC_ERR_BAD_ARG : VC_OK;
+}
+int vc_allan_fit(int n, const double* tau, const double* avar, const double* rel_err, double out[5], int* mask) {
+  if (n < 1 || !tau || !avar || !rel_err || !out || !mask) return VC_ERR_BAD_ARG;
+  const vc::AllanFit f = vc::allan_fit(n, tau, avar, rel_err);
+  out[0] = f.N; out[1] = f.B; out[2] = f.K; out[3] = f.rms_log; out[4] = (double)f.n_points;
+  *mask = f.mask;
+  return f.status;
+}
 
 }  // extern "C"

@@ -53,6 +53,7 @@ SYMBOLS = [
     "vc_register_stream", "vc_register_color", "vc_register_points", "vc_time_register",
     "vc_depthcal_create", "vc_depthcal_create_for_camera", "vc_depthcal_destroy", "vc_depthcal_get", "vc_depthcal_clear", "vc_depthcal_add", "vc_depthcal_expected",
     "vc_depthcal_sums", "vc_depthcal_fit", "vc_depthcal_get_fit", "vc_depthcal_set_fit", "vc_depthcal_apply", "vc_time_depthcal",
+    "vc_allan_create", "vc_allan_destroy", "vc_allan_get", "vc_allan_static", "vc_allan_set_range", "vc_allan_run", "vc_time_allan", "vc_allan_factors", "vc_allan_fit",
 ]
 
 
@@ -207,7 +208,7 @@ def load():
         L.vc_allreduce_calls.restype = C.c_longlong
         L.vc_last_error.restype = C.c_char_p
         for name in ("vc_destroy", "vc_detector_destroy", "vc_shard_comm_destroy", "vc_undistorter_destroy", "vc_rectifier_destroy", "vc_comparer_destroy", "vc_converter_destroy",
-                     "vc_uncertainty_destroy", "vc_stereo_uncertainty_destroy", "vc_selector_destroy", "vc_registrar_destroy", "vc_depthcal_destroy"):
+                     "vc_uncertainty_destroy", "vc_stereo_uncertainty_destroy", "vc_selector_destroy", "vc_registrar_destroy", "vc_depthcal_destroy", "vc_allan_destroy"):
             getattr(L, name).restype = None
         _lib = L
     return _lib
@@ -1621,3 +1622,85 @@ class DepthCalibrator:
         out = np.zeros(3)
         _check(self.L.vc_time_depthcal(self.h, int(n_images), int(reps), _d(out)), "time_depthcal")
         return dict(tables=out[0], accumulate=out[1], apply=out[2])
+
+
+def allan_factors(n_used, per_decade=20, max_fraction=1.0 / 9.0):
+    """The averaging factors of an Allan deviation over n_used samples and IEEE Std 952's relative standard error of every point
+    (vc_allan_factors; host only) -> (m int32 [n_m], rel_err [n_m])."""
+    L = load()
+    n_m = C.c_int(0)
+    _check(L.vc_allan_factors(int(n_used), int(per_decade), C.c_double(max_fraction), 0, None, None, C.byref(n_m)), "allan_factors")
+    m = np.zeros(n_m.value, dtype=np.int32); e = np.zeros(n_m.value)
+    _check(L.vc_allan_factors(int(n_used), int(per_decade), C.c_double(max_fraction), len(m), C.c_void_p(m.ctypes.data), C.c_void_p(e.ctypes.data), C.byref(n_m)),
+           "allan_factors")
+    return m, e
+
+
+def allan_fit(tau, avar, rel_err):
+    """White noise N, bias instability B and rate random walk K of one Allan variance curve (vc_allan_fit; host only) ->
+    dict(N, B, K, mask, rms_log, n_points, status); status 1: fewer than three usable points, 2: no feasible subset of the terms."""
+    tau = np.ascontiguousarray(tau, dtype=np.float64).reshape(-1); avar = np.ascontiguousarray(avar, dtype=np.float64).reshape(-1)
+    e = np.ascontiguousarray(rel_err, dtype=np.float64).reshape(-1)
+    if not (len(tau) == len(avar) == len(e)) or len(tau) < 1:
+        raise VicalibError("allan_fit: tau, avar and rel_err need the same length, at least 1")
+    out = np.zeros(5); mask = C.c_int(0)
+    st = _check(load().vc_allan_fit(len(tau), _d(tau), _d(avar), _d(e), C.c_void_p(out.ctypes.data), C.byref(mask)), "allan_fit")
+    return dict(N=out[0], B=out[1], K=out[2], rms_log=out[3], n_points=int(out[4]), mask=mask.value, status=st)
+
+
+class AllanAnalyzer:
+    """The noise of an IMU from a log recorded at rest (include/vicalib_amd.h: vc_allan*): the log's means and prefix sums live on the device;
+    run(m) -> (avar [6, n_m], terms [n_m]) over the range in use; static(window, gyro_thr, accel_thr) finds the longest quiet stretch and makes
+    it the range; set_range(first, count).  gyro, accel: [n, 3]; time: [n], strictly increasing.  Channels gx gy gz ax ay az."""
+
+    def __init__(self, gyro, accel, time, device=0):
+        self.L = load()
+        self.h = C.c_void_p()
+        g = np.ascontiguousarray(gyro, dtype=np.float64); a = np.ascontiguousarray(accel, dtype=np.float64); t = np.ascontiguousarray(time, dtype=np.float64).reshape(-1)
+        if g.ndim != 2 or g.shape[1] != 3 or a.shape != g.shape or len(t) != len(g):
+            raise VicalibError("AllanAnalyzer: gyro and accel need the shape [n, 3], time the length n")
+        _check(self.L.vc_allan_create(int(device), len(t), _d(g), _d(a), _d(t), C.byref(self.h)), "allan_create")
+        self.n = len(t)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.vc_allan_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+    def get(self):
+        """-> dict(n, tau0, dt_min, dt_max, means [6], irregular, range (first, count))"""
+        n = C.c_int(0); tau0 = C.c_double(0); lo = C.c_double(0); hi = C.c_double(0); means = np.zeros(6); irr = C.c_longlong(0); rng = (C.c_int * 2)()
+        _check(self.L.vc_allan_get(self.h, C.byref(n), C.byref(tau0), C.byref(lo), C.byref(hi), C.c_void_p(means.ctypes.data), C.byref(irr), rng), "allan_get")
+        return dict(n=n.value, tau0=tau0.value, dt_min=lo.value, dt_max=hi.value, means=means, irregular=irr.value, range=(rng[0], rng[1]))
+
+    def set_range(self, first, count):
+        _check(self.L.vc_allan_set_range(self.h, int(first), int(count)), "allan_set_range")
+
+    def static(self, window, gyro_thr=0.0, accel_thr=0.0):
+        """-> (status, first, count, n_quiet); status 1: no window start is quiet, the range stays"""
+        rng = (C.c_int * 2)(); nq = C.c_int(0)
+        st = _check(self.L.vc_allan_static(self.h, int(window), C.c_double(gyro_thr), C.c_double(accel_thr), rng, C.byref(nq)), "allan_static")
+        return st, rng[0], rng[1], nq.value
+
+    @staticmethod
+    def _factors(m):
+        m = np.ascontiguousarray(m, dtype=np.int32).reshape(-1)
+        if len(m) < 1:
+            raise VicalibError("AllanAnalyzer: at least one averaging factor is needed")
+        return m
+
+    def run(self, m):
+        m = self._factors(m)
+        avar = np.zeros((6, len(m))); terms = np.zeros(len(m), dtype=np.int32)
+        _check(self.L.vc_allan_run(self.h, len(m), C.c_void_p(m.ctypes.data), C.c_void_p(avar.ctypes.data), C.c_void_p(terms.ctypes.data)), "allan_run")
+        return avar, terms
+
+    def time(self, m, reps=10):
+        """mean ms of one launch set, `reps` back to back between HIP events: dict(scan, sweep)"""
+        m = self._factors(m)
+        out = np.zeros(2)
+        _check(self.L.vc_time_allan(self.h, len(m), C.c_void_p(m.ctypes.data), int(reps), C.c_void_p(out.ctypes.data)), "time_allan")
+        return dict(scan=out[0], sweep=out[1])
