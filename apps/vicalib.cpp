@@ -83,6 +83,11 @@ static void DefineFlags() {
   Define("seed_focal", "bool", "false", "Without -model_files: start every camera at the focal length its views of the target give (homographies, on the GPU) instead of 300.");
   Define("seed_focal_radius", "double", "0.5", "Corners used by -seed_focal lie within this fraction of the half diagonal of the image centre (<= 0: the whole image).");
   Define("seed_focal_fit_px", "double", "0", "Views whose homography fits worse than this many pixels rms are left out of -seed_focal (0: off).");
+  Define("seed_imu", "bool", "false", "With -imu: start the camera-IMU rotation of camera 0, the time offset, the gyro bias and gravity from the data (camera rates against gyro rates, on the GPU) instead of identity, the streams' first stamps, zero and one accelerometer sample.");
+  Define("seed_imu_range", "double", "0.5", "Time offsets searched by -seed_imu: -range ... +range seconds around the start value.");
+  Define("seed_imu_step", "double", "0", "Step of that search in seconds (0: the median IMU sample interval).");
+  Define("seed_imu_max_gap", "double", "0.5", "Consecutive frames further apart than this many seconds give -seed_imu no rate.");
+  Define("seed_imu_min_intervals", "int32", "10", "-seed_imu wants at least this many frame intervals with a rate (at least 3).");
   Define("gyro_sigma", "double", "5.3088444e-5", "Sigma of gyroscope measurements.");
   Define("accel_sigma", "double", "0.001883649", "Sigma of accel measurements.");
   Define("remove_outliers", "bool", "false", "Remove outliers and re-optimise.");
@@ -421,6 +426,45 @@ static bool ReadModelFile(const std::string& path, vic::CameraAndPose* cam, std:
   return true;
 }
 
+// rotation matrix (row-major) -> unit quaternion [x y z w], w >= 0
+static void RotationToQuat(const double* R, double* q) {
+  const double tr = R[0] + R[4] + R[8];
+  if (tr > 0.0) { const double s = 2.0 * std::sqrt(tr + 1.0); q[0] = (R[7] - R[5]) / s; q[1] = (R[2] - R[6]) / s; q[2] = (R[3] - R[1]) / s; q[3] = 0.25 * s; }
+  else if (R[0] > R[4] && R[0] > R[8]) { const double s = 2.0 * std::sqrt(1.0 + R[0] - R[4] - R[8]); q[0] = 0.25 * s; q[1] = (R[1] + R[3]) / s; q[2] = (R[2] + R[6]) / s; q[3] = (R[7] - R[5]) / s; }
+  else if (R[4] > R[8]) { const double s = 2.0 * std::sqrt(1.0 + R[4] - R[0] - R[8]); q[0] = (R[1] + R[3]) / s; q[1] = 0.25 * s; q[2] = (R[5] + R[7]) / s; q[3] = (R[2] - R[6]) / s; }
+  else { const double s = 2.0 * std::sqrt(1.0 + R[8] - R[0] - R[4]); q[0] = (R[2] + R[6]) / s; q[1] = (R[5] + R[7]) / s; q[2] = 0.25 * s; q[3] = (R[3] - R[1]) / s; }
+  const double n = (q[3] < 0.0 ? -1.0 : 1.0) / std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+  for (int k = 0; k < 4; ++k) q[k] *= n;
+}
+static void QuatMul(const double* a, const double* b, double* o) {
+  const double x = a[3] * b[0] + a[0] * b[3] + a[1] * b[2] - a[2] * b[1], y = a[3] * b[1] + a[1] * b[3] + a[2] * b[0] - a[0] * b[2];
+  const double z = a[3] * b[2] + a[2] * b[3] + a[0] * b[1] - a[1] * b[0], w = a[3] * b[3] - a[0] * b[0] - a[1] * b[1] - a[2] * b[2];
+  o[0] = x; o[1] = y; o[2] = z; o[3] = w;
+}
+static void QuatRotate(const double* q, const double* v, double* o) {
+  const double p[4] = {v[0], v[1], v[2], 0.0}, c[4] = {-q[0], -q[1], -q[2], q[3]};
+  double t[4], r[4];
+  QuatMul(q, p, t); QuatMul(t, c, r);
+  o[0] = r[0]; o[1] = r[1]; o[2] = r[2];
+}
+// poses [qx qy qz qw tx ty tz]: a b, and the inverse
+static vic::Se3 Se3Mul(const vic::Se3& a, const vic::Se3& b) {
+  vic::Se3 o;
+  QuatMul(a.v.data(), b.v.data(), o.v.data());
+  double t[3];
+  QuatRotate(a.v.data(), b.v.data() + 4, t);
+  for (int k = 0; k < 3; ++k) o.v[4 + k] = t[k] + a.v[4 + k];
+  return o;
+}
+static vic::Se3 Se3Inverse(const vic::Se3& a) {
+  vic::Se3 o;
+  for (int k = 0; k < 3; ++k) o.v[k] = -a.v[k];
+  o.v[3] = a.v[3];
+  double t[3];
+  QuatRotate(o.v.data(), a.v.data() + 4, t);
+  for (int k = 0; k < 3; ++k) o.v[4 + k] = -t[k];
+  return o;
+}
 static void RotationMatrix(const double* q, double* R) {
   const double x = q[0], y = q[1], z = q[2], w = q[3];
   R[0] = 1 - 2 * (y * y + z * z); R[1] = 2 * (x * y - z * w); R[2] = 2 * (x * z + y * w);
@@ -1755,6 +1799,15 @@ int main(int argc, char** argv) {
     if (!FlagString("model_files").empty()) { std::fprintf(stderr, "ERROR: -seed_focal and -model_files exclude each other: a model file brings its own focal length\n"); return 1; }
     if (!(FlagDouble("seed_focal_fit_px") >= 0.0)) { std::fprintf(stderr, "ERROR: illegal value for flag 'seed_focal_fit_px': expected at least 0\n"); return 1; }
   }
+  if (FlagBool("seed_imu")) {
+    if (FlagString("imu").empty()) { std::fprintf(stderr, "ERROR: -seed_imu needs -imu: there is no log to seed from\n"); return 1; }
+    if (!FlagBool("calibrate_imu")) { std::fprintf(stderr, "ERROR: -seed_imu and -nocalibrate_imu exclude each other: nothing would use the seed\n"); return 1; }
+    if (FlagBool("has_initial_guess")) { std::fprintf(stderr, "ERROR: -seed_imu and -has_initial_guess exclude each other: the guess is the start\n"); return 1; }
+    if (!(FlagDouble("seed_imu_range") > 0.0) || !std::isfinite(FlagDouble("seed_imu_range"))) { std::fprintf(stderr, "ERROR: illegal value for flag 'seed_imu_range': expected more than 0\n"); return 1; }
+    if (!std::isfinite(FlagDouble("seed_imu_step"))) { std::fprintf(stderr, "ERROR: illegal value for flag 'seed_imu_step': expected a number (0: the median sample interval)\n"); return 1; }
+    if (!(FlagDouble("seed_imu_max_gap") > 0.0)) { std::fprintf(stderr, "ERROR: illegal value for flag 'seed_imu_max_gap': expected more than 0\n"); return 1; }
+    if (FlagInt("seed_imu_min_intervals") < 1) { std::fprintf(stderr, "ERROR: illegal value for flag 'seed_imu_min_intervals': expected at least 1\n"); return 1; }
+  }
   UncertaintyOptions uncertainty;
   if (!UncertaintyFlags(&uncertainty, &err)) { std::fprintf(stderr, "ERROR: %s\n", err.c_str()); return 1; }
   StereoUncertaintyOptions stereo_uncertainty;
@@ -2017,6 +2070,82 @@ int main(int argc, char** argv) {
     }
   }
 
+  const bool guess = FlagBool("has_initial_guess");
+  // initial time offset (vicalib-task.cc:638-662): with system time the clocks are already aligned
+  double image_time_offset = 0.0;
+  {
+    double t0f = (double)frame_ids[0] / FlagDouble("frame_rate");
+    for (const Channel& ch : channels) { auto it = ch.frame_time.find(frame_ids[0]); if (it != ch.frame_time.end()) { t0f = it->second; break; } }
+    if (calibrate_imu && FlagBool("find_time_offset") && !FlagBool("use_system_time") && !imu.time.empty()) image_time_offset = imu.time[0] - t0f;
+  }
+
+  // ---- -seed_imu: R_ck of camera 0, the time offset, the gyro bias and gravity from the rates of camera 0's PnP rotations against the gyro's,
+  // one batch on -device before any calibrator exists; the one result serves every rank.  Any status but 0: a W line, today's start.
+  vic::SeedImuResult imu_seed;
+  if (FlagBool("seed_imu")) {
+    const vic::CameraAndPose& cam0 = input_cameras[0];
+    std::map<long, std::vector<const Detection*>> per_frame;
+    for (const Detection& d : channels[0].det)
+      if (d.dot < grid_w * grid_h) per_frame[d.frame].push_back(&d);
+    std::vector<int> view_model, view_off(1, 0), view_frame;
+    std::vector<double> view_K, pw, pc, frame_t(frame_ids.size()), frame_q(4 * frame_ids.size(), 0.0);
+    std::vector<unsigned char> frame_ok(frame_ids.size(), 0);
+    for (size_t k = 0; k < frame_ids.size(); ++k) {
+      const long id = frame_ids[k];
+      double t = (double)id / FlagDouble("frame_rate");
+      for (const Channel& ch : channels) { auto it = ch.frame_time.find(id); if (it != ch.frame_time.end()) { t = it->second; break; } }
+      frame_t[k] = t + image_time_offset;                                 // the time the calibrators get
+      frame_q[4 * k + 3] = 1.0;
+      auto it = per_frame.find(id);
+      if (it == per_frame.end() || it->second.size() < 4) continue;
+      for (const Detection* d : it->second) { pw.insert(pw.end(), {d->X, d->Y, d->Z}); pc.insert(pc.end(), {d->u, d->v}); }
+      view_model.push_back(cam0.model); view_off.push_back((int)(pc.size() / 2)); view_frame.push_back((int)k);
+      for (size_t j = 0; j < 10; ++j) view_K.push_back(j < cam0.params.size() ? cam0.params[j] : 0.0);
+    }
+    const int nv = (int)view_frame.size();
+    std::vector<double> T_cw(7 * (size_t)nv + 7, 0.0), rms((size_t)nv + 1, 0.0);
+    std::vector<int> n_in((size_t)nv + 1, 0), pnp_status((size_t)nv + 1, -1);
+    int rc = nv > 0 ? vc_pnp_planar_batch((int)FlagInt("device"), nv, view_model.data(), view_K.data(), view_off.data(), pw.data(), pc.data(), (int)FlagInt("pnp_ransac_its"),
+                                          FlagDouble("pnp_ransac_tol"), T_cw.data(), rms.data(), n_in.data(), nullptr, pnp_status.data())
+                    : VC_OK;
+    if (rc == VC_ERR_NO_DEVICE) { std::fprintf(stderr, "F -seed_imu: no HIP device %d\n", (int)FlagInt("device")); return 3; }
+    int n_ok = 0;
+    for (int v = 0; v < nv && rc == VC_OK; ++v) {
+      if (pnp_status[v] != 0) continue;
+      const size_t k = (size_t)view_frame[v];
+      for (int j = 0; j < 3; ++j) frame_q[4 * k + j] = -T_cw[7 * (size_t)v + j];      // R_wc = R_cw^T
+      frame_q[4 * k + 3] = T_cw[7 * (size_t)v + 3];
+      frame_ok[k] = 1; ++n_ok;
+    }
+    if (rc == VC_OK) {
+      try {
+        imu_seed = vic::SeedImu((int)FlagInt("device"), frame_t, frame_q, frame_ok, imu.time, imu.gyro, imu.accel, FlagDouble("seed_imu_range"), FlagDouble("seed_imu_step"), 8,
+                                FlagDouble("seed_imu_max_gap"), (int)FlagInt("seed_imu_min_intervals"));
+      } catch (const std::exception& e) {
+        if (std::string(e.what()).find("status -1)") != std::string::npos) { std::fprintf(stderr, "F -seed_imu: no HIP device %d\n", (int)FlagInt("device")); return 3; }
+        std::fprintf(stderr, "W -seed_imu: %s; starting without the seed\n", e.what());
+      }
+    } else std::fprintf(stderr, "W -seed_imu: the pose batch of camera 0 failed (status %d); starting without the seed\n", rc);
+    if (imu_seed.status == 0) {
+      const double* R = imu_seed.R_ck;
+      const vic::Se3 old0 = input_cameras[0].T_ck;
+      double q[4];
+      RotationToQuat(R, q);
+      for (int j = 0; j < 4; ++j) input_cameras[0].T_ck.v[j] = q[j];                    // the translation stays
+      for (size_t c = 1; c < n_cam; ++c) input_cameras[c].T_ck = Se3Mul(Se3Mul(input_cameras[c].T_ck, Se3Inverse(old0)), input_cameras[0].T_ck);      // the rig's relative poses stay
+      const double angle = 2.0 * std::atan2(std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2]), std::fabs(q[3])) * 180.0 / M_PI;
+      std::fprintf(stderr, "I -seed_imu: time offset %.6f ms, R_ck [qx qy qz qw] %.9f %.9f %.9f %.9f (%.3f degrees from identity), gyro bias %.6g %.6g %.6g, "
+                           "gravity %.6g %.6g, rms / signal %.4f, %d intervals (%d of %zu frames with a rotation)\n",
+                   1e3 * imu_seed.time_offset, q[0], q[1], q[2], q[3], angle, imu_seed.gyro_bias[0], imu_seed.gyro_bias[1], imu_seed.gyro_bias[2], imu_seed.g_dir[0],
+                   imu_seed.g_dir[1], imu_seed.rms / imu_seed.signal, imu_seed.count, n_ok, frame_ids.size());
+      if (imu_seed.rms > 0.5 * imu_seed.signal)
+        std::fprintf(stderr, "W -seed_imu: the camera's rates and the gyro's explain each other badly (rms / signal %.2f above 0.5): too little rotation about two axes?\n", imu_seed.rms / imu_seed.signal);
+    } else if (imu_seed.status > 0) {
+      const char* why = imu_seed.status == 1 ? "too few frame intervals with a rate inside the log" : imu_seed.status == 2 ? "the best offset lies on the edge of -seed_imu_range" : "a result is not finite";
+      std::fprintf(stderr, "W -seed_imu: no seed (%s; %d of %zu frames with a rotation); starting without it\n", why, n_ok, frame_ids.size());
+    }
+  }
+
   // ---- one calibrator per GPU; frames sharded contiguously, the library's own RCCL communicator does the per-iteration
   // all-reduces (-gpus 1: plain single-device run, no communicator) -----------------------------------------------------
   const int n_gpus = std::max(1, (int)FlagInt("gpus"));
@@ -2025,14 +2154,6 @@ int main(int argc, char** argv) {
   for (int r = 0; r < n_gpus; ++r) {
     try { cals[r].reset(new vic::ViCalibrator((int)FlagInt("device") + r)); }
     catch (const std::exception& e) { std::fprintf(stderr, "F %s (device %d)\n", e.what(), (int)FlagInt("device") + r); return 3; }
-  }
-  const bool guess = FlagBool("has_initial_guess");
-  // initial time offset (vicalib-task.cc:638-662): with system time the clocks are already aligned
-  double image_time_offset = 0.0;
-  {
-    double t0f = (double)frame_ids[0] / FlagDouble("frame_rate");
-    for (const Channel& ch : channels) { auto it = ch.frame_time.find(frame_ids[0]); if (it != ch.frame_time.end()) { t0f = it->second; break; } }
-    if (calibrate_imu && FlagBool("find_time_offset") && !FlagBool("use_system_time") && !imu.time.empty()) image_time_offset = imu.time[0] - t0f;
   }
   long n_obs = 0; int seeded = 0;
   std::vector<std::vector<const Detection*>> rank_corners((size_t)n_gpus);      // (report) the detection behind every corner, in the order it was added
@@ -2076,6 +2197,11 @@ int main(int argc, char** argv) {
         if (want_report) rank_corners[r].insert(rank_corners[r].end(), kv.second.begin(), kv.second.end());
         n_obs += (long)kv.second.size();
       }
+    }
+    if (imu_seed.status == 0) {                                                            // -seed_imu: the same start on every rank
+      const double b[6] = {imu_seed.gyro_bias[0], imu_seed.gyro_bias[1], imu_seed.gyro_bias[2], 0, 0, 0};
+      cal.SetTimeOffset(imu_seed.time_offset); cal.SetBiases(b);
+      if (vc_set_gravity(cal.handle(), imu_seed.g_dir) != VC_OK) { std::fprintf(stderr, "F the gravity seed was rejected\n"); return 1; }
     }
     cal.SetPnPRansac((int)FlagInt("pnp_ransac_its"), FlagDouble("pnp_ransac_tol"));
     cal.SetPnPDevice(FlagBool("pnp_device"));

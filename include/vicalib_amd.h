@@ -954,6 +954,46 @@ int vc_allan_factors(int n_used, int per_decade, double max_fraction, int cap, i
  * Returns 0, 1 (fewer than three points, the model's terms: nothing fitted) or 2 (no feasible subset); VC_ERR_BAD_ARG: a null pointer, n < 1. */
 int vc_allan_fit(int n, const double* tau, const double* avar, const double* rel_err, double out[5], int* mask);
 
+/* ---- the inertial seed: camera-IMU rotation, time offset, gyro bias and gravity before anything is solved ------------------------------
+ * On the device, no handle.  The frames bring the camera's rotation in the world (frame_q_wc, [x y z w], e.g. from vc_pnp_planar_batch;
+ * frame_ok = 0: a frame without one), the log n_samples (2 .. 2^24; more is VC_ERR_UNSUPPORTED) of gyro and accelerometer.  A sample stamped
+ * t was taken at image-clock time t + offset, T_wk = T_wc T_ck and w_c = R_ck (z_g + b_g): the scale factors are taken as 1.
+ *   a_i    = log(R_wc,i^T R_wc,i+1) / (t_{i+1} - t_i), valid when both frames are ok and 0 < t_{i+1} - t_i <= max_gap_s
+ *   b_i(d) = the mean of the piecewise-linear gyro signal over [t_i - d, t_{i+1} - d], from its prefix integrals; an interval that leaves
+ *            the log is not valid at that lag
+ * Per lag d, over the n valid intervals: R = Horn's rotation with a - am = R (b - bm), J = sum |R (b - bm) - (a - am)|^2 / n evaluated as
+ * (Sa + Sb - 2 tr(R H)) / n, bias = R^T am - bm.  A lag with fewer than max(3, min_intervals) intervals has J = +inf, R = I, bias = 0; its
+ * count is still returned.  moments (18 per lag): n, sum a', sum b, sum |a'|^2, sum |b|^2, sum b a'^T (row-major), a' = a minus the rate of
+ * the first valid interval.  Any output pointer may be NULL.  Everything is fp64; no sum's order depends on anything but the sizes: two
+ * runs give the same bits, a lag gives the same bits alone or among others, and the gyro channels permuted cyclically give the same J
+ * bits with the columns of R permuted.
+ * VC_ERR_BAD_ARG comes before any device call: a null required pointer, n_frames < 2, n_samples < 2, n_lags < 1, a time that is not finite
+ * or not strictly increasing (frames and samples), a sample or a lag that is not finite, a quaternion of an ok frame with a norm outside
+ * [0.5, 2], max_gap_s <= 0, min_intervals < 1.  VC_ERR_NO_DEVICE without that device: there is no host fallback. */
+int vc_seed_imu_sweep(int device, int n_frames, const double* frame_t, const double* frame_q_wc /* n_frames x 4 */, const unsigned char* frame_ok,
+                      int n_samples, const double* imu_t, const double* gyro /* n_samples x 3 */, const double* accel /* n_samples x 3 */,
+                      double max_gap_s, int min_intervals, int n_lags, const double* lags,
+                      double* J, double* R /* n_lags x 9 */, double* bias /* n_lags x 3 */, int* count, double* moments /* n_lags x 18 */);
+/* The seed.  A coarse lattice of lags -range_s .. +range_s at step_s (<= 0: the median sample interval), the lowest J (the lowest index
+ * among equals); a fine lattice of 4 fine + 1 lags at step_s / fine around it and a parabola through the three points around its minimum;
+ * one more lag at the refined offset gives R_ck (row-major), gyro_bias, rms = sqrt(J), signal = sqrt(Sa / n), count.  Gravity at that
+ * (R_ck, offset): u = normalise(sum R_wc,i R_ck abar_i), abar_i the mean accelerometer reading over the interval; g_dir = (asin(u_y),
+ * asin(-u_x / cos g_dir[0])) as vc_get_gravity reports it.
+ * status: 0 ok; 1 fewer than max(3, min_intervals) valid intervals at every lag; 2 the minimum lies on the edge of the range (the offset
+ * is outside it); 3 a result that is not finite.  With a status other than 0 only status and the coarse curve are written.  rms / signal
+ * near 1 means the rates do not explain each other: the caller declines the seed.  The coarse curve: coarse_cap entries of room in
+ * coarse_lags / coarse_J (either may be NULL), *n_coarse (nullable) the lattice's size.  VC_ERR_BAD_ARG as vc_seed_imu_sweep, and for
+ * range_s <= 0, fine < 1, a lattice of more than 2^20 lags, status == NULL. */
+int vc_seed_imu(int device, int n_frames, const double* frame_t, const double* frame_q_wc, const unsigned char* frame_ok, int n_samples,
+                const double* imu_t, const double* gyro, const double* accel, double max_gap_s, int min_intervals, double range_s, double step_s,
+                int fine, double* time_offset, double R_ck[9], double gyro_bias[3], double g_dir[2], double* rms, double* signal, int* count,
+                int* status, int coarse_cap, double* coarse_lags, double* coarse_J, int* n_coarse);
+/* Mean kernel times in ms, `reps` launches back to back between two events each: out_ms[0] the prefix integrals and the camera rates,
+ * [1] the sweep of those lags with its finishing kernel, [2] the gravity sums at lags[0]. */
+int vc_time_seed_imu(int device, int n_frames, const double* frame_t, const double* frame_q_wc, const unsigned char* frame_ok, int n_samples,
+                     const double* imu_t, const double* gyro, const double* accel, double max_gap_s, int min_intervals, int n_lags,
+                     const double* lags, int reps, double out_ms[3]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -69,6 +69,43 @@ inline SeedFocalResult SeedFocalBatch(int device, const std::vector<int>& view_c
   return r;
 }
 
+// The inertial seed (vc_seed_imu, vc_seed_imu_sweep; on the device, no handle): the rotation camera <- IMU, the time offset, the gyro bias and the
+// direction of gravity from the frames' camera rotations (frame_q_wc: n x 4, [x y z w]; frame_ok: 0 = no rotation) and the IMU log.
+struct SeedImuResult {
+  int status = -1, count = 0;                   // 0 ok, 1 too few intervals, 2 the minimum on the edge of the range, 3 not finite
+  double time_offset = 0, R_ck[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, gyro_bias[3] = {0, 0, 0}, g_dir[2] = {0, 0}, rms = 0, signal = 0;      // filled with status 0
+  std::vector<double> coarse_lags, coarse_J;
+};
+struct SeedImuSweepResult { std::vector<double> J, R, bias, moments; std::vector<int> count; };      // per lag: 1, 9, 3, 18, 1
+inline SeedImuSweepResult SeedImuSweep(int device, const std::vector<double>& frame_t, const std::vector<double>& frame_q_wc, const std::vector<unsigned char>& frame_ok,
+                                       const std::vector<double>& imu_t, const std::vector<double>& gyro, const std::vector<double>& accel,
+                                       const std::vector<double>& lags, double max_gap_s = 0.5, int min_intervals = 10) {
+  const size_t nf = frame_t.size(), ns = imu_t.size(), nl = lags.size();
+  if (frame_q_wc.size() != 4 * nf || frame_ok.size() != nf || gyro.size() != 3 * ns || accel.size() != 3 * ns) throw std::runtime_error("vicalib_amd: SeedImuSweep: array sizes disagree");
+  SeedImuSweepResult r;
+  r.J.resize(nl); r.R.resize(9 * nl); r.bias.resize(3 * nl); r.moments.resize(18 * nl); r.count.resize(nl);
+  vc_checked(vc_seed_imu_sweep(device, (int)nf, frame_t.data(), frame_q_wc.data(), frame_ok.data(), (int)ns, imu_t.data(), gyro.data(), accel.data(), max_gap_s,
+                               min_intervals, (int)nl, lags.data(), r.J.data(), r.R.data(), r.bias.data(), r.count.data(), r.moments.data()), "SeedImuSweep");
+  return r;
+}
+inline SeedImuResult SeedImu(int device, const std::vector<double>& frame_t, const std::vector<double>& frame_q_wc, const std::vector<unsigned char>& frame_ok,
+                             const std::vector<double>& imu_t, const std::vector<double>& gyro, const std::vector<double>& accel, double range_s = 0.5,
+                             double step_s = 0.0, int fine = 8, double max_gap_s = 0.5, int min_intervals = 10) {
+  const size_t nf = frame_t.size(), ns = imu_t.size();
+  if (frame_q_wc.size() != 4 * nf || frame_ok.size() != nf || gyro.size() != 3 * ns || accel.size() != 3 * ns) throw std::runtime_error("vicalib_amd: SeedImu: array sizes disagree");
+  SeedImuResult r;
+  int n_coarse = 0;
+  for (int pass = 0; pass < 2; ++pass) {                                     // (the coarse curve is caller-sized: a longer one is fetched by a second call)
+    r.coarse_lags.assign((size_t)(n_coarse > 4096 ? n_coarse : 4096), 0.0); r.coarse_J.assign(r.coarse_lags.size(), 0.0);
+    vc_checked(vc_seed_imu(device, (int)nf, frame_t.data(), frame_q_wc.data(), frame_ok.data(), (int)ns, imu_t.data(), gyro.data(), accel.data(), max_gap_s,
+                           min_intervals, range_s, step_s, fine, &r.time_offset, r.R_ck, r.gyro_bias, r.g_dir, &r.rms, &r.signal, &r.count, &r.status,
+                           (int)r.coarse_lags.size(), r.coarse_lags.data(), r.coarse_J.data(), &n_coarse), "SeedImu");
+    if ((size_t)n_coarse <= r.coarse_lags.size()) break;
+  }
+  r.coarse_lags.resize((size_t)n_coarse); r.coarse_J.resize((size_t)n_coarse);
+  return r;
+}
+
 class ViCalibrator {
  public:
   explicit ViCalibrator(int device = 0) {

@@ -54,6 +54,7 @@ SYMBOLS = [
     "vc_depthcal_create", "vc_depthcal_create_for_camera", "vc_depthcal_destroy", "vc_depthcal_get", "vc_depthcal_clear", "vc_depthcal_add", "vc_depthcal_expected",
     "vc_depthcal_sums", "vc_depthcal_fit", "vc_depthcal_get_fit", "vc_depthcal_set_fit", "vc_depthcal_apply", "vc_time_depthcal",
     "vc_allan_create", "vc_allan_destroy", "vc_allan_get", "vc_allan_static", "vc_allan_set_range", "vc_allan_run", "vc_time_allan", "vc_allan_factors", "vc_allan_fit",
+    "vc_seed_imu_sweep", "vc_seed_imu", "vc_time_seed_imu",
 ]
 
 
@@ -187,6 +188,63 @@ def time_seed_focal_batch(view_cam, cam_pp, cam_radius, view_off, p_w, p_c, min_
     _check(load().vc_time_seed_focal_batch(int(device), len(cam), ip(cam_arg), len(rad), _d(pp), _d(rad), ip(off), _d(p_w), _d(p_c), int(min_corners),
                                            C.c_double(max_fit_px), C.c_double(min_tilt_deg), int(reps), C.byref(ms)), "time_seed_focal_batch")
     return ms.value
+
+
+def _seed_imu_arrays(frame_t, frame_q_wc, frame_ok, imu_t, gyro, accel):
+    ft = np.ascontiguousarray(frame_t, dtype=np.float64).reshape(-1)
+    fq = np.ascontiguousarray(frame_q_wc, dtype=np.float64)
+    ok = np.ascontiguousarray(np.asarray(frame_ok) != 0, dtype=np.uint8).reshape(-1)
+    it = np.ascontiguousarray(imu_t, dtype=np.float64).reshape(-1)
+    g = np.ascontiguousarray(gyro, dtype=np.float64); a = np.ascontiguousarray(accel, dtype=np.float64)
+    if fq.shape != (len(ft), 4) or len(ok) != len(ft) or g.shape != (len(it), 3) or a.shape != (len(it), 3):
+        raise VicalibError("seed_imu: frame_q_wc needs the shape [n_frames, 4], frame_ok the length n_frames, gyro and accel the shape [n_samples, 3]")
+    return ft, fq, ok, it, g, a
+
+
+def seed_imu_sweep(frame_t, frame_q_wc, frame_ok, imu_t, gyro, accel, lags, max_gap_s=0.5, min_intervals=10, device=0):
+    """The fit of the camera rates to the gyro rates at every lag, on the device (vc_seed_imu_sweep).  frame_q_wc: [x y z w] of R_wc per frame
+    (frame_ok = 0: none); returns J [n_lags], R [n_lags, 3, 3], bias [n_lags, 3], count [n_lags], moments [n_lags, 18]."""
+    ft, fq, ok, it, g, a = _seed_imu_arrays(frame_t, frame_q_wc, frame_ok, imu_t, gyro, accel)
+    lags = np.ascontiguousarray(lags, dtype=np.float64).reshape(-1)
+    n = len(lags)
+    J = np.zeros(max(n, 1)); R = np.zeros((max(n, 1), 3, 3)); bias = np.zeros((max(n, 1), 3)); count = np.zeros(max(n, 1), dtype=np.int32); mom = np.zeros((max(n, 1), 18))
+    ip = lambda x: x.ctypes.data_as(C.c_void_p)
+    _check(load().vc_seed_imu_sweep(int(device), len(ft), _d(ft), _d(fq), ip(ok), len(it), _d(it), _d(g), _d(a), C.c_double(max_gap_s), int(min_intervals), n,
+                                    _d(lags) if n else None, _d(J), _d(R), _d(bias), ip(count), _d(mom)), "seed_imu_sweep")
+    return dict(J=J[:n], R=R[:n], bias=bias[:n], count=count[:n], moments=mom[:n])
+
+
+def seed_imu(frame_t, frame_q_wc, frame_ok, imu_t, gyro, accel, range_s=0.5, step_s=0.0, fine=8, max_gap_s=0.5, min_intervals=10, device=0):
+    """The inertial seed (vc_seed_imu): status (0 ok, 1 too few intervals, 2 the minimum on the edge of the range, 3 not finite), the coarse
+    curve (coarse_lags, coarse_J) and, with status 0, time_offset, R_ck [3, 3], gyro_bias, g_dir, rms, signal, count."""
+    ft, fq, ok, it, g, a = _seed_imu_arrays(frame_t, frame_q_wc, frame_ok, imu_t, gyro, accel)
+    L = load()
+    ip = lambda x: x.ctypes.data_as(C.c_void_p)
+    off = C.c_double(0); rms = C.c_double(0); sig = C.c_double(0); count = C.c_int(0); status = C.c_int(-1); n_coarse = C.c_int(0)
+    R = np.zeros((3, 3)); bias = np.zeros(3); g_dir = np.zeros(2)
+    cap = 0
+    for _ in range(2):                    # the coarse curve is caller-sized: the first call reports its length, a second one fetches a longer curve
+        lags = np.zeros(max(cap, 4096)); J = np.zeros(max(cap, 4096))
+        _check(L.vc_seed_imu(int(device), len(ft), _d(ft), _d(fq), ip(ok), len(it), _d(it), _d(g), _d(a), C.c_double(max_gap_s), int(min_intervals),
+                             C.c_double(range_s), C.c_double(step_s), int(fine), C.byref(off), _d(R), _d(bias), _d(g_dir), C.byref(rms), C.byref(sig),
+                             C.byref(count), C.byref(status), len(lags), _d(lags), _d(J), C.byref(n_coarse)), "seed_imu")
+        if n_coarse.value <= len(lags):
+            break
+        cap = n_coarse.value
+    out = dict(status=status.value, coarse_lags=lags[:n_coarse.value].copy(), coarse_J=J[:n_coarse.value].copy())
+    if status.value == 0:
+        out.update(time_offset=off.value, R_ck=R, gyro_bias=bias, g_dir=g_dir, rms=rms.value, signal=sig.value, count=count.value)
+    return out
+
+
+def time_seed_imu(frame_t, frame_q_wc, frame_ok, imu_t, gyro, accel, lags, max_gap_s=0.5, min_intervals=10, device=0, reps=10):
+    """mean kernel times in ms (vc_time_seed_imu: HIP events, launches back to back): prepare (prefix integrals, camera rates), sweep, gravity"""
+    ft, fq, ok, it, g, a = _seed_imu_arrays(frame_t, frame_q_wc, frame_ok, imu_t, gyro, accel)
+    lags = np.ascontiguousarray(lags, dtype=np.float64).reshape(-1)
+    ms = np.zeros(3)
+    _check(load().vc_time_seed_imu(int(device), len(ft), _d(ft), _d(fq), ok.ctypes.data_as(C.c_void_p), len(it), _d(it), _d(g), _d(a), C.c_double(max_gap_s),
+                                   int(min_intervals), len(lags), _d(lags), int(reps), _d(ms)), "time_seed_imu")
+    return dict(prepare=ms[0], sweep=ms[1], gravity=ms[2])
 
 
 def load():
