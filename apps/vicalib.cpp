@@ -192,6 +192,21 @@ struct Run {
   std::vector<double> rmse;
   SelectHeld select_held;
   std::vector<std::string> incomplete;                                          // "-flag: the files are" of every output behind the result that failed
+  // -dot_bias_rounds: the radius of every dot of the target by dot id, the detections as they were read (per channel, u v per detection), and
+  // the last round's table for dot_bias.csv
+  int dot_bias_rounds = 0;
+  std::vector<double> dot_radius;
+  std::vector<std::vector<double>> original_uv;
+  struct DotBiasRow { long frame; int cam, dot; double bu, bv, radius_px; int status; };
+  std::vector<DotBiasRow> dot_bias_rows;
+};
+// what a calibrator is rebuilt from between the rounds of -dot_bias_rounds: the result of the round before
+struct Restart {
+  std::vector<vic::CameraAndPose> cameras;
+  std::vector<vic::VicalibFrame> frames;
+  std::array<double, 6> biases, scale_factor;
+  std::array<double, 2> gravity;
+  double time_offset = 0.0;
 };
 
 // A stage that can end the program returns true to go on and false to end it with exit status *rc.  Stop says why on stderr.
@@ -238,6 +253,15 @@ static bool CheckFlags(Run& s, int* rc) {
   if (FlagBool("seed_focal")) {
     if (!FlagString("model_files").empty()) return FlagError(rc, "-seed_focal and -model_files exclude each other: a model file brings its own focal length");
     if (!(FlagDouble("seed_focal_fit_px") >= 0.0)) return FlagError(rc, "illegal value for flag 'seed_focal_fit_px': expected at least 0");
+  }
+  s.dot_bias_rounds = (int)FlagInt("dot_bias_rounds");
+  if (s.dot_bias_rounds < 0) return FlagError(rc, "illegal value for flag 'dot_bias_rounds': expected at least 0");
+  if (s.dot_bias_rounds > 0) {
+    if (FlagInt("gpus") > 1) return FlagError(rc, "-dot_bias_rounds needs -gpus 1: the rounds rebuild one calibrator from its own result");
+    if (s.holdout_every > 0) return FlagError(rc, "-dot_bias_rounds and -holdout_every exclude each other: held-out frames would keep their bias");
+    for (const char* f : {"dot_radius", "grid_large_rad", "grid_small_rad"})
+      if (!(FlagDouble(f) >= 0.0) || !std::isfinite(FlagDouble(f)))
+        return FlagError(rc, std::string("illegal value for flag '") + f + "' with -dot_bias_rounds: expected a radius in metres, at least 0");
   }
   if (FlagBool("seed_imu")) {
     if (FlagString("imu").empty()) return FlagError(rc, "-seed_imu needs -imu: there is no log to seed from");
@@ -374,6 +398,19 @@ static bool ReadSensors(Run& s, int* rc) {
   if (s.have_imu && !ReadImu(StripScheme(FlagString("imu")), FlagBool("use_system_time"), &s.imu, &err)) return Stop(rc, 1, "F %s\n", err.c_str());
   s.calibrate_imu = FlagBool("calibrate_imu");
   if (s.calibrate_imu && !s.have_imu) { std::fprintf(stderr, "W -calibrate_imu without -imu: calibrating the cameras only\n"); s.calibrate_imu = false; }
+  return true;
+}
+
+// ---- -dot_bias_rounds: the radius of every dot of the target by dot id (row * grid_width + col).  -dot_radius gives all dots one radius; else
+// a dot is large or small by the target's pattern: -grid_pattern_file, or generated from -grid_height / -grid_width (a preset's, with
+// -grid_preset) and -grid_seed by the library's own generator, as for image input
+static bool DotRadii(Run& s, int* rc) {
+  if (FlagDouble("dot_radius") > 0.0) { s.dot_radius.assign((size_t)s.grid_w * s.grid_h, FlagDouble("dot_radius")); return true; }
+  if (FlagString("grid_pattern_file").empty() && FlagString("grid_preset") == "medium")
+    return Stop(rc, 1, "F -dot_bias_rounds with -grid_preset medium: the preset's size is not known here -- pass the target's pattern with -grid_pattern_file, or -dot_radius\n");
+  TargetSpec tg;
+  if (!ReadTarget(s, "", &tg, rc)) return false;
+  for (int big : tg.pattern) s.dot_radius.push_back(FlagDouble(big ? "grid_large_rad" : "grid_small_rad"));
   return true;
 }
 
@@ -561,10 +598,12 @@ static bool SeedImu(Run& s, int* rc) {
 
 // ---- one calibrator per GPU; frames sharded contiguously, the library's own RCCL communicator does the per-iteration
 // all-reduces (-gpus 1: plain single-device run, no communicator) -----------------------------------------------------
-static bool LoadCalibrators(Run& s, int* rc) {
+// from: the result a round of -dot_bias_rounds starts from (cameras, frame poses and velocities, biases, scale factors, gravity, time offset; the
+// optimisation flags of -has_initial_guess), instead of the input cameras and the PnP seeds
+static bool LoadCalibrators(Run& s, int* rc, const Restart* from = nullptr) {
   const int n_gpus = std::max(1, (int)FlagInt("gpus"));
   const size_t n_cam = s.channels.size(), n_frames = s.frame_ids.size();
-  const bool guess = FlagBool("has_initial_guess");
+  const bool guess = from ? true : FlagBool("has_initial_guess");
   if ((size_t)n_gpus * 2 > n_frames) return Stop(rc, 1, "F -gpus %d needs at least %d frames\n", n_gpus, 2 * n_gpus);
   s.cals.resize((size_t)n_gpus);
   for (int r = 0; r < n_gpus; ++r) {
@@ -579,7 +618,7 @@ static bool LoadCalibrators(Run& s, int* rc) {
     const double zeros[6] = {0, 0, 0, 0, 0, 0}, ones[6] = {1, 1, 1, 1, 1, 1};
     cal.SetBiases(zeros); cal.SetScaleFactor(ones);
     cal.FixCameraIntrinsics(!FlagBool("calibrate_intrinsics"));                            // vicalib-task.cc:128
-    for (const vic::CameraAndPose& c : s.input_cameras)
+    for (const vic::CameraAndPose& c : from ? from->cameras : s.input_cameras)
       if (cal.AddCamera(c) < 0) return Stop(rc, 1, "F AddCamera failed (model %s, %zu parameters)\n", ModelName(c.model), c.params.size());
     // every shard gets the whole IMU stream: its last block reaches into the next shard's first frame
     if (s.have_imu && !s.imu.time.empty() && cal.AddImuMeasurements((int)s.imu.time.size(), s.imu.gyro.data(), s.imu.accel.data(), s.imu.time.data()) != VC_OK)
@@ -593,20 +632,27 @@ static bool LoadCalibrators(Run& s, int* rc) {
       for (const auto& kv : DetectionsByFrame(s.channels[c], frame_index, s.grid_w * s.grid_h)) {
         pw.clear(); pc.clear();
         AppendCorners(kv.second, &pw, &pc);
-        if (FlagBool("output_conics"))
+        if (FlagBool("output_conics") && !from)
           for (const Detection* d : kv.second) std::printf("%ld,%d,%.10g,%.10g,%.10g,%.10g,%.10g\n", d->frame, d->dot, d->u, d->v, d->X, d->Y, d->Z);
         cal.AddObservations(kv.first, c, (int)kv.second.size(), pw.data(), pc.data());
         if (s.want_report) s.rank_corners[r].insert(s.rank_corners[r].end(), kv.second.begin(), kv.second.end());
         n_obs += (long)kv.second.size();
       }
-    if (s.imu_seed.status == 0) {                                                          // -seed_imu: the same start on every rank
+    if (from) {
+      for (size_t k = lo; k < hi; ++k) cal.SetFramePose((int)(k - lo), from->frames[k].t_wp_);
+      std::vector<double> v_w;
+      for (size_t k = lo; k < hi; ++k) v_w.insert(v_w.end(), from->frames[k].v_w_.begin(), from->frames[k].v_w_.end());
+      cal.SetBiases(from->biases.data()); cal.SetScaleFactor(from->scale_factor.data()); cal.SetTimeOffset(from->time_offset);
+      if (vc_set_frame_velocities(cal.handle(), v_w.data(), (int)(hi - lo)) != VC_OK) return Stop(rc, 1, "F the frame velocities of the result were rejected\n");
+      if (s.calibrate_imu && vc_set_gravity(cal.handle(), from->gravity.data()) != VC_OK) return Stop(rc, 1, "F the gravity of the result was rejected\n");
+    } else if (s.imu_seed.status == 0) {                                                   // -seed_imu: the same start on every rank
       const double b[6] = {s.imu_seed.gyro_bias[0], s.imu_seed.gyro_bias[1], s.imu_seed.gyro_bias[2], 0, 0, 0};
       cal.SetTimeOffset(s.imu_seed.time_offset); cal.SetBiases(b);
       if (vc_set_gravity(cal.handle(), s.imu_seed.g_dir) != VC_OK) return Stop(rc, 1, "F the gravity seed was rejected\n");
     }
     cal.SetPnPRansac((int)FlagInt("pnp_ransac_its"), FlagDouble("pnp_ransac_tol"));
     cal.SetPnPDevice(FlagBool("pnp_device"));
-    seeded += cal.InitFramePosesPnP();
+    if (!from) seeded += cal.InitFramePosesPnP();
     // ---- VicalibTask::Start(has_initial_guess) (vicalib-task.cc:226-234) + flags read inside the calibrator ---------
     cal.SetOptimizationFlags(guess, guess && s.calibrate_imu, !guess, FlagBool("find_time_offset"));
     cal.SetFunctionTolerance(FlagDouble("function_tolerance"));
@@ -614,6 +660,7 @@ static bool LoadCalibrators(Run& s, int* rc) {
     cal.SetCalibrateImu(s.calibrate_imu);
     cal.SetRemoveOutliers(FlagBool("remove_outliers"), FlagDouble("outlier_threshold"));
   }
+  if (from) return true;
   std::fprintf(stderr, "I %zu cameras, %zu frames on %d GPU(s) (%d with a PnP seed), %ld corner observations, %zu IMU samples\n", n_cam, n_frames, n_gpus, seeded, n_obs, s.imu.time.size());
   return true;
 }
@@ -647,6 +694,82 @@ static void Solve(Run& s) {
   for (auto& c : s.cals) c->Stop();
   s.secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   for (auto& c : s.cals) for (size_t i = 0; i < c->NumFrames(); ++i) s.all_frames.push_back(c->GetFrame(i));
+}
+
+// ---- one round of -dot_bias_rounds: the bias of every calibrated observation predicted at the result (its cameras and T_ck, the frames' T_wk) in
+// one batch on -device, subtracted from the ORIGINAL detections (nothing accumulates round over round), the calibrator rebuilt from the result
+// and solved again.  An observation whose bias cannot be predicted (status != 0) keeps its original pixel.
+static bool DotBiasRound(Run& s, int round, int* rc) {
+  const size_t n_cam = s.channels.size();
+  Restart at;
+  {
+    vic::ViCalibrator& cal = *s.cals[0];
+    at.cameras = CamerasAtResult(cal, s.input_cameras);
+    at.frames = s.all_frames;
+    at.biases = cal.GetBiases(); at.scale_factor = cal.GetScaleFactor(); at.gravity = cal.GetGravity(); at.time_offset = cal.time_offset();
+  }
+  const std::vector<double> rmse_before = s.cals[0]->GetCameraProjRMSE();
+  if (s.original_uv.empty()) {
+    s.original_uv.resize(n_cam);
+    for (size_t c = 0; c < n_cam; ++c)
+      for (const Detection& d : s.channels[c].det) s.original_uv[c].insert(s.original_uv[c].end(), {d.u, d.v});
+  }
+  const std::map<long, int> fit_index = FrameIndex(s.frame_ids);
+  std::vector<int> view_model, view_off(1, 0), obs_cam;
+  std::vector<double> view_K, view_T, pw, radius;
+  std::vector<Detection*> obs;
+  for (size_t c = 0; c < n_cam; ++c)
+    for (const auto& kv : DetectionsByFrame(s.channels[c], fit_index, s.grid_w * s.grid_h)) {
+      const vic::Se3 T_cw = Se3Mul(at.cameras[c].T_ck, Se3Inverse(at.frames[(size_t)kv.first].t_wp_));
+      view_model.push_back(at.cameras[c].model);
+      for (size_t j = 0; j < 10; ++j) view_K.push_back(j < at.cameras[c].params.size() ? at.cameras[c].params[j] : 0.0);
+      view_T.insert(view_T.end(), T_cw.v.begin(), T_cw.v.end());
+      for (const Detection* d : kv.second) {
+        pw.insert(pw.end(), {d->X, d->Y, d->Z});
+        radius.push_back((size_t)d->dot < s.dot_radius.size() && d->dot >= 0 ? s.dot_radius[(size_t)d->dot] : 0.0);
+        obs.push_back(const_cast<Detection*>(d)); obs_cam.push_back((int)c);          // (an element of s.channels[c].det, which this run owns)
+      }
+      view_off.push_back((int)obs.size());
+    }
+  vic::DotBiasResult db;
+  try { db = vic::DotBiasBatch(Device(), view_model, view_K, view_T, view_off, pw, radius); }
+  catch (const std::exception& e) { return Stop(rc, 3, "F -dot_bias_rounds: %s (device %d)\n", e.what(), Device()); }
+  std::vector<double> sum2(n_cam, 0.0), worst(n_cam, 0.0);
+  std::vector<long> count(n_cam, 0), refused(n_cam, 0);
+  s.dot_bias_rows.clear();
+  for (size_t i = 0; i < obs.size(); ++i) {
+    Detection* d = obs[i];
+    const size_t c = (size_t)obs_cam[i], k = (size_t)(d - s.channels[c].det.data());
+    const bool ok = db.status[i] == 0;
+    const double bu = ok ? db.bias[2 * i] : 0.0, bv = ok ? db.bias[2 * i + 1] : 0.0;
+    d->u = s.original_uv[c][2 * k] - bu; d->v = s.original_uv[c][2 * k + 1] - bv;
+    ++count[c];
+    if (ok) { sum2[c] += bu * bu + bv * bv; worst[c] = std::max(worst[c], std::sqrt(bu * bu + bv * bv)); } else ++refused[c];
+    s.dot_bias_rows.push_back(Run::DotBiasRow{d->frame, (int)c, d->dot, bu, bv, ok ? db.radius_px[i] : 0.0, db.status[i]});
+  }
+  s.cals.clear(); s.rank_corners.clear(); s.all_frames.clear();
+  if (!LoadCalibrators(s, rc, &at)) return false;
+  Solve(s);
+  const std::vector<double> rmse_after = s.cals[0]->GetCameraProjRMSE();
+  long refused_all = 0;
+  for (size_t c = 0; c < n_cam; ++c) {
+    const long used = count[c] - refused[c];
+    std::fprintf(stderr, "I dot bias round %d, camera %zu: bias rms %.6f px, max %.6f px over %ld observations, %ld without a prediction, RMSE %.6g -> %.6g px\n", round, c,
+                 used > 0 ? std::sqrt(sum2[c] / used) : 0.0, worst[c], count[c], refused[c], rmse_before[c], rmse_after[c]);
+    refused_all += refused[c];
+  }
+  if (refused_all > 0) std::fprintf(stderr, "W dot bias round %d: %ld observations keep their original pixel (no bias could be predicted: see the status column of dot_bias.csv with -report_dir)\n", round, refused_all);
+  return true;
+}
+// dot_bias.csv of the last round, beside the residual report
+static void WriteDotBiasCsv(const Run& s) {
+  const std::string dir = FlagString("report_dir");
+  (void)mkdir(dir.c_str(), 0777);
+  FILE* f = std::fopen((dir + "/dot_bias.csv").c_str(), "w");
+  if (!f) { std::fprintf(stderr, "E cannot write dot_bias.csv into %s\n", dir.c_str()); return; }
+  std::fprintf(f, "frame,camera,dot,bu,bv,radius_px,status\n");
+  for (const Run::DotBiasRow& r : s.dot_bias_rows) std::fprintf(f, "%ld,%d,%d,%.10g,%.10g,%.10g,%d\n", r.frame, r.cam, r.dot, r.bu, r.bv, r.radius_px, r.status);
+  std::fclose(f);
 }
 
 // ---- Finish + PrintResults (vicalibrator.h:536-544) ------------------------------------------------------------------
@@ -954,14 +1077,19 @@ int main(int argc, char** argv) {
   if (err == "help") return Usage(0);
   if (!parsed && !FlagError(&rc, err)) return rc;
   Run s;
-  if (!CheckFlags(s, &rc) || !RunStandAloneMode(s, &rc) || !ReadSensors(s, &rc) || !StartCameras(s, &rc) || !ChooseFrames(s, &rc)) return rc;
+  if (!CheckFlags(s, &rc) || !RunStandAloneMode(s, &rc) || !ReadSensors(s, &rc)) return rc;
+  if (s.dot_bias_rounds > 0 && !DotRadii(s, &rc)) return rc;
+  if (!StartCameras(s, &rc) || !ChooseFrames(s, &rc)) return rc;
   if (FlagBool("seed_focal") && !SeedFocal(s, &rc)) return rc;
   s.image_time_offset = InitialTimeOffset(s);
   if (FlagBool("seed_imu") && !SeedImu(s, &rc)) return rc;
   if (!LoadCalibrators(s, &rc) || !SetupCommunicator(s, &rc)) return rc;
   Solve(s);
+  for (int round = 1; round <= s.dot_bias_rounds; ++round)
+    if (!DotBiasRound(s, round, &rc)) return rc;
   PrintResults(s);
   if (s.want_report) ResidualReport(s);
+  if (s.dot_bias_rounds > 0 && !FlagString("report_dir").empty()) WriteDotBiasCsv(s);
   if (!s.held_ids.empty()) ScoreHeldOut(s);
   s.cals[0]->WriteCameraModels(FlagString("output"));      // WriteCalibration (vicalib-engine.cc:353-372)
   PostResultOutputs(s);

@@ -47,6 +47,10 @@ static void DefineEngineFlags() {      // vicalib-engine.cc:30-104
   Define("seed_imu_step", "double", "0", "Step of that search in seconds (0: the median IMU sample interval).");
   Define("seed_imu_max_gap", "double", "0.5", "Consecutive frames further apart than this many seconds give -seed_imu no rate.");
   Define("seed_imu_min_intervals", "int32", "10", "-seed_imu wants at least this many frame intervals with a rate (at least 3).");
+  Define("dot_bias_rounds", "int32", "0", "After the solve, this many times: predict the bias of every dot's measured centre (the centre of a circle's image is not the image of "
+         "its centre) at the result on the GPU, subtract it from the original detections and solve again from the result (0: off; needs -gpus 1, no -holdout_every).  "
+         "The radii are -grid_large_rad / -grid_small_rad by the target's pattern (-grid_pattern_file, or generated from -grid_height / -grid_width / -grid_seed), or -dot_radius.");
+  Define("dot_radius", "double", "0", "With -dot_bias_rounds: the radius of every dot (m), instead of the large / small pattern (0: use the pattern).");
   Define("gyro_sigma", "double", "5.3088444e-5", "Sigma of gyroscope measurements.");
   Define("accel_sigma", "double", "0.001883649", "Sigma of accel measurements.");
   Define("remove_outliers", "bool", "false", "Remove outliers and re-optimise.");
@@ -62,8 +66,8 @@ static void DefineEngineFlags() {      // vicalib-engine.cc:30-104
   Define("static_threshold_preset", "int32", "0", "(sensor front-end) ignored: a visual_inertial_calibration::StaticThresholdPreset.");
   Define("use_static_threshold_preset", "bool", "false", "(sensor front-end) ignored: use one of the predefined static thresholds.");
   Define("output_pattern_file", "string", "", "(pattern front-end) ignored: EPS or SVG file to save the calibration pattern.");
-  Define("grid_large_rad", "double", "0.00423", "(pattern front-end) ignored: radius of large dots (m).");
-  Define("grid_small_rad", "double", "0.00283", "(pattern front-end) ignored: radius of small dots (m).");
+  Define("grid_large_rad", "double", "0.00423", "(pattern front-end) radius of large dots (m); read only by -dot_bias_rounds, ignored otherwise.");
+  Define("grid_small_rad", "double", "0.00283", "(pattern front-end) radius of small dots (m); read only by -dot_bias_rounds, ignored otherwise.");
   Define("clip_good", "bool", "false", "(sensor front-end) ignored: output proto file of only good tracked images.");
 }
 static void DefineTaskFlags() {      // vicalib-task.cc:19-51, and what only this tool has up to held-out scoring

@@ -112,6 +112,26 @@ int vc_seed_focal_batch(int device, int n_views, const int* view_cam, int n_cams
 int vc_time_seed_focal_batch(int device, int n_views, const int* view_cam, int n_cams, const double* cam_pp, const double* cam_radius,
                              const int* view_off, const double* p_w, const double* p_c, int min_corners, double max_fit_px,
                              double min_tilt_deg, int reps, double* kernel_ms);
+/* The predicted bias of a dot's measured centre, on the device.  A measurement is the centre of the dot's image ellipse as the detector's
+   dual-conic fit returns it; the solve holds it against the projection of the circle's centre, and under perspective and distortion the two
+   differ.  View v has the camera (view_model, view_K) and the pose view_T_cw (target into camera, [qx qy qz qw tx ty tz]) and owns
+   observations view_off[v] .. view_off[v+1]-1.  An observation is a dot centre p_w on the target and its radius in metres; the circle lies
+   in the plane through the centre parallel to the target's x-y plane.  bias = what the detector's estimator (unit weights, 64 samples of
+   the rim, no noise, no blur) returns minus project(centre), in pixels: subtract it from a measurement.  radius_px = the dot's radius in
+   pixels to first order.  status: 0 ok, 1 the centre does not project (behind the camera, not finite), 2 a rim sample does not project or
+   its edge direction is zero or not finite, 3 the 5 x 5 system is singular or the bias is not finite, 4 |bias| > radius_px (the estimate
+   left the dot: the view is too oblique to trust).  The outputs of an observation with status != 0 are left untouched.  radius = 0: bias
+   exactly (0, 0), radius_px 0, status 0 (where the centre projects).
+   VC_ERR_BAD_ARG before any device call (a null pointer, n_views < 0, offsets that decrease or start below 0, an unknown model, a radius
+   that is negative or not finite); VC_ERR_NO_DEVICE without that device: there is no host fallback.  Two runs give the same bits, and an
+   observation gives the same bits alone or among others. */
+int vc_dot_bias_batch(int device, int n_views, const int* view_model, const double* view_K /* n_views x 10 */,
+                      const double* view_T_cw /* n_views x 7 */, const int* view_off /* n_views + 1 */,
+                      const double* p_w /* total x 3 */, const double* radius /* total */,
+                      double* bias /* total x 2 */, double* radius_px /* total */, int* status /* total */);
+/* Mean time in ms of the batch's kernel alone on that input: `reps` launches back to back between two events, after one that warms up. */
+int vc_time_dot_bias_batch(int device, int n_views, const int* view_model, const double* view_K, const double* view_T_cw, const int* view_off,
+                           const double* p_w, const double* radius, int reps, double* kernel_ms);
 /* AddObservation(frame, cam, p_w, p_c, time) :385-468, in bulk: n corners of one (frame, camera) */
 int vc_add_observations(vc_calibrator* h, int frame, int camera, int n, const double* p_w /* n x 3 */,
                         const double* p_c /* n x 2 */);

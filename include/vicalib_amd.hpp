@@ -69,6 +69,27 @@ inline SeedFocalResult SeedFocalBatch(int device, const std::vector<int>& view_c
   return r;
 }
 
+// The predicted bias of every dot's measured centre (vc_dot_bias_batch; on the device, no handle): view v has the camera view_model / view_K
+// (x 10) and the pose view_T_cw (x 7, target into camera) and owns observations view_off[v] .. view_off[v+1]-1 of p_w (x 3) / radius (metres).
+struct DotBiasResult {
+  std::vector<double> bias, radius_px;      // x 2, x 1 per observation; NaN where the observation was refused
+  std::vector<int> status;
+};
+inline DotBiasResult DotBiasBatch(int device, const std::vector<int>& view_model, const std::vector<double>& view_K, const std::vector<double>& view_T_cw,
+                                  const std::vector<int>& view_off, const std::vector<double>& p_w, const std::vector<double>& radius) {
+  const size_t nv = view_model.size(), n = radius.size();
+  if (view_K.size() != 10 * nv || view_T_cw.size() != 7 * nv || view_off.size() != nv + 1 || p_w.size() != 3 * n || view_off.front() != 0 || (size_t)view_off.back() != n)
+    throw std::runtime_error("vicalib_amd: DotBiasBatch: array sizes disagree");
+  const double nan = std::nan("");
+  DotBiasResult r;
+  r.bias.assign(2 * n + 1, nan); r.radius_px.assign(n + 1, nan); r.status.assign(n + 1, -1);
+  const double none[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  vc_checked(vc_dot_bias_batch(device, (int)nv, nv ? view_model.data() : r.status.data(), nv ? view_K.data() : none, nv ? view_T_cw.data() : none, view_off.data(),
+                               n ? p_w.data() : none, n ? radius.data() : none, r.bias.data(), r.radius_px.data(), r.status.data()), "DotBiasBatch");
+  r.bias.resize(2 * n); r.radius_px.resize(n); r.status.resize(n);
+  return r;
+}
+
 // The inertial seed (vc_seed_imu, vc_seed_imu_sweep; on the device, no handle): the rotation camera <- IMU, the time offset, the gyro bias and the
 // direction of gravity from the frames' camera rotations (frame_q_wc: n x 4, [x y z w]; frame_ok: 0 = no rotation) and the IMU log.
 struct SeedImuResult {

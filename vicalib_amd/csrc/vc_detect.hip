@@ -34,6 +34,7 @@
 #include "../../include/vicalib_amd.h"
 #include "vc_kutil.hpp"
 #include "vc_hostutil.hpp"
+#include "vc_conic5.hpp"
 
 namespace {
 
@@ -272,23 +273,8 @@ __global__ __launch_bounds__(64) void k_det_fit(DetView v) {
 #pragma unroll
   for (int k = 0; k < 20; ++k) acc[k] = vc::wave_allsum(acc[k]);      // (all lanes, fixed order)
   if (lane == 0) {
-    double M[5][6];
-    int e = 0;
-    for (int i = 0; i < 5; ++i) for (int j = i; j < 5; ++j) { M[i][j] = acc[e]; M[j][i] = acc[e]; ++e; }
-    for (int i = 0; i < 5; ++i) M[i][5] = acc[15 + i];
-    bool ok = true;
-    for (int c = 0; c < 5; ++c) {                   // Gaussian elimination with partial pivoting
-      int p = c;
-      for (int rr = c + 1; rr < 5; ++rr) if (fabs(M[rr][c]) > fabs(M[p][c])) p = rr;
-      if (M[p][c] == 0.0) { ok = false; break; }
-      if (p != c) for (int j = 0; j < 6; ++j) { const double t = M[p][j]; M[p][j] = M[c][j]; M[c][j] = t; }
-      for (int rr = c + 1; rr < 5; ++rr) {
-        const double f = M[rr][c] / M[c][c];
-        for (int j = c; j < 6; ++j) M[rr][j] -= f * M[c][j];
-      }
-    }
-    double th[5] = {0, 0, 0, 0, 0};
-    if (ok) for (int i = 4; i >= 0; --i) { double s = M[i][5]; for (int j = i + 1; j < 5; ++j) s -= M[i][j] * th[j]; th[i] = s / M[i][i]; }
+    double th[5];
+    const bool ok = vc::conic5_solve(acc, th);      // Gaussian elimination with partial pivoting (vc_conic5.hpp)
     DetRec& rec = v.recs[ci];
     rec.cx = ok ? cx + 0.5 * th[3] : -1.0;
     rec.cy = ok ? cy + 0.5 * th[4] : -1.0;

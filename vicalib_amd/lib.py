@@ -29,7 +29,7 @@ SYMBOLS = [
     "vc_get_biases", "vc_get_scale_factor", "vc_get_gravity", "vc_time_offset", "vc_mean_squared_error", "vc_get_camera_proj_rmse",
     "vc_get_num_iterations", "vc_num_imu_measurements", "vc_get_imu_measurements", "vc_get_integration_poses", "vc_print_results", "vc_write_camera_models", "vc_trace_len", "vc_get_trace", "vc_set_shard", "vc_get_stream", "vc_prepare",
     "vc_linearize", "vc_step_hold", "vc_shared_dim", "vc_run_iterations", "vc_download_state", "vc_evaluate", "vc_time_kernels", "vc_time_stages", "vc_get_imu_blocks", "vc_get_debug_stamps", "vc_num_observations", "vc_num_tiles",
-    "vc_init_frame_poses_pnp", "vc_pnp_planar", "vc_pnp_planar_ransac", "vc_set_pnp_ransac", "vc_pnp_planar_batch", "vc_time_pnp_planar_batch", "vc_set_pnp_device", "vc_seed_focal_batch", "vc_time_seed_focal_batch","vc_rccl_unique_id", "vc_set_shard_rccl", "vc_shard_comm_create", "vc_set_shard_comm", "vc_shard_comm_destroy", "vc_allreduce_calls", "vc_shard_info", "vc_pass_paths", "vc_chain_order", "vc_last_error", "vc_get_imu_weights",
+    "vc_init_frame_poses_pnp", "vc_pnp_planar", "vc_pnp_planar_ransac", "vc_set_pnp_ransac", "vc_pnp_planar_batch", "vc_time_pnp_planar_batch", "vc_set_pnp_device", "vc_seed_focal_batch", "vc_time_seed_focal_batch", "vc_dot_bias_batch", "vc_time_dot_bias_batch", "vc_rccl_unique_id", "vc_set_shard_rccl", "vc_shard_comm_create", "vc_set_shard_comm", "vc_shard_comm_destroy", "vc_allreduce_calls", "vc_shard_info", "vc_pass_paths", "vc_chain_order", "vc_last_error", "vc_get_imu_weights",
     "vc_solution_covariance_dim", "vc_get_solution_covariance", "vc_get_solution_covariance_names",
     "vc_target_make_pattern", "vc_target_find",
     "vc_report_compute", "vc_report_num_corners", "vc_report_corners", "vc_report_num_views", "vc_report_views", "vc_report_error_map", "vc_report_num_imu_blocks", "vc_report_imu", "vc_time_report_sweeps",
@@ -187,6 +187,48 @@ def time_seed_focal_batch(view_cam, cam_pp, cam_radius, view_off, p_w, p_c, min_
     ip = lambda a: a.ctypes.data_as(C.c_void_p)
     _check(load().vc_time_seed_focal_batch(int(device), len(cam), ip(cam_arg), len(rad), _d(pp), _d(rad), ip(off), _d(p_w), _d(p_c), int(min_corners),
                                            C.c_double(max_fit_px), C.c_double(min_tilt_deg), int(reps), C.byref(ms)), "time_seed_focal_batch")
+    return ms.value
+
+
+def _dot_bias_arrays(models, params, T_cw, view_off, p_w, radius):
+    from .synth import MODEL_IDS
+    n = len(models)
+    m = np.array([MODEL_IDS[x] if isinstance(x, str) else int(x) for x in models], dtype=np.int32)
+    K = np.zeros((n, 10))
+    for v in range(n):
+        K[v, :len(params[v])] = params[v]
+    T = np.ascontiguousarray(T_cw, dtype=np.float64).reshape(-1, 7)
+    off = np.ascontiguousarray(view_off, dtype=np.int32).reshape(-1)
+    p_w = np.ascontiguousarray(p_w, dtype=np.float64).reshape(-1, 3); rad = np.ascontiguousarray(radius, dtype=np.float64).reshape(-1)
+    if len(T) != n or len(off) != n + 1 or len(rad) != len(p_w) or off[0] != 0 or off[-1] != len(rad):
+        raise VicalibError("dot_bias_batch: T_cw needs one row per view, view_off one entry more from 0 to the number of observations, radius one per row of p_w")
+    pad = lambda a, shape, dt: a if len(a) else np.zeros(shape, dtype=dt)
+    return n, pad(m, 1, np.int32), pad(K, (1, 10), np.float64), pad(T, (1, 7), np.float64), off, pad(p_w, (1, 3), np.float64), pad(rad, 1, np.float64), len(rad)
+
+
+def dot_bias_batch(models, params, T_cw, view_off, p_w, radius, device=0, out=None):
+    """The predicted bias of every dot's measured centre, on the device (vc_dot_bias_batch).  models / params / T_cw: per view (names or ids; up to
+    10 parameters each; target into camera [qx qy qz qw tx ty tz]); view v owns observations view_off[v] .. view_off[v+1]-1 of p_w [n, 3] (dot
+    centres on the target) and radius [n] (metres).  Returns bias [n, 2] (pixels: subtract it from a measured centre), radius_px [n], status [n];
+    `out` may hold pre-filled bias / radius_px arrays: an observation with status != 0 leaves its rows as they were (the default fill is NaN)."""
+    nv, m, K, T, off, p_w, rad, n = _dot_bias_arrays(models, params, T_cw, view_off, p_w, radius)
+    out = dict(out or {})
+    bias = out.get("bias", np.full((n, 2), np.nan)); rpx = out.get("radius_px", np.full(n, np.nan))
+    for a in (bias, rpx):
+        assert a.dtype == np.float64 and a.flags.c_contiguous
+    status = np.full(max(n, 1), -1, dtype=np.int32)
+    keep = [np.zeros(2) if bias.size == 0 else bias, np.zeros(1) if rpx.size == 0 else rpx]
+    ip = lambda a: a.ctypes.data_as(C.c_void_p)
+    _check(load().vc_dot_bias_batch(int(device), nv, ip(m), _d(K), _d(T), ip(off), _d(p_w), _d(rad), _d(keep[0]), _d(keep[1]), ip(status)), "dot_bias_batch")
+    return dict(bias=bias, radius_px=rpx, status=status[:n])
+
+
+def time_dot_bias_batch(models, params, T_cw, view_off, p_w, radius, device=0, reps=10):
+    """mean time in ms of the kernel of dot_bias_batch alone on that input (vc_time_dot_bias_batch: HIP events, launches back to back)"""
+    nv, m, K, T, off, p_w, rad, n = _dot_bias_arrays(models, params, T_cw, view_off, p_w, radius)
+    ms = C.c_double(0)
+    ip = lambda a: a.ctypes.data_as(C.c_void_p)
+    _check(load().vc_time_dot_bias_batch(int(device), nv, ip(m), _d(K), _d(T), ip(off), _d(p_w), _d(rad), int(reps), C.byref(ms)), "time_dot_bias_batch")
     return ms.value
 
 
