@@ -334,7 +334,7 @@ struct vc_calibrator {
   // withheld ones with events: the same iterates as a run that never used the flags.
   int resume_after_sync_timeout(const Ctrl& c);
   // The trust-region loop (ceres::Solve :956 with LEVENBERG_MARQUARDT).  The loop itself runs
-  // on the device (lm_decide in vc_kernels.hip); the host enqueues passes in batches and polls Ctrl::done.
+  // on the device (lm_decide in vck_decide.hpp); the host enqueues passes in batches and polls Ctrl::done.
   int solve_once(Termination* term, double* final_cost, long* nres);
   int last_iters = 0;
   // one pass with the decision logic on hold (parity hooks): linearise at the accepted state

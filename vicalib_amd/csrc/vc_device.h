@@ -1,5 +1,5 @@
 // vc_device.h -- device-side views shared by the host driver (vc_calibrator.hpp and its translation units)
-// and the HIP kernels (vc_kernels.hip).  HBM layout (see DESIGN.md "Data layout"):
+// and the HIP kernels (vc_kernels.hip and its stage fragments vck_*.hpp, vc_imu_kernels.hip).  HBM layout (see DESIGN.md "Data layout"):
 //   observations  tile-sorted SoA: obs_uv[n] (16 B) + obs_pt[n] (u16 index into points[]) = 18 B / corner
 //   tiles         (frame, camera) groups: tile_frame, tile_cam, tile_off[n_tiles+1]
 //   frame poses   n_frames x 8 doubles [q(4) t(3) pad], double-buffered (accepted / trial)

@@ -45,19 +45,16 @@ __device__ __forceinline__ ImuView imu_view(const DevView& v) { ImuView b = {v.i
 
 // ------------------------------------------------------------------------------------------ IMU Jacobian
 constexpr int kImuJacLds = 34 * 9 + 6;            // [34][9]: the block's 33 local columns and, as a 34th, the residual itself
-// (row a, column b) of every entry of the compact block record (vc_device.h: kSeg*), b = 33: gradient -- one table look-up per entry
+// (row a, column b) of every entry of the compact block record (vc_device.h: kSeg*), b = 33: gradient.  Nothing reads this table since the
+// dot-product form of the block's J^T J (rounds 1-5) left; a __constant__ object is emitted whether it is read or not (1552 bytes: DESIGN 4, file map).
 struct SegTab {
   unsigned short v[kSegStride];
   constexpr SegTab() : v() { for (int e = 0; e < kSegLen; ++e) { int a = 0, b = 0; seg_entry(e, &a, &b); v[e] = (unsigned short)(a | (b << 8)); } }
 };
 __constant__ SegTab d_seg_tab = SegTab();
-constexpr int kSegIters = (kSegLen + 31) / 32;      // entries of the record per lane (32 lanes per block)
-// ... and the other way round for the matrix-pipe form of the block's J^T J (round 6): the 34 columns (33 local columns + the residual) are
-// three column tiles of 16; tile pair (I, J) of v_mfma_f64_16x16x4 leaves entry (a, b) = (16 I + 4 g + lane / 16, 16 J + lane % 16) in
+// The table the kernel reads runs the other way round, for the block's J^T J on the matrix pipe (round 6): the 34 columns (33 local columns + the
+// residual) are three column tiles of 16; tile pair (I, J) of v_mfma_f64_16x16x4 leaves entry (a, b) = (16 I + 4 g + lane / 16, 16 J + lane % 16) in
 // accumulator register g of `lane` -- v[I * 3 + J][lane][g] is that entry's place in the compact record (0xffff: the record has no such entry)
-#ifndef VC_IJ_MFMA
-#define VC_IJ_MFMA 1      // (0: the block's J^T J as 25 nine-term dot products per lane out of LDS, the form of rounds 1-5 -- A/B builds)
-#endif
 struct SegInv {
   unsigned short v[9][64][4];
   constexpr SegInv() : v() {
@@ -123,15 +120,9 @@ __global__ __launch_bounds__(256) void k_imu_jac(DevView v, int wr, int trial) {
   double r[9], dr[9];
   const int col = (l < 6) ? l : (l < 30 ? l + 3 : -1);         // lanes 30, 31 carry the values only
   const bool valid = brec[10] >= 0.0;
-#if VC_IJ_MFMA
   unsigned long long seg_at[9];      // where the lane's four accumulator entries of every tile pair go in the record (tile pair (2, 0) has none)
 #pragma unroll
   for (int t = 0; t < 9; ++t) seg_at[t] = t == 6 ? ~0ull : *reinterpret_cast<const unsigned long long*>(&d_seg_inv.v[t][lane][0]);
-#else
-  int seg_ab[kSegIters];
-#pragma unroll
-  for (int it = 0; it < kSegIters; ++it) { const int e = l + 32 * it; seg_ab[it] = d_seg_tab.v[e < kSegLen ? e : 0]; }
-#endif
   wave_lds_sync();
   IJSTAMP(1);
   imu_block_final_direction(valid, brec, wq, v.rotation_only, T2, T1, v2, v1, v.imu_grav + cur * 16, col, r, dr);
@@ -180,13 +171,14 @@ __global__ __launch_bounds__(256) void k_imu_jac(DevView v, int wr, int trial) {
   // have been performed -- k_final ends on that count (round 4: on a flag a one-thread kernel raised behind this one, 6 us after this
   // kernel's end, which since round 5's leaner k_final was what the pass ended on)
   const bool counted2 = trial && v.final_wait > 0;
-#if VC_IJ_MFMA
   // J^T J and J^T r of the block in the compact record, entry e = w * <column a, column b> with the residual as column 33 -- on the matrix
   // pipe (round 6).  As 25 nine-term dot products per lane the phase was 450 LDS reads per lane, 6.2 of the kernel's ~20 us; here the whole
   // wavefront takes its two blocks one after the other: the block's [34][9] image read ONCE as nine operand registers (column tile T, rows
   // 4 ks .. 4 ks + 3: the same register is the A operand of tile pairs (T, .) and the B operand of (., T)), 8 tile pairs x 3 k-steps of
   // v_mfma_f64_16x16x4, and every accumulator entry goes to the place the inverse table names.  (a, b) and (b, a) are the same products in
-  // the same order: the record's symmetric blocks stay symmetric to the bit.
+  // the same order: the record's symmetric blocks stay symmetric to the bit.  (The dot-product form, rounds 1-5, asked for its 25 (row, column)
+  // pairs per lane at the kernel's entry, statically unrolled: as a loop every entry waited for its own table look-up -- 25 dependent global
+  // round trips, 10 of the kernel's 24 us at cfg3.)
   {
     const int i16 = lane & 15, kq = lane >> 4;
 #pragma unroll
@@ -224,24 +216,6 @@ __global__ __launch_bounds__(256) void k_imu_jac(DevView v, int wr, int trial) {
     }
     if (exists && l == 0) { if (counted2) __hip_atomic_store(v.seg_costb[cur] + s, ct->imu_mult * rho, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); else v.seg_costb[cur][s] = ct->imu_mult * rho; }
   }
-#else
-  if (exists) {
-  // J^T J and J^T r of the block in the compact record: entry e = w * <column a, column b> with the residual as column 33
-  // (statically unrolled, the (row, column) pairs of the lane's 25 entries requested at the kernel's entry: as a loop every entry
-  //  waited for its own table look-up -- 25 dependent global round trips, 10 of the kernel's 24 us at cfg3)
-  double* rec = v.segb[cur] + (size_t)s * kSegStride;
-#pragma unroll
-  for (int it = 0; it < kSegIters; ++it) {
-    const int e = l + 32 * it;
-    const int ab = seg_ab[it], a = ab & 255, bb = ab >> 8;
-    double acc = 0.0;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) acc += Jl[a * 9 + k] * Jl[bb * 9 + k];
-    if (e < kSegLen) { if (counted2) __hip_atomic_store(rec + e, w * acc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); else rec[e] = w * acc; }
-  }
-  if (l == 0) { if (counted2) __hip_atomic_store(v.seg_costb[cur] + s, ct->imu_mult * rho, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); else v.seg_costb[cur][s] = ct->imu_mult * rho; }
-  }
-#endif
   if (counted2) {
     __builtin_amdgcn_s_waitcnt(0);          // this wavefront's stores have been performed
     __syncthreads();
@@ -820,19 +794,11 @@ __global__ __launch_bounds__(256, 2) void k_chain_init(DevView v) {     // (two 
     const bool live = f < f1;
     const bool pin_f = (f == 0 && v.pin_first), pin_l = (f == N - 1 && v.pin_last), pin_self = pin_f || pin_l;
     const bool pin_next = (f + 1 == N - 1 && v.pin_last);
-#if defined(VC_INIT_EXP) && (VC_INIT_EXP & 1)
-    const double* rc = nullptr; const double* rp = nullptr;      // experiment: no IMU-record loads
-#else
     const double* rc = (live && f >= 1) ? v.segb[cur] + (size_t)(f - 1) * kSegStride : nullptr;
     const double* rp = (live && f + 1 < N) ? v.segb[cur] + (size_t)f * kSegStride : nullptr;
-#endif
 #pragma unroll
     for (int c = 0; c < CMAX; ++c) {
-#if defined(VC_INIT_EXP) && (VC_INIT_EXP & 4)
-      const int tc = -1;                                                          // experiment: no Gram-record loads
-#else
       const int tc = __builtin_amdgcn_readfirstlane(__shfl(fct_f, c, 64));      // (wave-uniform: a scalar branch per camera)
-#endif
 #pragma unroll
       for (int q = 0; q < 3; ++q) R.gv[c][q] = 0.0;
       if (c < C && tc >= 0) {
@@ -844,7 +810,7 @@ __global__ __launch_bounds__(256, 2) void k_chain_init(DevView v) {     // (two 
     // Branch-free from here on: every lane loads from a valid address (a lane without an entry reads the start of record 0) and keeps
     // the value or a zero by a select.  Loads under divergent branches are not hoisted out of them: round 4's form -- `if (lane has this
     // entry) x += record[..]`, ~40 masked loads per frame -- ran them as a chain of dependent round trips, 8 of the 17 us a wavefront
-    // took at BASELINE cfg3 and 60 of 124 us at cfg5's per-rank size (tools/init_stamps.py with -DVC_INIT_EXP=1: the kernel without them).
+    // took at BASELINE cfg3 and 60 of 124 us at cfg5's per-rank size (tools/init_stamps.py on a build of the kernel without the IMU-record loads).
     const double* safe = v.cg;                 // (always there; only its first entry is ever read through `safe`, and the value is dropped)
     const double* rcs = rc ? rc : safe;
     const double* rps = rp ? rp : safe;
@@ -1118,9 +1084,6 @@ __global__ __launch_bounds__(256, 2) void k_chain_init(DevView v) {     // (two 
 #pragma unroll
         for (int i = 0; i < 9; ++i) val[i] = pin_self ? ((i == jb) ? 1.0 : 0.0) : As[i * 9 + jb] + ((i == jb) ? ls[i] : 0.0);
       }
-#if defined(VC_INIT_EXP) && (VC_INIT_EXP & 2)
-      if (val[0] == 123.456)                       // experiment: no image stores
-#endif
       if (col < nW) {
 #pragma unroll
         for (int i = 0; i < 9; ++i) Wt[i * ldt + col] = val[i];
@@ -1518,11 +1481,7 @@ __global__ __launch_bounds__(64 * NW) void k_chain_fwd(DevView v, int s, int m, 
 // it issues, address arithmetic included: per frame of a two-sided sweep the columns' addresses were ~340 instructions, the frame's
 // elimination itself ~850 (round 6, tools/isa_classes.py with markers).  Images stay below 4 GB (n_frames x 9 x ldx x 8: 0.9 GB at 50 000 frames).
 __device__ __forceinline__ double ld_boff(const double* base, unsigned boff) { return *reinterpret_cast<const double*>(reinterpret_cast<const char*>(base) + boff); }
-__device__ __forceinline__ void st_boff(double* base, unsigned boff, double x) { *reinterpret_cast<double*>(reinterpret_cast<char*>(base) + boff) = x; }
 struct ElimLds { double* XS; double* An; double* Ls; };
-#ifndef VC_ELIM_STORE_BOFF
-#define VC_ELIM_STORE_BOFF 0      // (1: the solved image stored through scalar base + byte offsets as well -- same-box A/B: the folded bottom level 28.0 -> 30.0 us, the upper levels unchanged)
-#endif
 template <bool WG_SYNC>
 __device__ __forceinline__ void chain_eliminate(const DevView& v, double* img /* the frame's image */, int ldx, int role, int pc, int sub, bool flag_lane,
                                                 const ElimLds& M, double* x, double* out, long long* stamp = nullptr /* profiling builds: phase stamps of this call */) {
@@ -1600,15 +1559,11 @@ __device__ __forceinline__ void chain_eliminate(const DevView& v, double* img /*
 #pragma unroll
     for (int k = 0; k < 9; ++k) { lv[k] = rl[k]; xv[k] = rx[k * kXsLd]; }
     if (role < 4) {
-#if VC_ELIM_STORE_BOFF
-      const unsigned pcb = 8u * (unsigned)pc, ldxb = 8u * (unsigned)ldx;
-#pragma unroll
-      for (int k = 0; k < 9; ++k) st_boff(img, pcb + k * ldxb, role == 2 ? lv[k] : x[k]);       // (A: L[k][sub], zero above the diagonal)
-#else
+      // (a 64-bit address per lane: storing through a scalar base + byte offsets as the loads do was slower -- same-box A/B: the folded
+      //  bottom level 28.0 -> 30.0 us, the upper levels unchanged)
       double* ic = img + pc;
 #pragma unroll
       for (int k = 0; k < 9; ++k) ic[k * ldx] = role == 2 ? lv[k] : x[k];       // (A: L[k][sub], zero above the diagonal)
-#endif
     }
 #pragma unroll
     for (int k = 0; k < 9; ++k) x[k] = role == 2 ? xv[k] : x[k];
@@ -1805,12 +1760,8 @@ __global__ __launch_bounds__(128 * NW, VC_FWD2_WAVES) void k_chain_fwd2(DevView 
       }
     }
     const int e = a + (at_mid ? mid : i0 + dir * j) * s;
-#ifdef VC_EXP_NO_O_LOADS      // (timing experiment only -- wrong numbers: what the level costs when the next frame's columns need no memory round trip)
-    if (!at_mid) { for (int k = 0; k < 9; ++k) o[k] = xin[k] * 0.999; }
-#else
     if (!at_mid)                        // the columns of the frame after this one: requested now, used after the elimination
       load_cols(j + 1 < cnt ? i0 + dir * (j + 1) : mid, false, j + 1 < cnt || wave == 0, o);
-#endif
     double x[9], out[18];
 #pragma unroll
     for (int k = 0; k < 9; ++k) x[k] = xin[k];

@@ -4,7 +4,7 @@
 namespace vc {
 
 // The trust-region rules of the Levenberg-Marquardt loop (the Ceres rules the project restates), stated once: read by
-// init_ctrl (vc_calibrator.hpp), lm_decide_local (vc_kernels.hip), the held-out pose refit (k_validate_pose, vc_validate.hip) and the model
+// init_ctrl (vc_calibrator.hpp), lm_decide_local (vck_decide.hpp), the held-out pose refit (k_validate_pose, vc_validate.hip) and the model
 // conversion's host loop (cvt_levenberg_marquardt, vc_convert.hpp).
 struct LmRules {
   static constexpr double kInitialRadius = 1e4;

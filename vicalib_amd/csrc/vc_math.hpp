@@ -1,5 +1,5 @@
 // vc_math.hpp -- closed-form arithmetic of the calibration hot path, written for
-// the HIP kernels (vc_kernels.hip) and usable from host code.
+// the HIP kernels (vc_kernels.hip and its stage fragments vck_*.hpp) and usable from host code.
 //
 // What the reference evaluates with ceres::Jet autodiff per corner
 // (ImuReprojectionCostFunctor, ceres-cost-functions.h:350-373, instantiated at
@@ -27,7 +27,7 @@ enum Model { kFov = 0, kPoly2 = 1, kPoly3 = 2, kKb4 = 3, kLinear = 4, kRational6
 VC_HD int model_nk(int m) { return m == kFov ? 5 : m == kPoly2 ? 6 : m == kPoly3 ? 7 : m == kKb4 ? 8 : m == kLinear ? 4 : m == kRational6 ? 10 : -1; }
 
 // f(std::integral_constant<int, MODEL>) with the run-time model as a compile-time constant: the one place that lists the six models for
-// the sweeps whose body is the same template for all of them (the Jacobian sweep keeps its own switch: jac_tile_dispatch, vc_kernels.hip)
+// the sweeps whose body is the same template for all of them (the Jacobian sweep keeps its own switch: jac_tile_dispatch, vck_reproj_jac.hpp)
 template <class F>
 VC_HD void with_model(int model, F&& f) {
   switch (model) {   // wave-uniform on the device

@@ -1,5 +1,5 @@
 // vc_reduced_tail.hpp -- what follows the reduced solve: the trial state of the shared parameters and their terms of the step's scalars.
-// Included by vc_kernels.hip (k_reduced runs it itself: vision-only passes, the level-by-level back-substitution) and by
+// Included by vck_reduced.hpp (k_reduced runs it itself: vision-only passes, the level-by-level back-substitution) and by
 // vc_imu_kernels.hip (round 6: one extra workgroup of the back-substitution's launch runs it -- k_reduced, a single workgroup on the critical
 // path, then ends with the step and the trial IMU parameters stored: DevView::tail_deferred).  Same arithmetic, same lane layout, same
 // summation order in both places: the scalars are identical to the bit.

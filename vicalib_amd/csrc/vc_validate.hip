@@ -14,7 +14,7 @@
 //                        floating-point atomic -- two runs, and a frame alone or among others, give the same bits.
 //                        Step: (H + D / radius) delta = -g with D = clamp(diag H) (lm_clamped_diag, no Jacobi scaling: six
 //                        parameters of one pose), 6 x 6 Cholesky in registers, trial pose by se3_plus, trial cost by a second sweep
-//                        (project_any<false>).  Accept / reject / radius: the rules of lm_decide_local (vc_kernels.hip), with
+//                        (project_any<false>).  Accept / reject / radius: the rules of lm_decide_local (vck_decide.hpp), with
 //                        the solver's own constants (LmRules, vc_device.h).  A corner at depth <= 0 at the iterate enters no sum of that
 //                        sweep and is counted.
 //  k_validate_residuals  one wavefront per held-out (frame, camera) tile at the refined poses, in the manner of k_report_vision:
