@@ -1,6 +1,6 @@
 #pragma once
 // vc_chain_order.hpp -- the order in which the interior frames of ONE group of the partitioned chain elimination are eliminated by odd-even
-// reduction inside a workgroup (vc_imu_kernels.hip: k_chain_oe, the top level, the three back-substitution kernels), and who a frame's
+// reduction inside a workgroup (vci_chain_oe.hpp: chain_oe_group under k_chain_oe and the top level; vc_imu_kernels.hip: the three back-substitution kernels), and who a frame's
 // neighbours are when its turn comes.  Plain C++ for host and device: the host test harness builds it (tests/host_harness).
 //
 // A group is [a | e_1 .. e_q | r]: q = 1 .. 7 interior frames, a left separator a and a right separator r that may each be absent (the

@@ -1,5 +1,5 @@
 #pragma once
-// vc_chain_plan.hpp -- the level schedule of the partitioned chain elimination (vc_imu_kernels.hip) and the forms of the visual-inertial
+// vc_chain_plan.hpp -- the level schedule of the partitioned chain elimination (chain_levels, vc_imu_kernels.hip; the levels' kernels in vci_chain_*.hpp) and the forms of the visual-inertial
 // pass that follow from it, computed once per upload (vc_upload.cpp) from the problem's shape and the switches of DESIGN §9.  Every
 // launcher, the pass (vc_pass.cpp), the buffer sizes and vc_pass_paths read this one plan.  Plain C++: the host test harness builds it.
 #include <algorithm>

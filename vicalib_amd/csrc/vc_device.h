@@ -1,5 +1,5 @@
 // vc_device.h -- device-side views shared by the host driver (vc_calibrator.hpp and its translation units)
-// and the HIP kernels (vc_kernels.hip and its stage fragments vck_*.hpp, vc_imu_kernels.hip).  HBM layout (see DESIGN.md "Data layout"):
+// and the HIP kernels (vc_kernels.hip and its stage fragments vck_*.hpp, vc_imu_kernels.hip and its stage fragments vci_*.hpp).  HBM layout (see DESIGN.md "Data layout"):
 //   observations  tile-sorted SoA: obs_uv[n] (16 B) + obs_pt[n] (u16 index into points[]) = 18 B / corner
 //   tiles         (frame, camera) groups: tile_frame, tile_cam, tile_off[n_tiles+1]
 //   frame poses   n_frames x 8 doubles [q(4) t(3) pad], double-buffered (accepted / trial)
@@ -252,7 +252,7 @@ void launch_sum_tile_cost(const DevView& v, double* out_cost_sq /*2*/, hipStream
 void launch_cam_sq(const DevView& v, double* out /*n_cams x 2: sum sq, count*/, hipStream_t s);
 void launch_outlier_mask(const DevView& v, int state, const double* thresh /*device, n_cams*/, unsigned char* mask, hipStream_t s);
 
-// inertial path (vc_imu_kernels.hip)
+// inertial path (vc_imu_kernels.hip and its stage fragments vci_*.hpp)
 void launch_imu_delta(const DevView& v, hipStream_t s, int trial = 0);         // block deltas under the IMU parameters of the accepted (0) / trial (1) state (k_imu_block)
 void launch_imu_jac(const DevView& v, int wr, hipStream_t s, int trial = 0);   // wr: weight buffer to read; trial as for launch_reproj_jac; needs launch_imu_delta
 void launch_imu_weights(const DevView& v, int wr, hipStream_t s);          // reads wsqrtb[wr], writes wsqrtb[1 - wr];                   // weight_sqrt_ from the accepted state

@@ -10,7 +10,7 @@
 // (:919-1040).  Where the reference hands a ceres::Problem to ceres::Solve (:956) this driver runs a
 // trust-region Levenberg-Marquardt loop (the Ceres algorithm: Jacobi scaling, diagonal clamp, step
 // quality, radius update) whose every O(observations) and O(frames) step is a HIP kernel
-// (vc_kernels.hip and its stage fragments vck_*.hpp, vc_imu_kernels.hip).  The host only takes the accept/reject decision from a handful of scalars.
+// (vc_kernels.hip and its stage fragments vck_*.hpp, vc_imu_kernels.hip and its stage fragments vci_*.hpp).  The host only takes the accept/reject decision from a handful of scalars.
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
 #include <algorithm>

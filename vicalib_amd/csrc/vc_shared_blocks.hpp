@@ -1,6 +1,6 @@
 // vc_shared_blocks.hpp -- the reduced system's terms that do not come from the frame elimination: the cameras' blocks H_cc = P^T G P and the
 // IMU-parameter block, from the fixed-order sums of the chunk records.  Included by vck_reduced.hpp (k_reduced adds them itself on vision-only
-// and sharded passes) and by vc_imu_kernels.hip (round 6: on single-process visual-inertial passes they are formed AHEAD of k_reduced -- side
+// and sharded passes) and by vc_imu_kernels.hip through vci_chain_fwd2.hpp (round 6: on single-process visual-inertial passes they are formed AHEAD of k_reduced -- side
 // jobs of the chain's upper-level launches, which leave most of the chip idle: hadd_side_job below -- and k_reduced, one workgroup the whole chip
 // waits for, only adds the finished record: DevView::hadd_early).
 #pragma once
