@@ -272,6 +272,14 @@ static bool CheckFlags(Run& s, int* rc) {
     if (!(FlagDouble("seed_imu_max_gap") > 0.0)) return FlagError(rc, "illegal value for flag 'seed_imu_max_gap': expected more than 0");
     if (FlagInt("seed_imu_min_intervals") < 1) return FlagError(rc, "illegal value for flag 'seed_imu_min_intervals': expected at least 1");
   }
+  if (FlagString("seed_rig") != "off") {
+    const std::string mode = FlagString("seed_rig");
+    if (mode != "pnp" && mode != "mono") return FlagError(rc, "illegal value '" + mode + "' specified for flag 'seed_rig': expected off, pnp or mono");
+    if (FlagBool("has_initial_guess")) return FlagError(rc, "-seed_rig and -has_initial_guess exclude each other: the guess is the start");
+    if (!(FlagDouble("seed_rig_tol_deg") > 0.0) || !(FlagDouble("seed_rig_tol_deg") < 90.0)) return FlagError(rc, "illegal value for flag 'seed_rig_tol_deg': expected more than 0 and less than 90");
+    if (FlagInt("seed_rig_min_support") < 1) return FlagError(rc, "illegal value for flag 'seed_rig_min_support': expected at least 1");
+    if (!(FlagDouble("seed_rig_max_rmse") > 0.0)) return FlagError(rc, "illegal value for flag 'seed_rig_max_rmse': expected more than 0");
+  }
   if (!UncertaintyFlags(&s.uncertainty, &err) || !StereoUncertaintyFlags(&s.stereo_uncertainty, &err) || !SelectFlags(&s.select, &err)) return FlagError(rc, err);
   // ---- -compare_models a.xml,b.xml: file against file, nothing is calibrated; -compare_to b.xml: read later, compared behind the results
   const bool comparing = !FlagString("compare_models").empty() || !FlagString("compare_to").empty();
@@ -522,6 +530,130 @@ static bool SeedFocal(Run& s, int* rc) {
       const char* why = sf.cam_status[c] == 1 ? "no usable view" : sf.cam_status[c] == 2 ? "the target was never tilted against the image plane" : "the views give no positive focal length";
       std::fprintf(stderr, "W camera %zu: no focal length seed (%s, %d of %d views usable); keeping fx = fy = %g\n", c, why, sf.cam_views[c], total, params[0]);
     }
+  }
+  return true;
+}
+
+// ---- -seed_rig pnp | mono: T_ck of every camera but the first from the views it shares with the others (vc_seed_rig: a vote among the per-frame
+// relative poses), once on -device over the frames that will be calibrated, before any calibrator of the joint solve exists; the one result serves
+// every rank.  pnp: the views are one PnP batch at the start intrinsics.  mono: every camera is calibrated alone first (identity pose, the frames
+// where it has >= 4 corners, PnP seeds, vision only); a usable result gives the camera's start intrinsics and, as T_cw = T_wk^-1, its views.
+static bool SeedRig(Run& s, int* rc) {
+  const size_t n_cam = s.channels.size(), n_frames = s.frame_ids.size();
+  if (n_cam < 2) { std::fprintf(stderr, "I -seed_rig: one camera, nothing to seed\n"); return true; }
+  const bool mono = FlagString("seed_rig") == "mono";
+  const std::map<long, int> fit_index = FrameIndex(s.frame_ids);
+  std::vector<unsigned char> view_ok(n_frames * n_cam, 0);
+  std::vector<double> view_T(7 * n_frames * n_cam, 0.0);
+  auto set_view = [&](size_t k, size_t c, const double* T_cw) {
+    for (int j = 0; j < 7; ++j) view_T[7 * (k * n_cam + c) + j] = T_cw[j];
+    view_ok[k * n_cam + c] = 1;
+  };
+  if (!mono) {
+    std::vector<int> view_model, view_off(1, 0), view_frame, view_cam;
+    std::vector<double> view_K, pw, pc;
+    for (size_t c = 0; c < n_cam; ++c) {
+      const vic::CameraAndPose& cam = s.input_cameras[c];
+      for (const auto& kv : DetectionsByFrame(s.channels[c], fit_index, s.grid_w * s.grid_h)) {
+        if (kv.second.size() < 4) continue;
+        AppendCorners(kv.second, &pw, &pc);
+        view_model.push_back(cam.model); view_off.push_back((int)(pc.size() / 2)); view_frame.push_back(kv.first); view_cam.push_back((int)c);
+        for (size_t j = 0; j < 10; ++j) view_K.push_back(j < cam.params.size() ? cam.params[j] : 0.0);
+      }
+    }
+    const int nv = (int)view_frame.size();
+    std::vector<double> T_cw(7 * (size_t)nv + 7, 0.0), rms((size_t)nv + 1, 0.0);
+    std::vector<int> n_in((size_t)nv + 1, 0), pnp_status((size_t)nv + 1, -1);
+    const int q = nv > 0 ? vc_pnp_planar_batch(Device(), nv, view_model.data(), view_K.data(), view_off.data(), pw.data(), pc.data(), (int)FlagInt("pnp_ransac_its"),
+                                               FlagDouble("pnp_ransac_tol"), T_cw.data(), rms.data(), n_in.data(), nullptr, pnp_status.data())
+                         : VC_OK;
+    if (q == VC_ERR_NO_DEVICE) return Stop(rc, 3, "F -seed_rig: no HIP device %d\n", Device());
+    if (q != VC_OK) { std::fprintf(stderr, "W -seed_rig: the pose batch failed (status %d); starting without the seed\n", q); return true; }
+    for (int v = 0; v < nv; ++v)
+      if (pnp_status[v] == 0) set_view((size_t)view_frame[v], (size_t)view_cam[v], &T_cw[7 * (size_t)v]);
+  } else {
+    const auto t0 = std::chrono::steady_clock::now();
+    for (size_t c = 0; c < n_cam; ++c) {
+      std::unique_ptr<vic::ViCalibrator> cal;
+      try { cal.reset(new vic::ViCalibrator(Device())); }
+      catch (const std::exception& e) { return Stop(rc, 3, "F -seed_rig: %s (device %d)\n", e.what(), Device()); }
+      const double zeros[6] = {0, 0, 0, 0, 0, 0}, ones[6] = {1, 1, 1, 1, 1, 1};
+      cal->SetSigmas(FlagDouble("gyro_sigma"), FlagDouble("accel_sigma"));
+      cal->SetBiases(zeros); cal->SetScaleFactor(ones);
+      cal->FixCameraIntrinsics(!FlagBool("calibrate_intrinsics"));
+      vic::CameraAndPose alone = s.input_cameras[c];
+      alone.T_ck = vic::Se3();
+      if (cal->AddCamera(alone) < 0) return Stop(rc, 1, "F AddCamera failed (model %s, %zu parameters)\n", ModelName(alone.model), alone.params.size());
+      std::vector<int> frame_of;                                                             // the calibrator's frame -> the run's
+      std::vector<double> pw, pc;
+      vic::Se3 placeholder; placeholder.v = {{0, 0, 0, 1, 0, 0, 1000}};
+      for (const auto& kv : DetectionsByFrame(s.channels[c], fit_index, s.grid_w * s.grid_h)) {
+        if (kv.second.size() < 4) continue;
+        const int f = cal->AddFrame(placeholder, FrameTime(s.channels, s.frame_ids[(size_t)kv.first]));
+        pw.clear(); pc.clear();
+        AppendCorners(kv.second, &pw, &pc);
+        cal->AddObservations((size_t)f, 0, (int)kv.second.size(), pw.data(), pc.data());
+        frame_of.push_back(kv.first);
+      }
+      bool usable = frame_of.size() >= 2;
+      double rmse = 0.0; unsigned iters = 0;
+      vic::CameraAndPose got;
+      if (usable) {
+        cal->SetPnPRansac((int)FlagInt("pnp_ransac_its"), FlagDouble("pnp_ransac_tol"));
+        cal->SetPnPDevice(FlagBool("pnp_device"));
+        cal->InitFramePosesPnP();
+        cal->SetOptimizationFlags(false, false, true, false);
+        cal->SetFunctionTolerance(FlagDouble("function_tolerance"));
+        cal->SetMaxIters((int)FlagInt("max_iters"));
+        cal->SetCalibrateImu(false);
+        cal->SetRemoveOutliers(FlagBool("remove_outliers"), FlagDouble("outlier_threshold"));
+        cal->Start();
+        while (cal->IsRunning()) std::this_thread::sleep_for(std::chrono::milliseconds(2));
+        cal->Stop();
+        rmse = cal->GetCameraProjRMSE()[0]; iters = cal->GetNumIterations();
+        got = cal->GetCamera(0);
+        usable = std::isfinite(rmse) && rmse <= FlagDouble("seed_rig_max_rmse");
+        for (double p : got.params) usable = usable && std::isfinite(p);
+      }
+      if (!usable) {
+        std::fprintf(stderr, "W -seed_rig: camera %zu alone is not usable (%zu frames, RMSE %.4g px above %g or not finite); it keeps its start and has no views in the seed\n",
+                     c, frame_of.size(), rmse, FlagDouble("seed_rig_max_rmse"));
+        continue;
+      }
+      s.input_cameras[c].params = got.params;
+      size_t n_views = 0;
+      for (size_t f = 0; f < frame_of.size(); ++f) {
+        const vic::Se3 T_cw = Se3Inverse(cal->GetFrame(f).t_wp_);
+        bool finite = true;
+        for (double p : T_cw.v) finite = finite && std::isfinite(p);
+        if (finite) { set_view((size_t)frame_of[f], c, T_cw.data()); ++n_views; }
+      }
+      std::fprintf(stderr, "I -seed_rig: camera %zu alone: RMSE %.4f px after %u iterations, %zu views\n", c, rmse, iters, n_views);
+    }
+    std::fprintf(stderr, "I -seed_rig: %zu cameras calibrated alone in %.3f s\n", n_cam, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+  }
+  vic::SeedRigResult r;
+  try { r = vic::SeedRig(Device(), (int)n_cam, view_ok, view_T, FlagDouble("seed_rig_tol_deg"), (int)FlagInt("seed_rig_min_support")); }
+  catch (const std::exception& e) {
+    if (std::string(e.what()).find("status -1)") != std::string::npos) return Stop(rc, 3, "F -seed_rig: no HIP device %d\n", Device());
+    std::fprintf(stderr, "W -seed_rig: %s; starting without the seed\n", e.what());
+    return true;
+  }
+  for (size_t c = 1; c < n_cam; ++c) {
+    if (r.cam_status[c] != 0) {
+      std::fprintf(stderr, "W -seed_rig: camera %zu is not connected to camera 0 by a pair with enough agreeing frames; it keeps its pose\n", c);
+      continue;
+    }
+    vic::Se3 T_c0;
+    for (int j = 0; j < 7; ++j) T_c0.v[j] = r.cam_T_c0[7 * c + j];
+    s.input_cameras[c].T_ck = Se3Mul(T_c0, s.input_cameras[0].T_ck);
+    const int par = r.cam_parent[c], a = std::min(par, (int)c), b = std::max(par, (int)c);
+    const size_t p = (size_t)(a * ((int)n_cam - 1) - (a * (a - 1)) / 2 + (b - a - 1));
+    const double* q = T_c0.v.data();
+    std::fprintf(stderr, "I -seed_rig: camera %zu: parent %d, baseline %.4f m, angle %.3f degrees, support %d / %d shared frames, rms %.4f degrees %.5f m, "
+                         "T_c0 [qx qy qz qw tx ty tz] %.9f %.9f %.9f %.9f %.6f %.6f %.6f\n", c, par,
+                 std::sqrt(q[4] * q[4] + q[5] * q[5] + q[6] * q[6]), 2.0 * std::atan2(std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2]), std::fabs(q[3])) * 180.0 / M_PI,
+                 r.pair_support[p], r.pair_shared[p], r.pair_rms_deg[p], r.pair_rms_m[p], q[0], q[1], q[2], q[3], q[4], q[5], q[6]);
   }
   return true;
 }
@@ -1081,6 +1213,7 @@ int main(int argc, char** argv) {
   if (s.dot_bias_rounds > 0 && !DotRadii(s, &rc)) return rc;
   if (!StartCameras(s, &rc) || !ChooseFrames(s, &rc)) return rc;
   if (FlagBool("seed_focal") && !SeedFocal(s, &rc)) return rc;
+  if (FlagString("seed_rig") != "off" && !SeedRig(s, &rc)) return rc;
   s.image_time_offset = InitialTimeOffset(s);
   if (FlagBool("seed_imu") && !SeedImu(s, &rc)) return rc;
   if (!LoadCalibrators(s, &rc) || !SetupCommunicator(s, &rc)) return rc;

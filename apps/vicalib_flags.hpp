@@ -42,6 +42,10 @@ static void DefineEngineFlags() {      // vicalib-engine.cc:30-104
   Define("seed_focal", "bool", "false", "Without -model_files: start every camera at the focal length its views of the target give (homographies, on the GPU) instead of 300.");
   Define("seed_focal_radius", "double", "0.5", "Corners used by -seed_focal lie within this fraction of the half diagonal of the image centre (<= 0: the whole image).");
   Define("seed_focal_fit_px", "double", "0", "Views whose homography fits worse than this many pixels rms are left out of -seed_focal (0: off).");
+  Define("seed_rig", "string", "off", "off | pnp | mono.  Start the pose of every camera but the first from the views it shares with the others (a vote among the per-frame relative poses, on the GPU) instead of -model_files' pose or identity.  pnp: the poses of one PnP batch at the start intrinsics; for -model_files with good intrinsics and no poses -- at the default start intrinsics (f = 300, no distortion) this mode is biased by tens of degrees on distorted lenses.  mono: every camera is calibrated alone first, its result gives its start intrinsics and its views.");
+  Define("seed_rig_tol_deg", "double", "3", "Two per-frame relative poses agree for -seed_rig within this angle, and within this angle times the distance to the target (more than 0, less than 90).");
+  Define("seed_rig_min_support", "int32", "3", "-seed_rig wants at least this many agreeing frames for a pair of cameras.");
+  Define("seed_rig_max_rmse", "double", "1.0", "-seed_rig mono leaves out a camera whose calibration alone ends above this many pixels of reprojection RMSE.");
   Define("seed_imu", "bool", "false", "With -imu: start the camera-IMU rotation of camera 0, the time offset, the gyro bias and gravity from the data (camera rates against gyro rates, on the GPU) instead of identity, the streams' first stamps, zero and one accelerometer sample.");
   Define("seed_imu_range", "double", "0.5", "Time offsets searched by -seed_imu: -range ... +range seconds around the start value.");
   Define("seed_imu_step", "double", "0", "Step of that search in seconds (0: the median IMU sample interval).");

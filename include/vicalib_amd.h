@@ -1014,6 +1014,37 @@ int vc_time_seed_imu(int device, int n_frames, const double* frame_t, const doub
                      const double* imu_t, const double* gyro, const double* accel, double max_gap_s, int min_intervals, int n_lags,
                      const double* lags, int reps, double out_ms[3]);
 
+/* ---- the rig seed: every camera's pose relative to camera 0 from the views it shares, before anything is solved ------------------------
+ * On the device, no handle.  The input is poses, wherever they come from: view_T_cw[k][c] = [qx qy qz qw tx ty tz] takes the target into
+ * camera c at frame k (a unit quaternion, e.g. from vc_pnp_planar_batch), view_ok[k][c] = 0: no such view; its pose is never read into a
+ * result (it may be NaN).  Pairs are (a < b) in the order (0,1), (0,2) .. (0,C-1), (1,2) ..; n_pairs = C (C - 1) / 2.  n_cams up to 8,
+ * n_frames up to 131072; more is VC_ERR_UNSUPPORTED.
+ * Per pair, every frame k with both views ok gives a candidate X_k = T_aw(k) T_bw(k)^-1 (camera b into camera a; the quaternion
+ * normalised) with the scale d_k = max(|t_aw(k)|, |t_bw(k)|).  Candidates i and j agree when |q_i . q_j| >= cos(tol / 2) and
+ * |t_i - t_j|^2 <= tol_rad^2 (d_i + d_j)^2: one angular tolerance serves both, since a pose error of angle e moves the camera by about e
+ * times its distance to the target.  The support of i is the number of shared frames that agree with it, itself included; the winner has
+ * the largest support, the lowest frame among equals.  The refit over the winner's agreeing frames: q = normalise(sum s_j q_j), s_j = -1
+ * where q_j . q_winner < 0, with qw >= 0; t the mean of t_j; pair_rms_deg the rms of the angles 2 atan2(|vec|, |w|) of q^-1 q_j,
+ * pair_rms_m the rms of |t_j - t|.  pair_shared: the frames both cameras see; pair_winner: the winner's frame.
+ * pair_status: 0 ok, 1 no shared frame, 2 support below min_support; with a status other than 0 only pair_shared and pair_status are
+ * written.
+ * The rig (host code): a maximum spanning tree over the status-0 pairs weighted by support, grown from camera 0 by Prim's rule, ties to
+ * the lowest tree camera, then the lowest new camera.  cam_T_c0[c] takes camera 0 into camera c, composed along the tree (qw >= 0;
+ * camera 0: the identity); cam_parent: -1 for camera 0 and for a camera not reached; cam_status: 0 reached, 1 not connected (its pose is
+ * left as it was).
+ * Everything is fp64, the supports are integers, no sum's order depends on anything but the pair's own shared frames: two runs give the
+ * same bits, and a pair gives the same bits whatever other cameras are in the batch.
+ * VC_ERR_BAD_ARG comes before any device call: a null pointer, n_frames < 0, n_cams < 1, tol_deg outside (0, 90), min_support < 1.
+ * VC_ERR_NO_DEVICE without that device: there is no host fallback. */
+int vc_seed_rig(int device, int n_frames, int n_cams, const unsigned char* view_ok /* n_frames x n_cams */,
+                const double* view_T_cw /* n_frames x n_cams x 7 */, double tol_deg, int min_support,
+                double* pair_T_ab /* n_pairs x 7 */, int* pair_shared, int* pair_support, int* pair_winner, double* pair_rms_deg, double* pair_rms_m,
+                int* pair_status, double* cam_T_c0 /* n_cams x 7 */, int* cam_parent, int* cam_status);
+/* Mean kernel times in ms, `reps` launches back to back between two events each: kernel_ms[0] the candidates, [1] the vote (quadratic in
+ * the shared frames), [2] the winner and the refit.  All zero when no pair shares a frame.  VC_ERR_BAD_ARG also for reps < 1. */
+int vc_time_seed_rig(int device, int n_frames, int n_cams, const unsigned char* view_ok, const double* view_T_cw, double tol_deg, int min_support,
+                     int reps, double kernel_ms[3]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,6 +12,7 @@
 #include <cmath>
 #include <stdexcept>
 #include <cstring>
+#include <limits>
 #include <string>
 #include <vector>
 
@@ -124,6 +125,30 @@ inline SeedImuResult SeedImu(int device, const std::vector<double>& frame_t, con
     if ((size_t)n_coarse <= r.coarse_lags.size()) break;
   }
   r.coarse_lags.resize((size_t)n_coarse); r.coarse_J.resize((size_t)n_coarse);
+  return r;
+}
+
+// The rig seed: every camera's pose relative to camera 0 from the views it shares (vc_seed_rig; on the device, no handle).  view_ok
+// [n_frames x n_cams], view_T_cw [n_frames x n_cams x 7]; a refused pair or a camera not reached keeps the fill (NaN poses, -1 counts).
+struct SeedRigResult {
+  std::vector<double> pair_T_ab, pair_rms_deg, pair_rms_m, cam_T_c0;      // per pair 7, 1, 1; per camera 7
+  std::vector<int> pair_shared, pair_support, pair_winner, pair_status, cam_parent, cam_status;
+};
+inline SeedRigResult SeedRig(int device, int n_cams, const std::vector<unsigned char>& view_ok, const std::vector<double>& view_T_cw, double tol_deg = 3.0,
+                             int min_support = 3) {
+  if (n_cams < 1 || view_ok.size() % (size_t)n_cams != 0 || view_T_cw.size() != 7 * view_ok.size()) throw std::runtime_error("vicalib_amd: SeedRig: array sizes disagree");
+  const size_t nf = view_ok.size() / (size_t)n_cams, np = (size_t)n_cams * (n_cams - 1) / 2, pad = np ? np : 1;
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  SeedRigResult r;
+  r.pair_T_ab.assign(7 * pad, nan); r.pair_rms_deg.assign(pad, nan); r.pair_rms_m.assign(pad, nan); r.cam_T_c0.assign(7 * (size_t)n_cams, nan);
+  r.pair_shared.assign(pad, 0); r.pair_support.assign(pad, -1); r.pair_winner.assign(pad, -1); r.pair_status.assign(pad, -1);
+  r.cam_parent.assign((size_t)n_cams, -1); r.cam_status.assign((size_t)n_cams, -1);
+  const unsigned char none = 0;
+  vc_checked(vc_seed_rig(device, (int)nf, n_cams, nf ? view_ok.data() : &none, nf ? view_T_cw.data() : &nan, tol_deg, min_support, r.pair_T_ab.data(),
+                         r.pair_shared.data(), r.pair_support.data(), r.pair_winner.data(), r.pair_rms_deg.data(), r.pair_rms_m.data(), r.pair_status.data(),
+                         r.cam_T_c0.data(), r.cam_parent.data(), r.cam_status.data()), "SeedRig");
+  r.pair_T_ab.resize(7 * np); r.pair_rms_deg.resize(np); r.pair_rms_m.resize(np);
+  r.pair_shared.resize(np); r.pair_support.resize(np); r.pair_winner.resize(np); r.pair_status.resize(np);
   return r;
 }
 

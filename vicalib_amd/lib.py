@@ -55,6 +55,7 @@ SYMBOLS = [
     "vc_depthcal_sums", "vc_depthcal_fit", "vc_depthcal_get_fit", "vc_depthcal_set_fit", "vc_depthcal_apply", "vc_time_depthcal",
     "vc_allan_create", "vc_allan_destroy", "vc_allan_get", "vc_allan_static", "vc_allan_set_range", "vc_allan_run", "vc_time_allan", "vc_allan_factors", "vc_allan_fit",
     "vc_seed_imu_sweep", "vc_seed_imu", "vc_time_seed_imu",
+    "vc_seed_rig", "vc_time_seed_rig",
 ]
 
 
@@ -287,6 +288,47 @@ def time_seed_imu(frame_t, frame_q_wc, frame_ok, imu_t, gyro, accel, lags, max_g
     _check(load().vc_time_seed_imu(int(device), len(ft), _d(ft), _d(fq), ok.ctypes.data_as(C.c_void_p), len(it), _d(it), _d(g), _d(a), C.c_double(max_gap_s),
                                    int(min_intervals), len(lags), _d(lags), int(reps), _d(ms)), "time_seed_imu")
     return dict(prepare=ms[0], sweep=ms[1], gravity=ms[2])
+
+
+def _seed_rig_arrays(view_ok, view_T_cw):
+    ok = np.ascontiguousarray(np.asarray(view_ok) != 0, dtype=np.uint8)
+    T = np.ascontiguousarray(view_T_cw, dtype=np.float64)
+    if ok.ndim != 2 or ok.shape[1] < 1 or T.shape != ok.shape + (7,):
+        raise VicalibError("seed_rig: view_ok needs the shape [n_frames, n_cams] with at least one camera, view_T_cw the shape [n_frames, n_cams, 7]")
+    pad = lambda a, shape, dt: a if a.size else np.zeros(shape, dtype=dt)
+    return ok.shape[0], ok.shape[1], pad(ok, 1, np.uint8), pad(T, 7, np.float64)
+
+
+def seed_rig(view_ok, view_T_cw, tol_deg=3.0, min_support=3, device=0, out=None):
+    """Every camera's pose relative to camera 0 from the views it shares, on the device (vc_seed_rig).  view_ok [n_frames, n_cams];
+    view_T_cw [n_frames, n_cams, 7]: target into camera, [qx qy qz qw tx ty tz]; a view that is not ok is never read.  Returns, per pair (a < b)
+    in the order (0,1), (0,2) .. (1,2) ..: pair_T_ab [n_pairs, 7] (camera b into camera a), pair_shared, pair_support, pair_winner, pair_rms_deg,
+    pair_rms_m, pair_status (0 ok, 1 no shared frame, 2 support below min_support); per camera: cam_T_c0 [n_cams, 7] (camera 0 into camera c),
+    cam_parent, cam_status (0 reached, 1 not connected).  `out` may hold pre-filled arrays of those names: a refused pair or a camera not
+    reached leaves its rows as they were (the default fill is NaN, -1 for the counts)."""
+    nf, nc, ok, T = _seed_rig_arrays(view_ok, view_T_cw)
+    n_pairs = nc * (nc - 1) // 2
+    out = dict(out or {})
+    f64 = lambda k, shape: out.get(k, np.full(shape, np.nan))
+    i32 = lambda k, n: out.get(k, np.full(n, -1, dtype=np.int32))
+    r = dict(pair_T_ab=f64("pair_T_ab", (n_pairs, 7)), pair_shared=i32("pair_shared", n_pairs), pair_support=i32("pair_support", n_pairs),
+             pair_winner=i32("pair_winner", n_pairs), pair_rms_deg=f64("pair_rms_deg", n_pairs), pair_rms_m=f64("pair_rms_m", n_pairs),
+             pair_status=i32("pair_status", n_pairs), cam_T_c0=f64("cam_T_c0", (nc, 7)), cam_parent=i32("cam_parent", nc), cam_status=i32("cam_status", nc))
+    for k, a in r.items():
+        assert a.flags.c_contiguous and a.dtype == (np.float64 if k in ("pair_T_ab", "pair_rms_deg", "pair_rms_m", "cam_T_c0") else np.int32), k
+    ip = lambda a: (a if a.size else np.zeros(1, dtype=a.dtype)).ctypes.data_as(C.c_void_p)
+    _check(load().vc_seed_rig(int(device), nf, nc, ip(ok), ip(T), C.c_double(tol_deg), int(min_support), ip(r["pair_T_ab"]), ip(r["pair_shared"]),
+                              ip(r["pair_support"]), ip(r["pair_winner"]), ip(r["pair_rms_deg"]), ip(r["pair_rms_m"]), ip(r["pair_status"]), ip(r["cam_T_c0"]),
+                              ip(r["cam_parent"]), ip(r["cam_status"])), "seed_rig")
+    return r
+
+
+def time_seed_rig(view_ok, view_T_cw, tol_deg=3.0, min_support=3, device=0, reps=10):
+    """mean kernel times in ms (vc_time_seed_rig: HIP events, launches back to back): candidates, support (the quadratic vote), finish, total"""
+    nf, nc, ok, T = _seed_rig_arrays(view_ok, view_T_cw)
+    ms = np.zeros(3)
+    _check(load().vc_time_seed_rig(int(device), nf, nc, ok.ctypes.data_as(C.c_void_p), _d(T), C.c_double(tol_deg), int(min_support), int(reps), _d(ms)), "time_seed_rig")
+    return dict(candidates=ms[0], support=ms[1], finish=ms[2], total=float(ms.sum()))
 
 
 def load():
