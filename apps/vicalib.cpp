@@ -199,6 +199,12 @@ struct Run {
   std::vector<std::vector<double>> original_uv;
   struct DotBiasRow { long frame; int cam, dot; double bu, bv, radius_px; int status; };
   std::vector<DotBiasRow> dot_bias_rows;
+  // -refine_target_rounds / -target_points: the target by dot id (x 3), as the detections name it (nominal) and as it is used (points); the last
+  // round's corner counts and statuses for -refine_target_output
+  int refine_rounds = 0;
+  bool quiet_load = false;
+  std::vector<double> target_nominal, target_points;
+  std::vector<int> target_seen, target_corners, target_status;
 };
 // what a calibrator is rebuilt from between the rounds of -dot_bias_rounds: the result of the round before
 struct Restart {
@@ -262,6 +268,18 @@ static bool CheckFlags(Run& s, int* rc) {
     for (const char* f : {"dot_radius", "grid_large_rad", "grid_small_rad"})
       if (!(FlagDouble(f) >= 0.0) || !std::isfinite(FlagDouble(f)))
         return FlagError(rc, std::string("illegal value for flag '") + f + "' with -dot_bias_rounds: expected a radius in metres, at least 0");
+  }
+  s.refine_rounds = (int)FlagInt("refine_target_rounds");
+  if (s.refine_rounds < 0) return FlagError(rc, "illegal value for flag 'refine_target_rounds': expected at least 0");
+  if (s.refine_rounds > 0) {
+    if (FlagInt("gpus") > 1) return FlagError(rc, "-refine_target_rounds needs -gpus 1: the rounds rebuild one calibrator from its own result");
+    if (s.holdout_every > 0) return FlagError(rc, "-refine_target_rounds and -holdout_every exclude each other: held-out frames would be scored against another target");
+    if (s.dot_bias_rounds > 0) return FlagError(rc, "-refine_target_rounds and -dot_bias_rounds exclude each other");
+    if (!FlagString("imu").empty() && FlagBool("calibrate_imu"))
+      return FlagError(rc, "-refine_target_rounds needs -nocalibrate_imu: the IMU ties the frame poses the target step marginalises freely");
+    if (!(FlagDouble("refine_target_sigma") > 0.0) || !std::isfinite(FlagDouble("refine_target_sigma")) || !(1.0 / (FlagDouble("refine_target_sigma") * FlagDouble("refine_target_sigma")) < 1e300))
+      return FlagError(rc, "illegal value for flag 'refine_target_sigma': expected a distance in metres, more than 0");
+    if (FlagString("refine_target_output").empty()) return FlagError(rc, "-refine_target_rounds needs a file name in -refine_target_output");
   }
   if (FlagBool("seed_imu")) {
     if (FlagString("imu").empty()) return FlagError(rc, "-seed_imu needs -imu: there is no log to seed from");
@@ -764,7 +782,7 @@ static bool LoadCalibrators(Run& s, int* rc, const Restart* from = nullptr) {
       for (const auto& kv : DetectionsByFrame(s.channels[c], frame_index, s.grid_w * s.grid_h)) {
         pw.clear(); pc.clear();
         AppendCorners(kv.second, &pw, &pc);
-        if (FlagBool("output_conics") && !from)
+        if (FlagBool("output_conics") && !from && !s.quiet_load)
           for (const Detection* d : kv.second) std::printf("%ld,%d,%.10g,%.10g,%.10g,%.10g,%.10g\n", d->frame, d->dot, d->u, d->v, d->X, d->Y, d->Z);
         cal.AddObservations(kv.first, c, (int)kv.second.size(), pw.data(), pc.data());
         if (s.want_report) s.rank_corners[r].insert(s.rank_corners[r].end(), kv.second.begin(), kv.second.end());
@@ -792,7 +810,7 @@ static bool LoadCalibrators(Run& s, int* rc, const Restart* from = nullptr) {
     cal.SetCalibrateImu(s.calibrate_imu);
     cal.SetRemoveOutliers(FlagBool("remove_outliers"), FlagDouble("outlier_threshold"));
   }
-  if (from) return true;
+  if (from || s.quiet_load) return true;
   std::fprintf(stderr, "I %zu cameras, %zu frames on %d GPU(s) (%d with a PnP seed), %ld corner observations, %zu IMU samples\n", n_cam, n_frames, n_gpus, seeded, n_obs, s.imu.time.size());
   return true;
 }
@@ -828,18 +846,29 @@ static void Solve(Run& s) {
   for (auto& c : s.cals) for (size_t i = 0; i < c->NumFrames(); ++i) s.all_frames.push_back(c->GetFrame(i));
 }
 
+// ---- what the rounds of -dot_bias_rounds and -refine_target_rounds share: the result as a start, and the calibrator rebuilt from it (with whatever the
+// round changed in the detections) and solved again
+static Restart RestartAtResult(Run& s) {
+  Restart at;
+  vic::ViCalibrator& cal = *s.cals[0];
+  at.cameras = CamerasAtResult(cal, s.input_cameras);
+  at.frames = s.all_frames;
+  at.biases = cal.GetBiases(); at.scale_factor = cal.GetScaleFactor(); at.gravity = cal.GetGravity(); at.time_offset = cal.time_offset();
+  return at;
+}
+static bool RebuildAndSolve(Run& s, const Restart& at, int* rc) {
+  s.cals.clear(); s.rank_corners.clear(); s.all_frames.clear();
+  if (!LoadCalibrators(s, rc, &at)) return false;
+  Solve(s);
+  return true;
+}
+
 // ---- one round of -dot_bias_rounds: the bias of every calibrated observation predicted at the result (its cameras and T_ck, the frames' T_wk) in
 // one batch on -device, subtracted from the ORIGINAL detections (nothing accumulates round over round), the calibrator rebuilt from the result
 // and solved again.  An observation whose bias cannot be predicted (status != 0) keeps its original pixel.
 static bool DotBiasRound(Run& s, int round, int* rc) {
   const size_t n_cam = s.channels.size();
-  Restart at;
-  {
-    vic::ViCalibrator& cal = *s.cals[0];
-    at.cameras = CamerasAtResult(cal, s.input_cameras);
-    at.frames = s.all_frames;
-    at.biases = cal.GetBiases(); at.scale_factor = cal.GetScaleFactor(); at.gravity = cal.GetGravity(); at.time_offset = cal.time_offset();
-  }
+  const Restart at = RestartAtResult(s);
   const std::vector<double> rmse_before = s.cals[0]->GetCameraProjRMSE();
   if (s.original_uv.empty()) {
     s.original_uv.resize(n_cam);
@@ -879,9 +908,7 @@ static bool DotBiasRound(Run& s, int round, int* rc) {
     if (ok) { sum2[c] += bu * bu + bv * bv; worst[c] = std::max(worst[c], std::sqrt(bu * bu + bv * bv)); } else ++refused[c];
     s.dot_bias_rows.push_back(Run::DotBiasRow{d->frame, (int)c, d->dot, bu, bv, ok ? db.radius_px[i] : 0.0, db.status[i]});
   }
-  s.cals.clear(); s.rank_corners.clear(); s.all_frames.clear();
-  if (!LoadCalibrators(s, rc, &at)) return false;
-  Solve(s);
+  if (!RebuildAndSolve(s, at, rc)) return false;
   const std::vector<double> rmse_after = s.cals[0]->GetCameraProjRMSE();
   long refused_all = 0;
   for (size_t c = 0; c < n_cam; ++c) {
@@ -901,6 +928,119 @@ static void WriteDotBiasCsv(const Run& s) {
   if (!f) { std::fprintf(stderr, "E cannot write dot_bias.csv into %s\n", dir.c_str()); return; }
   std::fprintf(f, "frame,camera,dot,bu,bv,radius_px,status\n");
   for (const Run::DotBiasRow& r : s.dot_bias_rows) std::fprintf(f, "%ld,%d,%d,%.10g,%.10g,%.10g,%d\n", r.frame, r.cam, r.dot, r.bu, r.bv, r.radius_px, r.status);
+  std::fclose(f);
+}
+
+// ---- -target_points / -refine_target_rounds: the target by dot id.  nominal = what the detections say (the grid); points = nominal, or the rows of
+// -target_points, which every detection's p_w is then taken from.
+static void TargetIntoDetections(Run& s) {
+  for (Channel& ch : s.channels)
+    for (Detection& d : ch.det)
+      if (d.dot >= 0 && (size_t)d.dot < s.target_seen.size()) { d.X = s.target_points[3 * (size_t)d.dot]; d.Y = s.target_points[3 * (size_t)d.dot + 1]; d.Z = s.target_points[3 * (size_t)d.dot + 2]; }
+}
+static bool TargetTables(Run& s, int* rc) {
+  const size_t P = (size_t)s.grid_w * (size_t)s.grid_h;
+  s.target_nominal.assign(3 * P, 0.0); s.target_seen.assign(P, 0); s.target_corners.assign(P, 0); s.target_status.assign(P, 1);
+  for (const Channel& ch : s.channels)
+    for (const Detection& d : ch.det)
+      if (d.dot >= 0 && (size_t)d.dot < P && !s.target_seen[(size_t)d.dot]) {
+        s.target_seen[(size_t)d.dot] = 1;
+        s.target_nominal[3 * (size_t)d.dot] = d.X; s.target_nominal[3 * (size_t)d.dot + 1] = d.Y; s.target_nominal[3 * (size_t)d.dot + 2] = d.Z;
+      }
+  s.target_points = s.target_nominal;
+  const std::string file = FlagString("target_points");
+  if (file.empty()) return true;
+  FILE* f = std::fopen(file.c_str(), "r");
+  if (!f) return Stop(rc, 1, "F cannot read -target_points %s\n", file.c_str());
+  char line[512];
+  long rows = 0;
+  while (std::fgets(line, sizeof(line), f)) {
+    int dot = -1; double x, y, z;
+    if (std::sscanf(line, "%d,%lf,%lf,%lf", &dot, &x, &y, &z) != 4) continue;      // (the header)
+    if (dot < 0 || (size_t)dot >= P || !std::isfinite(x) || !std::isfinite(y) || !std::isfinite(z)) { std::fclose(f); return Stop(rc, 1, "F -target_points %s: dot %d is not a dot of the %d x %d target or its position is not finite\n", file.c_str(), dot, s.grid_w, s.grid_h); }
+    s.target_points[3 * (size_t)dot] = x; s.target_points[3 * (size_t)dot + 1] = y; s.target_points[3 * (size_t)dot + 2] = z;
+    ++rows;
+  }
+  std::fclose(f);
+  if (rows == 0) return Stop(rc, 1, "F -target_points %s holds no dot\n", file.c_str());
+  std::fprintf(stderr, "I target: %ld dots from %s\n", rows, file.c_str());
+  return true;      // (the detections keep the nominal target until the frames have their pose seeds: SeedThenMeasuredTarget)
+}
+// -target_points: the pose seed is a PLANAR PnP and refuses a target that is not flat, so the calibrators are loaded and seeded with the nominal
+// target first, then loaded again with the measured one and given those seeds.  Everything else is the fresh start it would have been.
+static bool SeedThenMeasuredTarget(Run& s, int* rc) {
+  std::vector<std::vector<vic::Se3>> seeds(s.cals.size());
+  for (size_t r = 0; r < s.cals.size(); ++r)
+    for (size_t i = 0; i < s.cals[r]->NumFrames(); ++i) seeds[r].push_back(s.cals[r]->GetFrame(i).t_wp_);
+  TargetIntoDetections(s);
+  s.cals.clear(); s.rank_corners.clear();
+  s.quiet_load = true;
+  const bool ok = LoadCalibrators(s, rc);
+  s.quiet_load = false;
+  if (!ok) return false;
+  for (size_t r = 0; r < s.cals.size(); ++r)
+    for (size_t i = 0; i < seeds[r].size(); ++i) s.cals[r]->SetFramePose((int)i, seeds[r][i]);
+  return true;
+}
+// one round of -refine_target_rounds: the step of DESIGN 4.22 at the result over all calibrated observations, the calibrator rebuilt from the result with
+// the refined target, solved again.  A singular result or a point that stayed unrefined: a W line, the round is skipped and the target kept.
+static bool RefineTargetRound(Run& s, int round, int* rc) {
+  const size_t n_cam = s.channels.size(), P = s.target_seen.size();
+  const Restart at = RestartAtResult(s);
+  const std::vector<double> rmse_before = s.cals[0]->GetCameraProjRMSE();
+  std::vector<int> model, flags, tile_frame, tile_cam, point_id;
+  std::vector<double> params, T_ck, T_wk, p_c;
+  std::vector<long long> tile_off(1, 0);
+  for (size_t c = 0; c < n_cam; ++c) {
+    model.push_back(at.cameras[c].model);
+    for (size_t j = 0; j < 10; ++j) params.push_back(j < at.cameras[c].params.size() ? at.cameras[c].params[j] : 0.0);
+    T_ck.insert(T_ck.end(), at.cameras[c].T_ck.v.begin(), at.cameras[c].T_ck.v.end());
+    flags.push_back((c == 0 ? 0 : 3) | (FlagBool("calibrate_intrinsics") ? 4 : 0));      // (the calibrator's layout without an IMU: camera 0 carries the rig)
+  }
+  for (const vic::VicalibFrame& fr : at.frames) T_wk.insert(T_wk.end(), fr.t_wp_.v.begin(), fr.t_wp_.v.end());
+  const std::map<long, int> fit_index = FrameIndex(s.frame_ids);
+  for (size_t c = 0; c < n_cam; ++c)
+    for (const auto& kv : DetectionsByFrame(s.channels[c], fit_index, s.grid_w * s.grid_h)) {
+      tile_frame.push_back(kv.first); tile_cam.push_back((int)c);
+      for (const Detection* d : kv.second) { point_id.push_back(d->dot); p_c.push_back(d->u); p_c.push_back(d->v); }
+      tile_off.push_back((long long)point_id.size());
+    }
+  const double sigma = FlagDouble("refine_target_sigma");
+  vic::TargetRefineResult tr;
+  try { tr = vic::TargetRefineBatch(Device(), model, params, T_ck, flags, T_wk, tile_frame, tile_cam, tile_off, point_id, p_c, s.target_points, s.target_nominal, 1.0 / (sigma * sigma)); }
+  catch (const std::exception& e) { return Stop(rc, 3, "F -refine_target_rounds: %s (device %d)\n", e.what(), Device()); }
+  int refined = 0, unobserved = 0;
+  for (size_t p = 0; p < P; ++p) (tr.point_status[p] == 0 ? refined : unobserved) += 1;
+  s.target_corners = tr.point_corners; s.target_status = tr.point_status;
+  if (tr.status != 0 || unobserved > 0) {
+    std::fprintf(stderr, "W target round %d skipped, the target is kept: %s (%d of %zu points without a usable corner)\n", round,
+                 tr.status != 0 ? "the system is singular" : "a point stayed unrefined", unobserved, P);
+    return true;
+  }
+  double sum2[3] = {0, 0, 0}, worst = 0.0;
+  for (size_t p = 0; p < P; ++p) {
+    double n2 = 0.0;
+    for (int a = 0; a < 3; ++a) { const double d = tr.refined[3 * p + a] - s.target_nominal[3 * p + a]; sum2[a] += d * d; n2 += d * d; }
+    worst = std::max(worst, std::sqrt(n2));
+  }
+  s.target_points = tr.refined;
+  TargetIntoDetections(s);
+  if (!RebuildAndSolve(s, at, rc)) return false;
+  const std::vector<double> rmse_after = s.cals[0]->GetCameraProjRMSE();
+  std::string rm;
+  for (size_t c = 0; c < n_cam; ++c) { char b[96]; std::snprintf(b, sizeof(b), "%s%.6g -> %.6g", c ? ", " : "", rmse_before[c], rmse_after[c]); rm += b; }
+  std::fprintf(stderr, "I target round %d: offset rms %.4f %.4f %.4f mm, max %.4f mm, %d points refined, %d unobserved, gauge rank %d, RMSE %s px\n", round,
+               1e3 * std::sqrt(sum2[0] / P), 1e3 * std::sqrt(sum2[1] / P), 1e3 * std::sqrt(sum2[2] / P), 1e3 * worst, refined, unobserved, tr.gauge_rank, rm.c_str());
+  return true;
+}
+static void WriteTargetCsv(Run& s) {
+  const std::string file = FlagString("refine_target_output");
+  FILE* f = std::fopen(file.c_str(), "w");
+  if (!f) { std::fprintf(stderr, "E cannot write %s\n", file.c_str()); s.incomplete.push_back("-refine_target_output: the file is"); return; }
+  std::fprintf(f, "dot,x,y,z,nx,ny,nz,corners,status\n");
+  for (size_t p = 0; p < s.target_seen.size(); ++p)
+    std::fprintf(f, "%zu,%.17g,%.17g,%.17g,%.17g,%.17g,%.17g,%d,%d\n", p, s.target_points[3 * p], s.target_points[3 * p + 1], s.target_points[3 * p + 2], s.target_nominal[3 * p],
+                 s.target_nominal[3 * p + 1], s.target_nominal[3 * p + 2], s.target_corners[p], s.target_status[p]);
   std::fclose(f);
 }
 
@@ -1212,15 +1352,21 @@ int main(int argc, char** argv) {
   if (!CheckFlags(s, &rc) || !RunStandAloneMode(s, &rc) || !ReadSensors(s, &rc)) return rc;
   if (s.dot_bias_rounds > 0 && !DotRadii(s, &rc)) return rc;
   if (!StartCameras(s, &rc) || !ChooseFrames(s, &rc)) return rc;
+  if ((s.refine_rounds > 0 || !FlagString("target_points").empty()) && !TargetTables(s, &rc)) return rc;
   if (FlagBool("seed_focal") && !SeedFocal(s, &rc)) return rc;
   if (FlagString("seed_rig") != "off" && !SeedRig(s, &rc)) return rc;
   s.image_time_offset = InitialTimeOffset(s);
   if (FlagBool("seed_imu") && !SeedImu(s, &rc)) return rc;
-  if (!LoadCalibrators(s, &rc) || !SetupCommunicator(s, &rc)) return rc;
+  if (!LoadCalibrators(s, &rc)) return rc;
+  if (!FlagString("target_points").empty() && !SeedThenMeasuredTarget(s, &rc)) return rc;
+  if (!SetupCommunicator(s, &rc)) return rc;
   Solve(s);
   for (int round = 1; round <= s.dot_bias_rounds; ++round)
     if (!DotBiasRound(s, round, &rc)) return rc;
+  for (int round = 1; round <= s.refine_rounds; ++round)
+    if (!RefineTargetRound(s, round, &rc)) return rc;
   PrintResults(s);
+  if (s.refine_rounds > 0) WriteTargetCsv(s);
   if (s.want_report) ResidualReport(s);
   if (s.dot_bias_rounds > 0 && !FlagString("report_dir").empty()) WriteDotBiasCsv(s);
   if (!s.held_ids.empty()) ScoreHeldOut(s);

@@ -55,6 +55,12 @@ static void DefineEngineFlags() {      // vicalib-engine.cc:30-104
          "its centre) at the result on the GPU, subtract it from the original detections and solve again from the result (0: off; needs -gpus 1, no -holdout_every).  "
          "The radii are -grid_large_rad / -grid_small_rad by the target's pattern (-grid_pattern_file, or generated from -grid_height / -grid_width / -grid_seed), or -dot_radius.");
   Define("dot_radius", "double", "0", "With -dot_bias_rounds: the radius of every dot (m), instead of the large / small pattern (0: use the pattern).");
+  Define("refine_target_rounds", "int32", "0", "After the solve, this many times: refine the 3-D positions of the target's dots at the result on the GPU (one Gauss-Newton step, "
+         "frame poses and shared camera parameters marginalised, position / orientation / size of the target held at the nominal one), rebuild the calibrator from the result "
+         "with the refined target and solve again (0: off; needs -gpus 1, no -holdout_every, no -dot_bias_rounds, no calibrated IMU).");
+  Define("refine_target_sigma", "double", "0.01", "With -refine_target_rounds: how far a dot may be expected from its nominal position (m); the prior's weight is 1 / sigma^2.");
+  Define("refine_target_output", "string", "target_refined.csv", "With -refine_target_rounds: the refined target, dot,x,y,z,nx,ny,nz,corners,status per dot.");
+  Define("target_points", "string", "", "A file written by -refine_target_output: the calibration starts from that measured target instead of the grid (the nominal target stays the grid).");
   Define("gyro_sigma", "double", "5.3088444e-5", "Sigma of gyroscope measurements.");
   Define("accel_sigma", "double", "0.001883649", "Sigma of accel measurements.");
   Define("remove_outliers", "bool", "false", "Remove outliers and re-optimise.");

@@ -132,6 +132,37 @@ int vc_dot_bias_batch(int device, int n_views, const int* view_model, const doub
 /* Mean time in ms of the batch's kernel alone on that input: `reps` launches back to back between two events, after one that warms up. */
 int vc_time_dot_bias_batch(int device, int n_views, const int* view_model, const double* view_K, const double* view_T_cw, const int* view_off,
                            const double* p_w, const double* radius, int reps, double* kernel_ms);
+/* One Gauss-Newton step on the calibration target's points with the frame poses AND the shared camera columns marginalised, on the device
+   (vicalib_amd/csrc/vc_target_refine.hpp has the definition).  The rig is that of vc_selector_create: n_cameras <= 8 cameras
+   (model, params x 10, T_ck x 7, cam_flags = kCamRotFree 1 | kCamTransFree 2 | kCamKFree 4, the shared columns D = sum of the cameras' free
+   columns <= 64, D = 0 allowed); n_frames poses T_wk (x 7); tile t holds corners tile_off[t] .. tile_off[t+1]-1 of point_id / p_c (measured
+   pixels, x 2) of (tile_frame[t], tile_cam[t]); points is the current target and nominal the printed one (n_points x 3 each,
+   4 <= n_points <= 1024); lambda > 0 is the prior's weight in px^2 / m^2 on the offset from nominal.  Corner rows are at unit weight, without
+   robust loss; a corner at camera depth <= 0 (any model but kb4) enters nothing and is counted behind.  frame_status: n_frames x
+   [status, corners, behind], status 0 usable, 1 underdetermined (fewer than 4 corners or a pivot of J_f^T J_f at or below 1e-12 x its largest
+   diagonal entry: the frame adds nothing), 2 usable with corners behind.  point_status: 0 refined, 1 no usable corner (left out of the system
+   and of the gauge; its row of refined is its row of points, bit for bit); point_corners: the usable corners of every point.  The similarity
+   tangent at nominal about the observed points' centroid is projected out: Q^T (refined - nominal) = 0, gauge_rank is the number of its
+   columns kept (7 unless the observed points are degenerate).  result_status: 0 ok, 1 singular (a pivot of the dense factorisation at or
+   below 1e-12 x the largest diagonal entry: refined, cost and predicted_decrease are left untouched).  cost = 1/2 sum r^2 over the usable
+   corners; predicted_decrease = 1/2 d . (Pi b).
+   VC_ERR_BAD_ARG before any device call (a null pointer, offsets that decrease or start below 0, a frame, camera or point id out of range,
+   an unknown model or flag, values that are not finite, lambda not finite and positive, n_points < 4); VC_ERR_UNSUPPORTED for D > 64,
+   n_points > 1024 or n_frames > 2^20; VC_ERR_NO_DEVICE without that device or when a HIP call fails (device memory included: the dense system is
+   (3 n_points)^2 doubles, 75 MB at the limit, the (frame, point) table n_frames x n_points ints): there is no host fallback.  No floating-point atomic: two runs give the same bits. */
+int vc_target_refine_batch(int device, int n_cameras, const int* model, const double* params /* n_cameras x 10 */,
+                           const double* T_ck /* n_cameras x 7 */, const int* cam_flags, int n_frames, const double* T_wk /* n_frames x 7 */,
+                           int n_tiles, const int* tile_frame, const int* tile_cam, const long long* tile_off /* n_tiles + 1 */,
+                           const int* point_id, const double* p_c /* x 2 */, const double* points /* n_points x 3 */,
+                           const double* nominal /* n_points x 3 */, int n_points, double lambda, double* refined /* n_points x 3 */,
+                           int* point_status, int* point_corners, int* frame_status /* n_frames x 3 */, int* gauge_rank, int* result_status,
+                           double* cost, double* predicted_decrease);
+/* Mean time in ms of the step's six stages alone on that input (sweep, assembly, elimination of the shared columns, gauge, factorisation,
+   solve): `reps` runs of the whole step with events between the stages, after one run that warms up.  kernel_ms: 6 doubles. */
+int vc_time_target_refine_batch(int device, int n_cameras, const int* model, const double* params, const double* T_ck, const int* cam_flags,
+                                int n_frames, const double* T_wk, int n_tiles, const int* tile_frame, const int* tile_cam,
+                                const long long* tile_off, const int* point_id, const double* p_c, const double* points, const double* nominal,
+                                int n_points, double lambda, int reps, double* kernel_ms /* 6 */);
 /* AddObservation(frame, cam, p_w, p_c, time) :385-468, in bulk: n corners of one (frame, camera) */
 int vc_add_observations(vc_calibrator* h, int frame, int camera, int n, const double* p_w /* n x 3 */,
                         const double* p_c /* n x 2 */);

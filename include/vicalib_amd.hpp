@@ -91,6 +91,37 @@ inline DotBiasResult DotBiasBatch(int device, const std::vector<int>& view_model
   return r;
 }
 
+// One Gauss-Newton step on the target's points with the frame poses and the shared camera columns marginalised (vc_target_refine_batch; on the
+// device, no handle).  The rig as for vc_selector_create (model, params x 10, T_ck x 7, flags per camera), poses x 7 per frame, tile t = corners
+// tile_off[t] .. tile_off[t+1]-1 of point_id / p_c (x 2) of (tile_frame[t], tile_cam[t]); points and nominal x 3 per target point.
+struct TargetRefineResult {
+  std::vector<double> refined;                        // x 3 per point; a singular result returns `points`
+  std::vector<int> point_status, point_corners;       // 0 refined, 1 no usable corner (its row of refined is its row of points)
+  std::vector<int> frame_status;                      // x 3 per frame: status, corners, behind
+  int gauge_rank = 0, status = -1;                    // status: 0 ok, 1 singular
+  double cost = 0, predicted_decrease = 0;
+};
+inline TargetRefineResult TargetRefineBatch(int device, const std::vector<int>& model, const std::vector<double>& params, const std::vector<double>& T_ck,
+                                            const std::vector<int>& cam_flags, const std::vector<double>& T_wk, const std::vector<int>& tile_frame,
+                                            const std::vector<int>& tile_cam, const std::vector<long long>& tile_off, const std::vector<int>& point_id,
+                                            const std::vector<double>& p_c, const std::vector<double>& points, const std::vector<double>& nominal, double lambda) {
+  const size_t nc = model.size(), nf = T_wk.size() / 7, nt = tile_frame.size(), np = points.size() / 3;
+  if (params.size() != 10 * nc || T_ck.size() != 7 * nc || cam_flags.size() != nc || T_wk.size() != 7 * nf || tile_cam.size() != nt || tile_off.size() != nt + 1 ||
+      p_c.size() != 2 * point_id.size() || nominal.size() != points.size() || points.size() != 3 * np || (size_t)tile_off.back() > point_id.size())
+    throw std::runtime_error("vicalib_amd: TargetRefineBatch: array sizes disagree");
+  TargetRefineResult r;
+  r.refined = points; r.refined.resize(3 * np + 1);
+  r.point_status.assign(np + 1, -1); r.point_corners.assign(np + 1, 0); r.frame_status.assign(3 * nf + 1, 0);
+  const int none_i[1] = {0};
+  const double none_d[2] = {0, 0};
+  vc_checked(vc_target_refine_batch(device, (int)nc, model.data(), params.data(), T_ck.data(), cam_flags.data(), (int)nf, T_wk.data(), (int)nt,
+                                    nt ? tile_frame.data() : none_i, nt ? tile_cam.data() : none_i, tile_off.data(), point_id.empty() ? none_i : point_id.data(),
+                                    p_c.empty() ? none_d : p_c.data(), points.data(), nominal.data(), (int)np, lambda, r.refined.data(), r.point_status.data(),
+                                    r.point_corners.data(), r.frame_status.data(), &r.gauge_rank, &r.status, &r.cost, &r.predicted_decrease), "TargetRefineBatch");
+  r.refined.resize(3 * np); r.point_status.resize(np); r.point_corners.resize(np); r.frame_status.resize(3 * nf);
+  return r;
+}
+
 // The inertial seed (vc_seed_imu, vc_seed_imu_sweep; on the device, no handle): the rotation camera <- IMU, the time offset, the gyro bias and the
 // direction of gravity from the frames' camera rotations (frame_q_wc: n x 4, [x y z w]; frame_ok: 0 = no rotation) and the IMU log.
 struct SeedImuResult {

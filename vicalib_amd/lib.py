@@ -56,6 +56,7 @@ SYMBOLS = [
     "vc_allan_create", "vc_allan_destroy", "vc_allan_get", "vc_allan_static", "vc_allan_set_range", "vc_allan_run", "vc_time_allan", "vc_allan_factors", "vc_allan_fit",
     "vc_seed_imu_sweep", "vc_seed_imu", "vc_time_seed_imu",
     "vc_seed_rig", "vc_time_seed_rig",
+    "vc_target_refine_batch", "vc_time_target_refine_batch",
 ]
 
 
@@ -231,6 +232,64 @@ def time_dot_bias_batch(models, params, T_cw, view_off, p_w, radius, device=0, r
     ip = lambda a: a.ctypes.data_as(C.c_void_p)
     _check(load().vc_time_dot_bias_batch(int(device), nv, ip(m), _d(K), _d(T), ip(off), _d(p_w), _d(rad), int(reps), C.byref(ms)), "time_dot_bias_batch")
     return ms.value
+
+
+def _target_refine_arrays(cameras, poses, tile_frame, tile_cam, tile_off, point_id, p_c, points, nominal):
+    from .synth import MODEL_IDS
+    n = len(cameras)
+    model = np.array([MODEL_IDS[c[0]] if isinstance(c[0], str) else int(c[0]) for c in cameras], dtype=np.int32)
+    params = np.zeros((max(n, 1), 10))
+    for i, c in enumerate(cameras):
+        params[i, :len(c[1])] = c[1]
+    T_ck = np.ascontiguousarray([c[2] for c in cameras], dtype=np.float64).reshape(-1, 7)
+    flags = np.array([c[3] for c in cameras], dtype=np.int32)
+    poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 7)
+    tf = np.ascontiguousarray(tile_frame, dtype=np.int32).reshape(-1); tc = np.ascontiguousarray(tile_cam, dtype=np.int32).reshape(-1)
+    off = np.ascontiguousarray(tile_off, dtype=np.int64).reshape(-1)
+    pid = np.ascontiguousarray(point_id, dtype=np.int32).reshape(-1); z = np.ascontiguousarray(p_c, dtype=np.float64).reshape(-1, 2)
+    points = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3); nominal = np.ascontiguousarray(nominal, dtype=np.float64).reshape(-1, 3)
+    if len(off) != len(tf) + 1 or len(tc) != len(tf) or len(z) != len(pid) or len(points) != len(nominal) or (len(off) and off[-1] > len(pid)):
+        raise VicalibError("target_refine_batch: tile_off needs one entry more than tile_frame / tile_cam and ends within point_id, p_c one row per point_id, "
+                           "nominal one row per row of points")
+    pad = lambda a, shape, dt: a if len(a) else np.zeros(shape, dtype=dt)
+    return (n, pad(model, 1, np.int32), params, pad(T_ck, (1, 7), np.float64), pad(flags, 1, np.int32), len(poses), pad(poses, (1, 7), np.float64), len(tf),
+            pad(tf, 1, np.int32), pad(tc, 1, np.int32), off, pad(pid, 1, np.int32), pad(z, (1, 2), np.float64), pad(points, (1, 3), np.float64),
+            pad(nominal, (1, 3), np.float64), len(points))
+
+
+def target_refine_batch(cameras, poses, tile_frame, tile_cam, tile_off, point_id, p_c, points, nominal, lam, device=0, out=None):
+    """One Gauss-Newton step on the target's points, the frame poses and the shared camera columns marginalised, on the device
+    (vc_target_refine_batch).  cameras: [(model, K, T_ck, flags)] as for Selector; poses [N, 7]; tile t holds corners tile_off[t] .. tile_off[t+1]-1 of
+    point_id / p_c (measured pixels) of (tile_frame[t], tile_cam[t]); points / nominal [P, 3]; lam: the prior's weight 1 / sigma^2.  Returns refined
+    [P, 3], point_status, point_corners, frame_status, corners, behind (per frame), gauge_rank, result_status (0 ok, 1 singular), cost,
+    predicted_decrease.  `out` may hold a pre-filled refined array: a singular result leaves it, cost and predicted_decrease (NaN) as they were."""
+    a = _target_refine_arrays(cameras, poses, tile_frame, tile_cam, tile_off, point_id, p_c, points, nominal)
+    N, P = a[5], a[15]
+    out = dict(out or {})
+    refined = out.get("refined", np.full((max(P, 1), 3), np.nan))
+    assert refined.dtype == np.float64 and refined.flags.c_contiguous and refined.size >= 3 * P
+    pstat = np.full(max(P, 1), -1, dtype=np.int32); pcor = np.zeros(max(P, 1), dtype=np.int32); fstat = np.zeros((max(N, 1), 3), dtype=np.int32)
+    rank, status = C.c_int(0), C.c_int(-1)
+    cost, pred = C.c_double(np.nan), C.c_double(np.nan)
+    ip = lambda x: x.ctypes.data_as(C.c_void_p)
+    _check(load().vc_target_refine_batch(int(device), a[0], ip(a[1]), _d(a[2]), _d(a[3]), ip(a[4]), N, _d(a[6]), a[7], ip(a[8]), ip(a[9]), ip(a[10]), ip(a[11]), _d(a[12]),
+                                         _d(a[13]), _d(a[14]), P, C.c_double(lam), _d(refined), ip(pstat), ip(pcor), ip(fstat), C.byref(rank), C.byref(status),
+                                         C.byref(cost), C.byref(pred)), "target_refine_batch")
+    return dict(refined=refined[:P], point_status=pstat[:P], point_corners=pcor[:P], frame_status=fstat[:N, 0].copy(), corners=fstat[:N, 1].copy(),
+                behind=fstat[:N, 2].copy(), gauge_rank=rank.value, result_status=status.value, cost=cost.value, predicted_decrease=pred.value)
+
+
+TARGET_REFINE_STAGES = ("sweep", "assembly", "shared", "gauge", "factor", "solve")
+
+
+def time_target_refine_batch(cameras, poses, tile_frame, tile_cam, tile_off, point_id, p_c, points, nominal, lam, device=0, reps=10):
+    """mean time in ms of the six stages of target_refine_batch alone on that input (vc_time_target_refine_batch: HIP events between the stages)"""
+    a = _target_refine_arrays(cameras, poses, tile_frame, tile_cam, tile_off, point_id, p_c, points, nominal)
+    ms = np.zeros(6)
+    ip = lambda x: x.ctypes.data_as(C.c_void_p)
+    _check(load().vc_time_target_refine_batch(int(device), a[0], ip(a[1]), _d(a[2]), _d(a[3]), ip(a[4]), a[5], _d(a[6]), a[7], ip(a[8]), ip(a[9]), ip(a[10]), ip(a[11]),
+                                              _d(a[12]), _d(a[13]), _d(a[14]), a[15], C.c_double(lam), int(reps), _d(ms)), "time_target_refine_batch")
+    return dict(zip(TARGET_REFINE_STAGES, ms.tolist()))
 
 
 def _seed_imu_arrays(frame_t, frame_q_wc, frame_ok, imu_t, gyro, accel):
